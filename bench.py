@@ -11,8 +11,14 @@ second of the slowest rank. samples = frames x channels.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (HBM, algorithmic
-bytes / HIP-event kernel time) and, at N=1, `cpu_baseline` (the C oracle on the host cores).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall
+time of one timed step) and the workload. A plain run sets up, warms up, times the steps and prints that
+line; `--full` adds what takes work of its own: the bit-exact check of the whole
+batch against the source PCM, `roofline` (HBM, algorithmic bytes / HIP-event kernel time) and, at N=1,
+`cpu_baseline` (the C oracle on the host cores) and `host_entry` (the PCIe-inclusive entry).
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's shard) as float .npy files:
+`status.npy` and `frames.npy` per packet, `pcm.npy` the decoded samples [packet][frame][channel] of a
+fixed, seeded sample of the packets (all of them when they fit in 64 MB), zero behind each packet's frames.
 """
 import argparse
 import importlib
@@ -27,6 +33,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 0x5A9D
 
 
 def parse():
@@ -46,6 +54,10 @@ def parse():
     ap.add_argument("--host-entry", action="store_true", help="(default now; kept for old command lines)")
     ap.add_argument("--profile", type=int, default=0, help="synth profile (0 = SURVEY 8d music model)")
     ap.add_argument("--out-stride-pad", type=int, default=0, help="extra bytes between PCM slots (experiments)")
+    ap.add_argument("--full", action="store_true", help="also the bit-exact check, roofline, CPU baseline and host entry "
+                    "(--no-verify / --no-cpu-baseline / --no-host-entry leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0) "
+                    "as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -74,6 +86,34 @@ def host_threads():
     except Exception:
         n = os.cpu_count() or 1
     return max(1, min(n, 64))
+
+
+def dump_outputs(out_dir, d_out, d_fr, d_st, P, FL, ch, bps):
+    """What a caller of the device entry receives (status, frame count, PCM) as float .npy files. PCM as sample values
+    (float32, float64 for 32-bit samples), of a seeded sample of the packets when all of them would not fit."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    status = d_st.cpu().numpy()
+    frames = d_fr.cpu().numpy().astype(np.int64)
+    np.save(os.path.join(out_dir, "status.npy"), status.astype(np.float64))
+    np.save(os.path.join(out_dir, "frames.npy"), frames.astype(np.float64))
+    ftype = np.float64 if bps == 4 else np.float32
+    per_packet = FL * ch * np.dtype(ftype).itemsize
+    n = min(P, max(1, (DUMP_BYTES - 16 * P) // per_packet))
+    idx = np.arange(P) if n == P else np.sort(np.random.default_rng(DUMP_SEED).choice(P, n, replace=False))
+    raw = d_out.index_select(0, torch.from_numpy(idx).to(d_out.device))[:, :FL * ch * bps].cpu().numpy()
+    raw = raw.reshape(n, FL * ch, bps)
+    if bps == 2:
+        s = raw.reshape(n, -1).view("<i2").astype(np.int32)
+    elif bps == 3:  # 20- and 24-bit samples: three bytes LE, sign-extended
+        s = raw[..., 0].astype(np.int32) | (raw[..., 1].astype(np.int32) << 8) | (raw[..., 2].astype(np.int8).astype(np.int32) << 16)
+    else:
+        s = raw.reshape(n, -1).view("<i4")
+    pcm = s.astype(ftype).reshape(n, FL, ch)
+    pcm[np.arange(FL)[None, :] >= frames[idx][:, None]] = 0  # a partial frame leaves the rest of its slot unspecified
+    np.save(os.path.join(out_dir, "pcm.npy"), pcm)
 
 
 def main():
@@ -145,7 +185,8 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    dec.timing_reset()
+    if args.full:
+        dec.timing_reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -155,6 +196,32 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, d_fr, d_st, P, FL, ch, bps)
+
+    if rank == 0:
+        value = samples * world * args.steps / elapsed / 1e6
+        line = {
+            "metric": "Msamples/s decoded (16-bit stereo, 4096-frame packets)" if (depth, ch, FL) == (16, 2, 4096)
+            else "Msamples/s decoded (%d-bit %d-ch, %d-frame packets)" % (depth, ch, FL),
+            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+            "config": {"workload": "%d packets/GPU x %d-bit %d-ch %d-frame ALAC, music-like synthetic, "
+                                   "device-resident in/out" % (P, depth, ch, FL),
+                       "packets_per_gpu": P, "samples_per_step_per_gpu": samples,
+                       "compression_ratio": round(b.compressed_bytes / max(1, frames_total * ch * bps), 4),
+                       "sharding": "independent packet ranges, no collective"},
+            "gen_seconds": round(gen_s, 2),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        dec.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
     kms = dec.kernel_times_ms(min(args.steps, 64))
     kernel_ms = float(np.mean(kms)) if len(kms) else float("nan")
     dispatch = dec.last_dispatch()
@@ -272,19 +339,8 @@ def main():
                       "source": traffic_src + " (SQ_INSTS_VALU, summed over the kernels of one decode)"}
 
     if rank == 0:
-        value = samples * world * args.steps / elapsed / 1e6
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms == kernel_ms else None
-        line = {
-            "metric": "Msamples/s decoded (16-bit stereo, 4096-frame packets)" if (depth, ch, FL) == (16, 2, 4096)
-            else "Msamples/s decoded (%d-bit %d-ch, %d-frame packets)" % (depth, ch, FL),
-            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
-            "config": {"workload": "%d packets/GPU x %d-bit %d-ch %d-frame ALAC, music-like synthetic, "
-                                   "device-resident in/out" % (P, depth, ch, FL),
-                       "packets_per_gpu": P, "samples_per_step_per_gpu": samples,
-                       "compression_ratio": round(b.compressed_bytes / max(1, frames_total * ch * bps), 4),
-                       "sharding": "independent packet ranges, no collective"},
+        line.update({
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5) if achieved else None,
                          "traffic": traffic, "traffic_source": (traffic_src + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload and this source)") if traffic else None,
@@ -293,8 +349,8 @@ def main():
                          "valu_issue": valu_issue,
                          "kernel_ms": round(kernel_ms, 4), "kernel_ms_is": "HIP events on the handle's stream around all kernels of one decode (sort pre-pass included)",
                          "algorithmic_bytes_per_launch": alg_bytes},
-            "cpu_baseline": cpu, "bit_exact": bit_exact, "gen_seconds": round(gen_s, 2), "host_entry": host_entry,
-        }
+            "cpu_baseline": cpu, "bit_exact": bit_exact, "host_entry": host_entry,
+        })
         if cpu:
             line["gpu_over_cpu"] = round(value / cpu["value"], 2)
         print(json.dumps(line), flush=True)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): profiles/collect_round.sh <outdir> [bench.py workload flags, e.g. --depth 24]
 # The evidence of one round for the headline workload (bench.py's default command) or for another configuration:
-#   kernel_stats.csv       rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-entry`
+#   kernel_stats.csv       rocprofv3 --kernel-trace --stats of `python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-entry`
 #   bench_under_rocprof.json   the bench line of that same run
 #   pmc_summary.txt        instruction / cycle counters (one --pmc pass per line of groups_duo.txt, never mixed with traces)
 #   traffic.json           HBM bytes per launch: FETCH_SIZE x 2 (gfx950 counts 128-B requests as 64) + WRITE_SIZE, stamped with
@@ -10,7 +10,7 @@ set -u
 OUT=$1; shift; mkdir -p "$OUT"
 export TMPDIR=/tmp
 WORKLOAD="$*"
-CMD="bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-entry $WORKLOAD"
+CMD="bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-entry $WORKLOAD"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $CMD > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.log"
 cp $(find "$OUT/trace" -name "*kernel_stats.csv" | head -1) "$OUT/kernel_stats.csv"
 head -40 $(find "$OUT/trace" -name "*kernel_trace.csv" | head -1) > "$OUT/kernel_trace_head.csv"

@@ -23,7 +23,9 @@ def test_header_declares_the_boundary():
 
 def test_library_exports_every_declared_symbol(pkg):
     pkg.build()
-    L = ctypes.CDLL(pkg.lib_path())
+    # through pkg.lib(): it loads torch's HIP runtime before the library, so that later GPU tests in this process still
+    # see the device (a bare CDLL here would bring in a second runtime and torch.cuda.is_available() would turn False)
+    L = pkg.lib()
     for name in _declared():
         assert hasattr(L, name), name
     L.alacgpu_version.restype = ctypes.c_char_p

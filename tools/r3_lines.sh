@@ -2,7 +2,7 @@
 # Bench lines of round 3 beyond the headline (device-resident, 1 GPU): the BASELINE configurations, SURVEY §8(f4)'s
 # formats, the batch-size sweep around the occupancy edge and the 9-key mix. usage: tools/r3_lines.sh <outdir>
 OUT=$1; mkdir -p "$OUT"
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-entry"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-entry"
 $B --packets 4096                                   > $OUT/config_b_4096pkts.json 2>/dev/null
 $B --depth 24                                        > $OUT/config_c_24bit_stereo.json 2>/dev/null
 $B --depth 24 --channels 8 --packets 16384           > $OUT/config_d_8ch_16384.json 2>/dev/null
