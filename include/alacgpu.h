@@ -241,6 +241,59 @@ void* alacgpu_stream(alacgpu_decoder* dec);
 
 int alacgpu_synchronize(alacgpu_decoder* dec);
 
+/*
+ * Batch ENCODER (0.6.0; the reference is decode-only). Input: one contiguous interleaved little-endian PCM stream in the
+ * decoder's output format (2 / 3 / 3 / 4 bytes per sample at 16 / 20 / 24 / 32 bits; a 20-bit sample is left-aligned in
+ * its 3 bytes and its low 4 bits are ignored). total_frames frames become ceil(total_frames / frame_length) packets; only
+ * the last one may be short, and only it carries the partial flag and its frame count. Every packet is encoded on its own
+ * (nothing carries over between packets): elements in the decoder's channel layout, an END tag, padded to a byte; per
+ * element mode 0, denShift 9, pbFactor 4, order 8 with Apple's initial coefficients warmed by one pass over the element's
+ * own samples, mixBits 2 / mixRes 2 for a CPE, bytesShifted 0 / 0 / 1 / 2 at 16 / 20 / 24 / 32 bits, the config's pb / mb
+ * / kb; an element whose compressed form is not smaller than raw goes out escaped (raw samples), and so does every element
+ * when frame_length <= 8 or kb = 0 (configs under which the decoder cannot read an order-8 element). The packets decode to the
+ * input PCM through alacgpu_decode_batch* and the reference. One handle is single-caller, like a decoder.
+ */
+typedef struct alacgpu_encoder alacgpu_encoder;
+
+/* Rejects what alacgpu_create rejects (ALACGPU_E_CONFIG, before any HIP call). One stream per handle. */
+int alacgpu_encoder_create(const alacgpu_config* cfg, int device, alacgpu_encoder** out);
+void alacgpu_encoder_destroy(alacgpu_encoder* enc);
+
+/* A blob capacity that always suffices for total_frames frames: every element at its escape size plus the largest
+ * header, per packet. 0 for a NULL handle. */
+uint64_t alacgpu_encode_max_bytes(const alacgpu_encoder* enc, uint64_t total_frames);
+
+/* Device-resident encode. d_pcm: total_frames interleaved frames; d_blob: blob_cap bytes, receives the packets back to
+ * back (dense); d_offsets: n + 1 entries, packet i is d_blob[d_offsets[i] .. d_offsets[i + 1]), so the result feeds
+ * alacgpu_decode_batch_device(..., d_sizes = NULL, ...) unchanged. A blob_cap below alacgpu_encode_max_bytes() is
+ * ALACGPU_E_ARG and nothing is written. Asynchronous on the handle's stream (alacgpu_encoder_stream()) unless sync != 0,
+ * with the ordering contract of alacgpu_decode_batch_device: inputs complete or ordered on that stream before the call,
+ * outputs complete after alacgpu_encoder_synchronize(). One encode takes at most 2^31 - 1 packets (more is ALACGPU_E_ARG;
+ * cut the stream). Device scratch of the handle, grown on demand: about 800 bytes per packet plus 2 x frame_length x depth
+ * / 8 bytes per channel of a packet (its chains' bitstreams); a failed allocation is ALACGPU_E_HIP. Every channel of a
+ * packet is one serial chain on one lane, so a batch of few long packets runs on few lanes: its time grows with
+ * frame_length, not with the device's width. */
+int alacgpu_encode_device(alacgpu_encoder* enc, const uint8_t* d_pcm, uint64_t total_frames, uint8_t* d_blob,
+                          uint64_t blob_cap, uint64_t* d_offsets, int sync);
+
+/* Host buffers, blocking. pcm holds total_frames frames; blob_cap as above; offsets gets n + 1 entries; *blob_bytes_out
+ * the bytes written (= offsets[n]). Buffers from alacgpu_host_alloc / hipHostMalloc / hipHostRegister are transferred in
+ * place, pageable ones are staged through pinned buffers of the handle. */
+int alacgpu_encode(alacgpu_encoder* enc, const uint8_t* pcm, uint64_t total_frames, uint8_t* blob, uint64_t blob_cap,
+                   uint64_t* offsets, uint64_t* blob_bytes_out);
+
+/* The 24-byte big-endian ALACSpecificConfig (config.go:64-79, what ParseMagicCookie reads) of what this handle has
+ * encoded: the config's fields, max_frame_bytes = its largest packet so far, avg_bit_rate = bits per second over all its
+ * packets so far (from the bytes, the frames and sample_rate). Synchronizes the handle's stream. */
+int alacgpu_encoder_cookie(alacgpu_encoder* enc, uint8_t out[24]);
+
+/* Duration of the last encode in milliseconds: HIP events around all its kernels (valid after a sync). */
+int alacgpu_encoder_last_kernel_ms(alacgpu_encoder* enc, float* ms);
+
+/* The handle's hipStream_t as an opaque pointer, and a wait for everything on it. */
+void* alacgpu_encoder_stream(alacgpu_encoder* enc);
+int alacgpu_encoder_synchronize(alacgpu_encoder* enc);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

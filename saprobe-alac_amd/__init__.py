@@ -30,7 +30,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _LIB = None
 
 __all__ = [
-    "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "ParseMagicCookie",
+    "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "PacketEncoder", "NewPacketEncoder", "ParseMagicCookie",
     "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim",
 ]
 
@@ -230,6 +230,17 @@ _EXPORTS = {
                                               ctypes.POINTER(ctypes.c_size_t)]),
     "alacgpu_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "alacgpu_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_encoder_create": (ctypes.c_int, [ctypes.POINTER(PacketConfig), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_encoder_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_encode_max_bytes": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "alacgpu_encode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "alacgpu_encoder_cookie": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "alacgpu_encoder_last_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_encoder_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_encoder_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -447,6 +458,110 @@ class PacketDecoder:
 def NewPacketDecoder(config, device=0):
     """NewPacketDecoder (decoder.go:90): raises ErrConfig for bit depths outside {16,20,24,32}."""
     return PacketDecoder(config, device)
+
+
+# ---- PacketEncoder (new: the reference is decode-only) ------------------------------------------------------------
+class PacketEncoder:
+    """Encodes interleaved LE PCM into ALAC packets on one MI355X (include/alacgpu.h: alacgpu_encoder_*).
+
+    The input is the decoder's output format: [frames][channels] int16 (16-bit) / int32 (32-bit) arrays, or raw bytes (2 /
+    3 / 3 / 4 bytes per sample at 16 / 20 / 24 / 32 bits; a 20-bit sample is left-aligned in 3 bytes and its low 4 bits
+    are ignored). Packets of FrameLength frames, the last one possibly short; see alacgpu.h for the per-element policy.
+    Single-caller, bound to one device and one stream."""
+
+    def __init__(self, config, device=0):
+        self._h = ctypes.c_void_p()
+        self._lib = lib()
+        self.config = config
+        _check(self._lib.alacgpu_encoder_create(ctypes.byref(config), device, ctypes.byref(self._h)))
+        self.device = device
+        self.bytes_per_frame = config.NumChannels * bytes_per_sample(config.BitDepth)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.alacgpu_encoder_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _pcm_bytes(self, pcm):
+        if isinstance(pcm, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(bytes(pcm), dtype=np.uint8)
+        else:
+            arr = np.asarray(pcm)
+            if arr.dtype == np.uint8 and arr.ndim == 1:
+                buf = np.ascontiguousarray(arr)
+            else:
+                depth, ch = self.config.BitDepth, self.config.NumChannels
+                if arr.ndim != 2 or arr.shape[1] != ch:
+                    raise ValueError("pcm must be [frames][%d]" % ch)
+                if depth == 16 and arr.dtype == np.int16:
+                    buf = np.ascontiguousarray(arr, dtype="<i2").view(np.uint8).reshape(-1)
+                elif depth == 32 and arr.dtype == np.int32:
+                    buf = np.ascontiguousarray(arr, dtype="<i4").view(np.uint8).reshape(-1)
+                elif depth in (20, 24) and arr.dtype == np.int32:
+                    # an int32 array holds the samples in the PCM domain of the depth; 20-bit ones go left-aligned
+                    v = arr.astype(np.int64).reshape(-1) << (4 if depth == 20 else 0)
+                    b = (v & 0xFFFFFF).astype("<u4").view(np.uint8).reshape(-1, 4)[:, :3]
+                    buf = np.ascontiguousarray(b).reshape(-1)
+                else:
+                    raise ValueError("%s samples do not fit a %d-bit stream" % (arr.dtype, depth))
+        if buf.size % self.bytes_per_frame:
+            raise ValueError("pcm is not a whole number of frames")
+        return buf
+
+    def max_bytes(self, frames):
+        """alacgpu_encode_max_bytes: a blob capacity that always suffices for `frames` frames."""
+        return int(self._lib.alacgpu_encode_max_bytes(self._h, frames))
+
+    def encode(self, pcm):
+        """alacgpu_encode: PCM -> (blob np.uint8, offsets np.uint64[n + 1]); packet i is blob[offsets[i]:offsets[i + 1]]."""
+        buf = self._pcm_bytes(pcm)
+        frames = buf.size // self.bytes_per_frame
+        fl = self.config.FrameLength
+        n = (frames + fl - 1) // fl
+        cap = self.max_bytes(frames)
+        blob = np.empty(max(cap, 1), dtype=np.uint8)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        got = ctypes.c_uint64()
+        _check(self._lib.alacgpu_encode(self._h, buf.ctypes.data if buf.size else None, frames, blob.ctypes.data, cap,
+                                        offsets.ctypes.data, ctypes.byref(got)))
+        return blob[:got.value].copy(), offsets
+
+    def encode_device(self, d_pcm, total_frames, d_blob, blob_cap, d_offsets, sync=True):
+        """alacgpu_encode_device: raw device pointers (ints), e.g. torch tensors' data_ptr(); d_offsets gets n + 1 uint64.
+        The handle's stream does not order against torch's: synchronize the inputs first."""
+        _check(self._lib.alacgpu_encode_device(self._h, d_pcm, total_frames, d_blob, blob_cap, d_offsets, 1 if sync else 0))
+
+    def cookie(self):
+        """alacgpu_encoder_cookie: 24-byte ALACSpecificConfig (ParseMagicCookie reads it) with the largest packet and the
+        average bit rate of what this encoder has written."""
+        out = (ctypes.c_uint8 * 24)()
+        _check(self._lib.alacgpu_encoder_cookie(self._h, out))
+        return bytes(out)
+
+    def last_kernel_ms(self):
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_encoder_last_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def synchronize(self):
+        _check(self._lib.alacgpu_encoder_synchronize(self._h))
+
+
+def NewPacketEncoder(config, device=0):
+    """A PacketEncoder (context manager); raises ErrConfig for the configs NewPacketDecoder rejects."""
+    return PacketEncoder(config, device)
 
 
 def NewDecoder(source, device=0, window=1024):

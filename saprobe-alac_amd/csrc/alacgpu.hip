@@ -1225,6 +1225,11 @@ int alacgpu_debug_prof(unsigned long long* out16) {
 }
 #endif
 
-const char* alacgpu_version(void) { return "alacgpu 0.5.0 gfx950"; }
+const char* alacgpu_version(void) { return "alacgpu 0.6.0 gfx950"; }
 
 } /* extern "C" */
+
+/* the encoder's entries (k_enc.hip) report through the same thread-local text as alacgpu_last_error */
+namespace alack {
+void set_last_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
+} /* namespace alack */
