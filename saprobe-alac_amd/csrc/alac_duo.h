@@ -30,21 +30,10 @@
 
 #include "alac_regular.h"
 
-#ifndef ALAC_DUO_UN8_MAX
-#define ALAC_DUO_UN8_MAX 12 /* longest predictor whose steady-state groups are 8 steps (else 4) */
-#endif
-#ifndef ALAC_DUO_STAMP
-/* profiling build only (-DALAC_DUO_PROF in alacgpu.hip): time stamps around the parts of an iteration */
-#define ALAC_DUO_STAMP(k)
-#endif
-
 namespace alac {
 
-#ifndef ALAC_DUO_CHUNK
-#define ALAC_DUO_CHUNK 16
-#endif
-constexpr uint32_t DUO_CHUNK = ALAC_DUO_CHUNK;
- /* steps per queue buffer (a multiple of 8) */
+constexpr uint32_t DUO_CHUNK = 16;     /* steps per queue buffer (a multiple of 8) */
+constexpr int DUO_UN8_MAX = 12;        /* longest predictor whose steady-state groups are 8 steps (else 4) */
 enum { ROLE_A = 0, ROLE_B = 1, ROLE_BOTH = 2, ROLE_C = 3 };
 
 /*
@@ -82,15 +71,6 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     constexpr bool DO_C = (ROLE == ROLE_C || ROLE == ROLE_BOTH) && EC;
     constexpr bool EMIT_A = (EA || EC) && LAST && !RAW; /* the samples leave wave B through the queue */
     constexpr bool DO_EMIT = EMIT_A ? (EC ? DO_C : DO_A) : DO_B;
-    /* FWD: with a writer wave, what the PCM of a pair needs from memory — the U samples, the shift bytes of the 3-byte
-     * block writer — is still fetched by the predictor wave and handed on through the queue (rows 2 CH .. and 3 CH ..).
-     * A wave's memory counter retires in issue order, loads and stores alike: a writer that fetched them itself would
-     * wait, at every load, for the PCM stores it issued before (24-bit pairs: 820 ticks per step in the writer against
-     * 430 in the other two). The predictor wave stores nothing in this phase. */
-#ifndef ALAC_FWD
-#define ALAC_FWD 0 /* measured (round 3): 16-bit pairs 2.36 -> 2.45 ms, 24-bit pairs 4.04 -> 3.78 (two waves: 3.52): not kept */
-#endif
-    constexpr bool FWD = ALAC_FWD != 0 && EMIT_A && EC && OUT == OUT_STEREO;
     constexpr uint32_t CH = EMIT_A ? DUO_CHUNK / 2u : DUO_CHUNK;
     const uint32_t na = GEN ? na_rt : (uint32_t)NA;
     uint32_t kb = cfg.kb;
@@ -249,10 +229,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
         for (int t = NR; t >= 1; --t) hb[t] = hb[t - 1];
         hb[0] = (uint32_t)o ^ BIAS;
         if (!LAST) *wv.u_row(i) = o; /* dead lanes write their own unused cell */
-        else if (EMIT_A) {
-            wv.rq_write(buf, CH + j, o);
-            if (FWD) wv.rq_write(buf, 2u * CH + j, u); /* the U sample rides along (see FWD) */
-        }
+        else if (EMIT_A) wv.rq_write(buf, CH + j, o);
         else emit(i, o, u, sw, jj, fp);
     };
     constexpr bool PK3 = CPE && LAST && !F16 && !RAW && !EMIT_A;      /* ... in the predictor wave */
@@ -326,22 +303,14 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             }
             if (i < n_it) { /* scalar: rows past n_it do not exist in the tile */
                 sq_v[j] = wv.rq_read(buf, CH + j);
-                if (FWD) u_v[j] = wv.rq_read(buf, 2u * CH + j);
                 if (!EC) {
                     if (CPE) u_v[j] = *wv.u_row(i);
                     if (merge_any) sw_v[j] = bits.window_raw(shift_pos + i * sstep_a);
                 }
             }
         }
-        if (FWD && PK3C && whole_pk3(c) && sb8) {
-#pragma unroll
-            for (uint32_t q = 0; q < CH / 4u; ++q)
-#pragma unroll
-                for (uint32_t k = 0; k < 3u; ++k) g_v[q][k] = (uint32_t)wv.rq_read(buf, 3u * CH + 3u * q + k);
-        }
     };
-    /* the writer wave: what a chunk needs from memory (U samples, shift values) is asked for a whole iteration ahead
-     * (unless the predictor wave hands it on: FWD) */
+    /* the writer wave: what a chunk needs from memory (U samples, shift values) is asked for a whole iteration ahead */
     int32_t u_n[CH];
     uint64_t sw_n[CH];
     uint32_t g_n[CH / 4u][3] = {};
@@ -353,11 +322,11 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             u_n[j] = 0;
             sw_n[j] = 0;
             if (i < n_it) {
-                if (CPE && !FWD) u_n[j] = *wv.u_row(i);
+                if (CPE) u_n[j] = *wv.u_row(i);
                 if (merge_any && !blocks) sw_n[j] = bits.window_raw(shift_pos + i * sstep_a);
             }
         }
-        if (!FWD && PK3C && blocks && sb8) {
+        if (PK3C && blocks && sb8) {
 #pragma unroll
             for (uint32_t q = 0; q < CH / 4u; ++q) bits.load12(sh_byte + 2u * (c * CH + 4u * q), g_n[q][0], g_n[q][1], g_n[q][2]);
         }
@@ -384,29 +353,21 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
         wv.st_step(); /* collective of wave A */
     };
     /* steady-state groups of role B: UN unrolled steps. Long predictors and the wide writers (64-bit shift windows)
-     * take half groups, or registers run out. For the wide writers, what a group needs from HBM / L2 (the U samples
-     * of its frames, the 8-byte windows on their shift values) is requested one group AHEAD, into upre / spre, so
-     * that the load latency hides behind a whole group of taps (24-bit stereo: 4.65 -> 4.11 ms). The 16-bit writer
-     * asks for its U samples at the top of its own group: one dword per frame, first needed a whole step later, and
-     * the extra registers and moves of looking ahead cost it more than the wait (2.45 -> 2.62 ms). */
-#ifndef ALAC_DUO_UN8_WIDE_MAX
-#define ALAC_DUO_UN8_WIDE_MAX 0 /* same for the writers of the wider samples (generic: their groups also hold 64-bit shift windows) */
-#endif
+     * take half groups, or registers run out. For the writers, what a group needs from HBM / L2 (the U samples of its
+     * frames, the 8-byte windows on their shift values) is requested one group AHEAD, into upre / spre, so that the
+     * load latency hides behind a whole group of taps (24-bit stereo: 4.65 -> 4.11 ms). The 16-bit writer, one dword
+     * per frame, first did without (looking ahead cost it 2.45 -> 2.62 ms at the time); it looks ahead too since the
+     * steps were shortened. */
     /* UN8W: the caller's streams have 3-byte samples, whose writer (PK3 below) holds no 64-bit windows: groups of eight
      * for predictors of up to eight taps. What it asks for a group ahead (shift bytes, U samples: scattered 64-byte
      * reads from HBM) then has eight steps to arrive instead of four. */
-    constexpr uint32_t UN = (NARROW && (((F16 || !LAST || RAW || EMIT_A) && NR <= ALAC_DUO_UN8_MAX) ||
-                                        NR <= (UN8W ? 8 : ALAC_DUO_UN8_WIDE_MAX))) ? 8u : 4u;
-    constexpr bool HBM_IN = (LAST && !RAW && !EMIT_A) || FWD; /* this wave reads the U tile / shift bytes (to write, or to hand on) */
+    constexpr uint32_t UN = (NARROW && (((F16 || !LAST || RAW || EMIT_A) && NR <= DUO_UN8_MAX) || (UN8W && NR <= 8))) ? 8u : 4u;
+    constexpr bool HBM_IN = LAST && !RAW && !EMIT_A; /* this wave reads the U tile / shift bytes (to write) */
     /* role B fed from memory (split pipeline's predictor pass: W::kResMem): the residuals of a group are requested one
      * group ahead, like the U samples of the wide writers */
     constexpr bool RMEM = W::kResMem && ROLE == ROLE_B;
     int32_t dpre[UN];
     uint32_t dpre_row = 0xffffffffu;
-#ifndef ALAC_AHEAD_F16
-#define ALAC_AHEAD_F16 1
-#endif
-    constexpr bool AHEAD = HBM_IN && (!F16 || ALAC_AHEAD_F16 != 0);
     int32_t upre[UN];
     uint64_t spre[UN];
     uint32_t pre_row = 0xffffffffu; /* first frame of the group upre / spre hold */
@@ -427,7 +388,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             if (CPE) upre[j] = *wv.u_row(row0 + j);
             if (merge_any && !pk3) spre[j] = bits.window_raw(shift_pos + (row0 + j) * sstep_b);
         }
-        if ((PK3 || (FWD && PK3C)) && pk3 && sb8) {
+        if (PK3 && pk3 && sb8) {
 #pragma unroll
             for (uint32_t q = 0; q < NSUB; ++q) bits.load12(sh_byte + 2u * (row0 + 4u * q), gpre[q][0], gpre[q][1], gpre[q][2]);
         }
@@ -445,17 +406,13 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
              * the history shift becomes register renaming across the unrolled steps */
             auto groups = [&](auto wrap, auto fp) {
                 constexpr bool FP = decltype(fp)::value;
-#if ALAC_AHEAD_F16 == 2
-#pragma unroll
-#else
 #pragma nounroll
-#endif
                 for (uint32_t g = 0; g < CH; g += UN) {
                     const uint32_t row0 = c * CH + g;
                     if (FP) fp_base = wv.st_group_base(UN);
                     int32_t dv[UN], uv[UN];
                     uint64_t sv[UN];
-                    if (AHEAD && pre_row != row0) prefetch_group(row0); /* first steady group: nothing was ahead */
+                    if (HBM_IN && pre_row != row0) prefetch_group(row0); /* first steady group: nothing was ahead */
                     if (RMEM && dpre_row != row0) {
 #pragma unroll
                         for (uint32_t j = 0; j < UN; ++j) dpre[j] = wv.rq_read(buf, g + j);
@@ -463,9 +420,8 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
 #pragma unroll
                     for (uint32_t j = 0; j < UN; ++j) {
                         dv[j] = RMEM ? dpre[j] : wv.rq_read(buf, g + j);
-                        uv[j] = AHEAD ? upre[j] : 0;
-                        sv[j] = AHEAD ? spre[j] : 0ull;
-                        if (HBM_IN && !AHEAD && CPE) uv[j] = *wv.u_row(row0 + j);
+                        uv[j] = HBM_IN ? upre[j] : 0;
+                        sv[j] = HBM_IN ? spre[j] : 0ull;
                     }
                     uint32_t gq[NSUB][3];
 #pragma unroll
@@ -474,17 +430,11 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
                         gq[q][1] = gpre[q][1];
                         gq[q][2] = gpre[q][2];
                     }
-                    if (AHEAD && row0 + 2u * UN <= steady_end) prefetch_group(row0 + UN);
+                    if (HBM_IN && row0 + 2u * UN <= steady_end) prefetch_group(row0 + UN);
                     if (RMEM && row0 + 2u * UN <= steady_end) { /* rq_read indexes from the chunk's first step */
                         dpre_row = row0 + UN;
 #pragma unroll
                         for (uint32_t j = 0; j < UN; ++j) dpre[j] = wv.rq_read(buf, g + UN + j);
-                    }
-                    if (FWD && PK3C && pk3 && sb8) { /* the shift bytes of the group's blocks, for the writer wave */
-#pragma unroll
-                        for (uint32_t q = 0; q < NSUB; ++q)
-#pragma unroll
-                            for (uint32_t k = 0; k < 3u; ++k) wv.rq_write(buf, 3u * CH + 3u * (g / 4u + q) + k, (int32_t)gq[q][k]);
                     }
                     if (PK3 && pk3) {
 #pragma unroll
@@ -545,16 +495,6 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             run_groups(wrap_yes{});
             return;
         }
-        if (FWD && PK3C && whole_pk3(c) && sb8) { /* a whole chunk outside the steady state: its shift bytes, on the spot */
-#pragma unroll
-            for (uint32_t q = 0; q < CH / 4u; ++q) {
-                uint32_t g0, g1, g2;
-                bits.load12(sh_byte + 2u * (c * CH + 4u * q), g0, g1, g2);
-                wv.rq_write(buf, 3u * CH + 3u * q, (int32_t)g0);
-                wv.rq_write(buf, 3u * CH + 3u * q + 1u, (int32_t)g1);
-                wv.rq_write(buf, 3u * CH + 3u * q + 2u, (int32_t)g2);
-            }
-        }
 #pragma nounroll
         for (uint32_t j = 0; j < CH; ++j) {
             const uint32_t i = c * CH + j;
@@ -565,7 +505,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             if (i == 0 || (GEN && na == 0)) o = del;
             else if (i <= na || (GEN && na == 31)) o = sext_cs(del + (int32_t)(hb[0] ^ BIAS), chan_shift);
             else o = predict(del, wrap_yes{});
-            put(buf, j, i, o, (CPE && (!EMIT_A || FWD)) ? *wv.u_row(i) : 0,
+            put(buf, j, i, o, (CPE && !EMIT_A) ? *wv.u_row(i) : 0,
                 (!EMIT_A && merge_any) ? bits.window_raw(shift_pos + i * sstep) : 0ull, 0u, fp_no{});
             if (LAST && !EMIT_A) wv.st_step();
             if (FP_OK && i + 1u == ns) (void)wv.st_finish(); /* see run_groups */
@@ -576,20 +516,14 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
      * c-2 from the samples B queued in iteration c-1); the barrier publishes the buffers written in the iteration */
     const uint32_t nch = (n_it + CH - 1u) / CH;
     const uint32_t iters = nch + (EMIT_A ? 2u : 1u);
-#ifdef ALAC_DUO_PROF
-    constexpr uint32_t kProfPhase = LAST ? 4u : 0u; /* ALAC_DUO_STAMP: the U phase and the last phase apart */
-#endif
     for (uint32_t c = 0; c < iters; ++c) {
-        ALAC_DUO_STAMP(0);
         if (DO_A) {
             if (EMIT_A && !EC && c >= 2u) fetch_chunk(c - 2u);
             if (c < nch) golomb_chunk(c);
         }
-        ALAC_DUO_STAMP(1);
         if (DO_B) {
             if (c >= 1u && c <= nch) predict_chunk(c - 1u);
         }
-        ALAC_DUO_STAMP(2);
         if (DO_A && EMIT_A && !EC) {
             if (c >= 2u) emit_chunk(c - 2u);
         }
@@ -597,27 +531,23 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             if (c >= 2u) {
 #pragma unroll
                 for (uint32_t j = 0; j < CH; ++j) {
-                    if (!FWD) u_v[j] = u_n[j];
+                    u_v[j] = u_n[j];
                     sw_v[j] = sw_n[j];
                 }
-                if (!FWD) {
 #pragma unroll
-                    for (uint32_t q = 0; q < CH / 4u; ++q) {
-                        g_v[q][0] = g_n[q][0];
-                        g_v[q][1] = g_n[q][1];
-                        g_v[q][2] = g_n[q][2];
-                    }
+                for (uint32_t q = 0; q < CH / 4u; ++q) {
+                    g_v[q][0] = g_n[q][0];
+                    g_v[q][1] = g_n[q][1];
+                    g_v[q][2] = g_n[q][2];
                 }
             }
-            if ((merge_any || !FWD) && c >= 1u && c <= nch) fetch_mem_ahead(c - 1u);
+            if (c >= 1u && c <= nch) fetch_mem_ahead(c - 1u);
             if (c >= 2u) {
                 fetch_chunk(c - 2u);
                 emit_chunk(c - 2u);
             }
         }
-        ALAC_DUO_STAMP(3);
         wv.duo_sync();
-        ALAC_DUO_STAMP(4);
     }
     if (DO_EMIT && LAST) wv.st_tail(pk_acc, pk_n); /* bytes of the last, incomplete dword */
     if (!LAST) wv.duo_sync_mem();                  /* the U tile is complete before anyone loads from it */

@@ -107,63 +107,6 @@ __device__ __forceinline__ int32_t alac_med3_0(int32_t x, int32_t m) {
     return r;
 }
 #define ALAC_MED3_0(x, m) alac_med3_0((int32_t)(x), (int32_t)(m))
-/* The two blocks of the Golomb step (alac_regular.h: gol_step, whose C++ form these follow instruction for
- * instruction), each ONE asm statement: the order inside is the order of issue, and no instruction reads the result of
- * the one before it (a lone wave: 8.3 cycles instead of 4.8). v_cmp .. v_addc: two instructions apart (the compiler keeps
- * the same distance). 128 is no inline constant and VOP3 takes no literal on gfx9: it comes in an SGPR. */
-#ifndef ALAC_GOL_ASM
-#define ALAC_GOL_ASM 0
-#endif
-#define ALAC_GOL_BLOCK_A(wa, wb, sh, ck, t9, norun, pos, mean, zq, pb, n, esc, mt, pos2, aoff, zq2, mean2, nhi)            \
-    do {                                                                                                                   \
-        uint32_t w_, k_, t_, pre_, v_, pk_, vm1_, cons_;                                                                   \
-        asm("v_alignbit_b32 %[w], %[Wa], %[Wb], %[Sh]\n\t"                                                                 \
-            "v_sub_u32 %[k], 31, %[Ck]\n\t"                                                                                \
-            "v_not_b32 %[t], %[w]\n\t"                                                                                     \
-            "v_sub_u32 %[Mt], %[Mean], %[T9]\n\t"                                                                          \
-            "v_ffbh_u32 %[pre], %[t]\n\t"                                                                                  \
-            "v_xad_u32 %[Zq2], %[Norun], -1, %[Zq]\n\t"                                                                    \
-            "v_sub_u32 %[t], %[Ck], %[pre]\n\t"                                                                            \
-            "v_sub_u32_e64 %[Esc], %[pre], 8 clamp\n\t"                                                                    \
-            "v_bfe_u32 %[v], %[w], %[t], %[k]\n\t"                                                                         \
-            "v_lshlrev_b32 %[pk], %[k], %[pre]\n\t"                                                                        \
-            "v_cmp_lt_u32 vcc, 1, %[v]\n\t"                                                                                \
-            "v_sub_u32_e64 %[vm1], %[v], 1 clamp\n\t"                                                                      \
-            "v_sub_u32 %[pk], %[pk], %[pre]\n\t"                                                                           \
-            "v_addc_co_u32 %[cons], vcc, %[pre], %[k], vcc\n\t"                                                            \
-            "v_add_u32 %[N], %[pk], %[vm1]\n\t"                                                                            \
-            "v_and_b32 %[cons], %[cons], %[Norun]\n\t"                                                                     \
-            "v_and_b32 %[N], %[N], %[Norun]\n\t"                                                                           \
-            "v_add_u32 %[Pos2], %[Pos], %[cons]\n\t"                                                                       \
-            "v_mad_u32_u24 %[Mean2], %[Pb], %[N], %[Mt]\n\t"                                                               \
-            "v_lshrrev_b32 %[Aoff], 3, %[Pos2]\n\t"                                                                        \
-            "v_lshrrev_b32 %[Nhi], 16, %[N]\n\t"                                                                           \
-            "v_and_b32 %[Aoff], 0x7c, %[Aoff]"                                                                             \
-            : [w] "=&v"(w_), [k] "=&v"(k_), [t] "=&v"(t_), [pre] "=&v"(pre_), [v] "=&v"(v_), [pk] "=&v"(pk_),              \
-              [vm1] "=&v"(vm1_), [cons] "=&v"(cons_), [N] "=&v"(n), [Esc] "=&v"(esc), [Mt] "=&v"(mt), [Pos2] "=&v"(pos2),  \
-              [Aoff] "=&v"(aoff), [Zq2] "=&v"(zq2), [Mean2] "=&v"(mean2), [Nhi] "=&v"(nhi)                                 \
-            : [Wa] "v"(wa), [Wb] "v"(wb), [Sh] "v"(sh), [Ck] "v"(ck), [T9] "v"(t9), [Norun] "v"(norun), [Pos] "v"(pos),    \
-              [Mean] "v"(mean), [Zq] "v"(zq), [Pb] "v"(pb)                                                                 \
-            : "vcc");                                                                                                      \
-    } while (0)
-#define ALAC_GOL_BLOCK_B(mean2, nhi, esc, pos2, zq2, norun, near, pbs, c31kb, rare, sh2, ck2, t92, norun2)                 \
-    do {                                                                                                                   \
-        uint32_t zs_, x_;                                                                                                  \
-        asm("v_sub_u32_e64 %[zs], %[C128], %[Mean2] clamp\n\t"                                                             \
-            "v_lshrrev_b32 %[x], 9, %[Mean2]\n\t"                                                                          \
-            "v_not_b32 %[Sh2], %[Pos2]\n\t"                                                                                \
-            "v_or3_b32 %[zs], %[Esc], %[Nhi], %[zs]\n\t"                                                                   \
-            "v_mul_hi_u32 %[T92], %[Mean2], %[Pbs]\n\t"                                                                    \
-            "v_add_u32 %[x], 3, %[x]\n\t"                                                                                  \
-            "v_ashrrev_i32 %[Norun2], 31, %[Zq2]\n\t"                                                                      \
-            "v_ffbh_u32 %[x], %[x]\n\t"                                                                                    \
-            "v_bitop3_b32 %[Rare], %[zs], %[Norun], %[Near] bitop3:0xc8\n\t"                                               \
-            "v_max_i32 %[Ck2], %[x], %[C31kb]"                                                                             \
-            : [zs] "=&v"(zs_), [x] "=&v"(x_), [Sh2] "=&v"(sh2), [T92] "=&v"(t92), [Norun2] "=&v"(norun2),                  \
-              [Rare] "=&v"(rare), [Ck2] "=&v"(ck2)                                                                         \
-            : [C128] "s"(128u), [Mean2] "v"(mean2), [Nhi] "v"(nhi), [Esc] "v"(esc), [Pos2] "v"(pos2), [Zq2] "v"(zq2),      \
-              [Norun] "v"(norun), [Near] "v"(near), [Pbs] "v"(pbs), [C31kb] "v"(c31kb));                                   \
-    } while (0)
 #define ALAC_PICK(dst, src) asm volatile("v_mov_b32 %0, %1" : "+v"(dst) : "v"(src))
 #define ALAC_OWN_REG(x) asm volatile("" : "+v"(x))
 typedef uint32_t alac_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -185,28 +128,17 @@ typedef int32_t alac_i32x4 __attribute__((ext_vector_type(4)));
         (d) = v_.w;                                                                    \
     } while (0)
 #define ALAC_STORE4(q, a, b, c, d) (*reinterpret_cast<alac_i32x4*>(q) = alac_i32x4{(a), (b), (c), (d)})
-#ifdef ALAC_DUO_PROF
-/* profiling build: cycles (s_memtime) between the stamps of alac_duo.h, summed per role over all waves into
- * Plan::prof (the plan is zeroed before every decode; alacgpu_debug_prof reads the last one back) */
-#define ALAC_DUO_STAMP(k)                                                   \
-    do {                                                                    \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
-        if ((k) > 0) wv.prof[kProfPhase + (k) - 1] += t_ - wv.prof_t;         \
-        wv.prof_t = t_;                                                     \
-    } while (0)
-#endif
 #include "alac_wave.h"
 #include "alac_regular.h"
 #include "alac_duo.h"
 #include "alac_split.h"
 
 /* s_setprio levels of the wave pair (see k_decode_body.inc: pair_item) */
-#ifndef ALAC_PRIO_B_LONG
 #define ALAC_PRIO_B_LONG 3  /* predictor waves, order > 8 */
 #define ALAC_PRIO_B_MID 2   /* order 6..8 */
 #define ALAC_PRIO_B_SHORT 1 /* order < 6 */
 #define ALAC_PRIO_A 2       /* entropy waves */
-#endif
+#define ALAC_PRIO_C 3       /* writer waves */
 
 namespace alack {
 
@@ -266,9 +198,6 @@ struct Plan {
     uint32_t gate[2][512];
     uint32_t balance[2][512]; /* per SIMD of the CU, a byte each: entropy waves - predictor waves placed there */
     uint32_t queue[2];
-#ifdef ALAC_DUO_PROF
-    unsigned long long prof[32]; /* [role A: U phase 0..3, last phase 4..7 | role C: 8..15 | role B: 16..19, 20..23] */
-#endif
 };
 
 /* LDS of the decode kernel (one wave per workgroup). Referenced by name, never through a generic pointer, so
@@ -276,16 +205,11 @@ struct Plan {
 static __shared__ uint32_t s_rows[kWave * kRowStride];                                  /* PCM stager rows */
 static __shared__ unsigned long long s_optr[kWave];                                     /* PCM slot of each lane's packet */
 static __shared__ __attribute__((aligned(16))) uint32_t s_ring[kRingSlots * kWave];     /* bitstream rings */
-/* residual queue of the wave pair (alac_duo.h), A -> B, double-buffered chunks */
+/* residual queue of the wave pair (alac_duo.h), A -> B, double-buffered chunks. Rows per buffer: a chunk of residuals
+ * A -> B; where another wave writes the PCM (alac_duo.h: EMIT_A) half a chunk of residuals and half a chunk of samples
+ * B -> writer */
 constexpr uint32_t kQ = alac::DUO_CHUNK;
-/* rows per buffer: a chunk of residuals A -> B; where another wave writes the PCM (alac_duo.h: EMIT_A) half a chunk of
- * residuals and half a chunk of samples B -> writer; with a writer wave and ALAC_FWD (ALAC_LDS_QROWS 32) also half a
- * chunk of U samples and six rows of shift bytes (alac_duo.h: FWD) */
-#ifndef ALAC_LDS_QROWS
-#define ALAC_LDS_QROWS ALAC_DUO_CHUNK
-#endif
-constexpr uint32_t kQRows = ALAC_LDS_QROWS;
-static __shared__ int32_t s_rq[2 * kQRows * kWave];
+static __shared__ int32_t s_rq[2 * kQ * kWave];
 
 /* U hand-off tile of one wave: frame_length rows of 64 cells and one spare row (the single-wave decoders read one
  * row ahead) */
@@ -300,9 +224,6 @@ struct GpuWave {
     uint8_t* my_out;
     uint32_t lane, wcnt, flushed;
     uint32_t ppw;              /* packets (= live lanes) per wave; also the row stride of the HBM tiles */
-#ifdef ALAC_DUO_PROF
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = 0;
-#endif
 
     ALAC_DEV bool any(bool p) const { return __ballot(p) != 0ull; }
     ALAC_DEV uint32_t max_u32(uint32_t v) const {
@@ -443,8 +364,8 @@ struct GpuWave {
     }
     ALAC_DEV void ring_write1(uint32_t slot, uint32_t v) { s_ring[slot * kWave + lane] = v; }
     /* residual queue: row j of buffer buf holds step j of the chunk for all 64 lanes (conflict-free) */
-    ALAC_DEV void rq_write(uint32_t buf, uint32_t j, int32_t v) { s_rq[(buf * kQRows + j) * kWave + lane] = v; }
-    ALAC_DEV int32_t rq_read(uint32_t buf, uint32_t j) const { return s_rq[(buf * kQRows + j) * kWave + lane]; }
+    ALAC_DEV void rq_write(uint32_t buf, uint32_t j, int32_t v) { s_rq[(buf * kQ + j) * kWave + lane] = v; }
+    ALAC_DEV int32_t rq_read(uint32_t buf, uint32_t j) const { return s_rq[(buf * kQ + j) * kWave + lane]; }
     /* two lanes per packet (alac_duo.h: duo_phase_lanes): DPP moves inside every pair of neighbouring lanes. Their source
      * must be the result of an instruction the compiler knows (not of inline asm): it inserts the wait states they need. */
     /* (mov_dpp, not update_dpp(0, ...): every lane of a quad_perm has a source, so there is no old value to keep; with one

@@ -495,33 +495,18 @@ ALAC_DEV void gol_head(RegLane<W>& s, uint32_t c31kb) {
  * TWO BLOCKS (round 4). A: window -> prefix -> value -> new position -> the ring slot of the next window; the read of
  * that slot (the caller's W::ring_read2_at, an instruction of the compiler's own, which therefore also places the wait
  * for it: right in front of the next step's block A); B: the mean, the rare-case flags and the next step's HEAD (RegLane)
- * — a dozen instructions between the read and the first look at its answer. On the GPU each block is ONE asm statement
- * (alac_gpu.h: ALAC_GOL_BLOCK_A / _B, the statements below instruction for instruction): the compiler keeps neither the
- * order of single statements nor asm statements apart from their readers without s_nop; a block it can
- * only take whole. The C++ form is what tests/host_sim runs and what ALAC_GOL_ASM 0 builds.
+ * — a dozen instructions between the read and the first look at its answer. Plain C++ whose statements the compiler
+ * keeps in order (the build runs with the pre-RA scheduler off, csrc/Makefile); the same code runs in tests/host_sim.
  * Returns n + zmode (0 inside a run).
  */
-#ifndef ALAC_GOL_ASM
-#define ALAC_GOL_ASM 0
-#endif
 template <bool ESC, class W, class B>
 ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, uint32_t kb, uint32_t wb, uint32_t c31kb,
                            uint32_t chan_bits, uint32_t i, uint32_t ns, uint32_t& ns_live) {
     const uint32_t o_pos = s.pos, o_mean = s.mean, o_zq = s.zq;
     RingRd<W>& rd = s.rd;
     const uint32_t o_wa = rd.wa, o_wb = rd.wb; /* stream dwords o_pos >> 5 and the next (o_pos: minus one) */
-#ifdef ALAC_PAD_A /* experiment: what an instruction more in the entropy step costs */
-    {
-        uint32_t pad_ = i;
-#pragma unroll
-        for (int t_ = 0; t_ < ALAC_PAD_A; ++t_) asm volatile("v_add_u32 %0, %0, %0" : "+v"(pad_));
-    }
-#endif
     uint32_t n, esc, mt, pos2, aoff, zq2, mean2, nhi;
     uint32_t rare, sh2, ck2, t92, norun2;
-#if ALAC_GOL_ASM
-    ALAC_GOL_BLOCK_A(o_wa, o_wb, s.h_sh, s.h_ck, s.h_t9, s.h_norun, o_pos, o_mean, o_zq, s.pb, n, esc, mt, pos2, aoff, zq2, mean2, nhi);
-#else
     {
         const uint32_t ck = s.h_ck, norun = s.h_norun;
         const uint32_t w = ALAC_ALIGNBIT(o_wa, o_wb, s.h_sh);   /* the 32 stream bits at the position */
@@ -547,12 +532,8 @@ ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, u
         nhi = n >> 16;
         aoff &= 4u * (RingRd<W>::RING - 1u); /* byte offset of ring slot (pos2 >> 5) & 31 in the lane's row */
     }
-#endif
     /* the next step's window: asked for now, looked at in the next step's block A */
     wv.ring_read2_at(aoff, rd.wa, rd.wb);
-#if ALAC_GOL_ASM
-    ALAC_GOL_BLOCK_B(mean2, nhi, esc, pos2, zq2, s.h_norun, s.near, s.pbs, c31kb, rare, sh2, ck2, t92, norun2);
-#else
     {
         /* rare cases, as nonzero-means-true flags: escape code (golomb.go:184), n > 0xffff (:216), near (RegLane), start
          * of a zero run (:223: mean * 4 < 512; mean2 < 2^26, the shift cannot wrap) */
@@ -567,7 +548,6 @@ ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, u
         rare = (fl | s.near) & s.h_norun;
         ck2 = (uint32_t)imax((int32_t)x, (int32_t)c31kb);
     }
-#endif
     s.pos = pos2;
     s.mean = mean2;
     s.zq = zq2;
@@ -638,6 +618,10 @@ ALAC_DEV int32_t gol_unfold(uint32_t nd) { return (int32_t)((nd >> 1) ^ (0u - (n
  * countdown must not come back up through the wrap: once a tap stopped adapting, none below it does (the reference
  * breaks out of its loop there). Until then nothing has wrapped and the normalised countdown equals the reference's
  * signed one. The literal form (predict_wide) is left for chanBits 32 and 33, whose differences wrap in int32. */
+/* ALAC_TAP_ORDER: the order of a tap's instructions, set per translation unit (1: k_dec16g.hip, k_split.hip; 2: the rest) */
+#ifndef ALAC_TAP_ORDER
+#define ALAC_TAP_ORDER 2
+#endif
 template <int NR, bool GEN, bool WRAP, bool CB_POS = false, bool MID = false>
 ALAC_DEV int32_t predict_narrow_core(int32_t (&coef)[NR], const uint32_t (&hb)[NR + 1], uint32_t na, int32_t del, uint32_t sgnm,
                                      uint32_t nsg, int32_t rem, uint32_t den_shift, int32_t den_half, uint32_t rnd_neg,
@@ -649,13 +633,6 @@ ALAC_DEV int32_t predict_narrow_core(int32_t (&coef)[NR], const uint32_t (&hb)[N
         for (int j = 1; j < NR; ++j)
             if (na == (uint32_t)j) ALAC_PICK(topb, hb[j]); /* scalar branch: na is wave-uniform */
     }
-#ifdef ALAC_PAD_B /* experiment: what an instruction more in the predictor step costs */
-    {
-        uint32_t pad_ = na;
-#pragma unroll
-        for (int t_ = 0; t_ < ALAC_PAD_B; ++t_) asm volatile("v_add_u32 %0, %0, %0" : "+v"(pad_));
-    }
-#endif
     /* no compares on the hot path (a v_cmp / v_cndmask pair costs a lone wave ~17 cycles, plain ALU ops ~5):
      * everything that depends on the sign of the residual is derived from its sign mask
      * (sgnm: ~0 for del < 0, nsg: 1 for del < 0) */
@@ -667,28 +644,14 @@ ALAC_DEV int32_t predict_narrow_core(int32_t (&coef)[NR], const uint32_t (&hb)[N
      * tap's nine instructions together. Measured against the alternative of one operation at a time over all taps
      * (independent instructions back to back): 2.45 ms vs 3.01 ms on the benchmark batch — with a partner wave on the
      * SIMD filling the gaps, short live ranges matter more than the distance between dependent instructions. */
-    int32_t acc = den_half;
-    int32_t accx = 0;                               /* sum coef_j * ex_j (ALAC_TAP_ORDER 1) */
+    int32_t accx = 0;                               /* sum coef_j * ex_j */
     uint32_t ntx = 0u - (topb ^ sgnm);              /* ex_j = (h_j ^ sgnm) + ntx */
     ALAC_OWN_REG(ntx); /* opaque: the compiler would take the sum apart again (xor + sub per tap instead of one v_xad_u32) */
     int32_t gos = 1;
 #pragma unroll
     for (int j = NR - 1; j >= 0; --j) {
         if (GEN && (uint32_t)j >= na) continue; /* scalar branch: taps the order does not have */
-#ifndef ALAC_TAP_ORDER
-#define ALAC_TAP_ORDER 2
-#endif
-#if ALAC_TAP_ORDER == 0
-        const int32_t e = (int32_t)(hb[j] - topb); /* out[i-1-j] - top; the bias cancels */
-        acc = ALAC_MAD24(coef[j], e, acc);         /* uses coef[j] before its update */
-        /* coefficient step sign(del) * -sign(top - h_j) = sign(del) * sign(e): (sign(e) ^ sgnm) + nsg */
-        const int32_t delta = (int32_t)ALAC_XAD(ALAC_SIGN(e), sgnm, nsg);
-        const uint32_t q = ALAC_SAD(topb, hb[j], rnd) >> den_shift;
-        const int32_t go = ALAC_CLAMP01(rem); /* tap j adapts while the budget is not used up */
-        const int32_t cj = ALAC_MAD24(delta, go, coef[j]);
-        coef[j] = WRAP ? (int32_t)(int16_t)cj : cj; /* predictor.go:664,675 */
-        rem = ALAC_MSUB24(rem, q, na - (uint32_t)j);
-#elif ALAC_TAP_ORDER == 1
+#if ALAC_TAP_ORDER == 1
         /* the eight-instruction tap (see below) with every instruction an asm statement, in the order of rounds 1-2: the
          * gated pair kernel (k_dec16g.hip: six pairs per CU) runs 5-8 % faster with this one than with the wait-state-free
          * order (70 000 packets 3.04 against 3.18 ms, 98 304 3.28 against 3.54), every other kernel slower */
@@ -740,9 +703,9 @@ ALAC_DEV int32_t predict_narrow_core(int32_t (&coef)[NR], const uint32_t (&hb)[N
     }
     /* den_half + sum coef_j * e_j: the chain's sum with the residual's sign taken out again ((x ^ -1) + 1 = -x) */
 #if ALAC_TAP_ORDER == 1
-    acc = (int32_t)ALAC_XAD(accx, sgnm, nsg + (uint32_t)den_half);
-#elif ALAC_TAP_ORDER == 2
-    acc = (int32_t)(((uint32_t)accx ^ sgnm) + (nsg + (uint32_t)den_half)); /* plain, like ex */
+    const int32_t acc = (int32_t)ALAC_XAD(accx, sgnm, nsg + (uint32_t)den_half);
+#else
+    const int32_t acc = (int32_t)(((uint32_t)accx ^ sgnm) + (nsg + (uint32_t)den_half)); /* plain, like ex */
 #endif
     const int32_t o = del + (int32_t)(topb ^ BIAS) + (acc >> den_shift);
     /* CB_POS: the caller knows chanBits >= 1, so the shift count is <= 31 and sext_cs' guard for 32 is not needed */

@@ -31,9 +31,6 @@ using namespace alack;
 namespace {
 
 thread_local char g_err[512] = "";
-#ifdef ALAC_DUO_PROF
-Plan* g_prof_plan = nullptr; /* profiling build: the plan of the last decode (alacgpu_debug_prof) */
-#endif
 
 void set_err(const char* fmt, ...) {
     va_list ap;
@@ -210,8 +207,6 @@ struct alacgpu_decoder {
     DevBuf cd, pd, plan2, keys2, perm2, rows;                /* split pipeline (more than two channels) */
     Slot slots[kSlots];                                      /* host-entry staging */
     CopyPool* pool;
-    uint32_t il_threads;                                     /* alac_interleave block size (64, 128 or 256) */
-    uint32_t il_four;                                        /* alac_interleave: four frames per lane (ALACGPU_IL4) */
     uint32_t n_cu;                                           /* compute units of the device */
     DevBuf cu_number;                                        /* PairArgs::cu_number */
     size_t chunk_bytes;                                      /* host entry: target bytes (in + out) per chunk */
@@ -223,7 +218,6 @@ struct alacgpu_decoder {
     size_t last_n;                                           /* the last device decode: packets, packets per wave slot, PairArgs::cap */
     uint32_t last_ppw, last_cap, last_fit5;
     uint32_t fit_force;                                      /* PairArgs::fit_force (ALACGPU_FIT) */
-    uint32_t order_exp;                                      /* ALACGPU_FIRST: 4 / 5 / 6, the launch of the narrow slots that goes first (experiments) */
 };
 
 namespace {
@@ -242,10 +236,6 @@ uint32_t pair_capacity(void (*kernel)(PairArgs)) {
         if (e.first == (const void*)kernel) return (uint32_t)e.second;
     int v = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, (int)(2 * kWave), 0) != hipSuccess || v <= 0) v = 4;
-    if (const char* e = getenv("ALACGPU_PAIR_CAP")) { /* experiments: fewer pairs per CU than would fit */
-        const int lim = atoi(e);
-        if (lim >= 1 && lim < v) v = lim;
-    }
     cache.emplace_back((const void*)kernel, v);
     return (uint32_t)v;
 }
@@ -368,9 +358,6 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
     alac::DevCfg c = dec->dev_cfg;
     c.aligned16 = (out_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_out) % 16) == 0) ? 1u : 0u;
     Plan* plan = (Plan*)dec->plan.p;
-#ifdef ALAC_DUO_PROF
-    g_prof_plan = plan;
-#endif
     const uint32_t* sz = (const uint32_t*)dec->sizes_ws.p; /* the checked sizes (alac_classify) */
     const uint32_t nb = (uint32_t)((n + 255) / 256);
     const uint32_t slot = (uint32_t)(dec->launches % kTimingSlots);
@@ -469,8 +456,7 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
             hipLaunchKernelGGL(quad_kernel(), dim3(slots), dim3(4 * kWave), (mode == kModeFit4 && stat < kQuadLdsFit4) ? kQuadLdsFit4 - stat : 0u,
                                dec->stream, q);
         };
-        uint32_t guess = decode_mode((uint32_t)((n + ppw - 1) / ppw), n_cu, a.cap, dec->fit_force, dec->cfg.num_channels == 1, a.fit5 != 0u);
-        if (dec->order_exp) guess = dec->order_exp; /* experiments (ALACGPU_FIRST): which launch goes first */
+        const uint32_t guess = decode_mode((uint32_t)((n + ppw - 1) / ppw), n_cu, a.cap, dec->fit_force, dec->cfg.num_channels == 1, a.fit5 != 0u);
         narrow(guess);
         /* the wide keys (chanBits > 23: 24- and 32-bit streams without their usual shift bytes): wave pairs */
         if (dec->cfg.bit_depth == 32) pairs(alac_decode_w32);
@@ -483,10 +469,9 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
     if (alac::lean_config(c)) {
         /* irregular packets were only scanned by alac_scan (status, frames, channel descriptors) */
         const uint64_t rs = row_stride_of(dec->cfg.frame_length);
-        /* frames per interleave block: one wavefront's worth keeps more blocks in flight per CU (the kernel waits on
-         * memory, not on arithmetic) */
-        const uint32_t il_threads = dec->il_threads;
-        const uint32_t bpp = (dec->cfg.frame_length + il_threads - 1u) / il_threads;
+        /* slices of a packet (k_split.hip), one wavefront's worth of frames each: one-wave blocks keep more blocks in flight
+         * per CU (the kernel waits on memory, not on arithmetic) */
+        const uint32_t bpp = (dec->cfg.frame_length + kWave - 1u) / kWave;
         if (dec->cfg.num_channels > 2) {
             /* split pipeline: one lane per channel, sorted by predictor order */
             Plan* plan2 = (Plan*)dec->plan2.p;
@@ -507,13 +492,12 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
         /* PCM of the split packets (with one or two channels: of the escape-only packets) */
         /* a block takes eight slices of a packet at a time (k_split.hip: kSlices) */
         /* (beside the regular packets' kernels: a few blocks per CU — it walks the scanned packets, a handful there) */
-        const uint32_t ib = (uint32_t)std::min<uint64_t>((uint64_t)n * ((bpp + 7u) / 8u),
-                                                         forked ? (uint64_t)4 * dec->n_cu : (uint64_t)8192u * (256u / il_threads));
+        const uint32_t ib = (uint32_t)std::min<uint64_t>((uint64_t)n * ((bpp + 7u) / 8u), forked ? (uint64_t)4 * dec->n_cu : (uint64_t)32768u);
         /* four frames per lane (k_split.hip: alac_interleave4) where the rows exist (more than two channels) and a frame is a whole
          * number of dwords (the layouts with a register-packed form: the others build their frames byte by byte and only lose
-         * occupancy to the bigger kernel: 16-bit 3-channel 3.25 -> 3.53 ms); ALACGPU_IL4=0: one frame per lane everywhere */
-        const uint32_t il_four = (dec->cfg.num_channels > 2 && (dec->cfg.num_channels * c.bps) % 4u == 0u && dec->il_four) ? 1u : 0u;
-        hipLaunchKernelGGL(il_four ? alac_interleave4 : alac_interleave, dim3(ib), dim3(il_threads), (il_four ? 128u : 32u) * il_threads, irr, c, d_blob, blob_bytes, d_offsets, sz,
+         * occupancy to the bigger kernel: 16-bit 3-channel 3.25 -> 3.53 ms) */
+        const bool four_frames = dec->cfg.num_channels > 2 && (dec->cfg.num_channels * c.bps) % 4u == 0u;
+        hipLaunchKernelGGL(four_frames ? alac_interleave4 : alac_interleave, dim3(ib), dim3(kWave), (four_frames ? 128u : 32u) * kWave, irr, c, d_blob, blob_bytes, d_offsets, sz,
                            (const uint32_t*)dec->perm.p, (const Plan*)plan, (const alac::ChanDesc*)dec->cd.p,
                            (const alac::PktDesc*)dec->pd.p, (const int32_t*)dec->rows.p, rs, d_out, (uint64_t)out_stride, bpp);
         hipLaunchKernelGGL(alac_legacy, dim3(scan_grid), dim3(kWave), 0, irr, c, d_blob, blob_bytes,
@@ -629,18 +613,9 @@ void configure(alacgpu_decoder* d, const alacgpu_config* cfg, int bps) {
     d->ahead_err[0] = 0;
     d->last_n = 0;
     d->last_ppw = d->last_cap = d->last_fit5 = 0;
-    d->il_threads = 64;
-    if (const char* e = getenv("ALACGPU_IL_THREADS")) {
-        const int v = atoi(e);
-        if (v == 64 || v == 128 || v == 256) d->il_threads = (uint32_t)v;
-    }
-    d->il_four = 1;
-    if (const char* e = getenv("ALACGPU_IL4")) d->il_four = (uint32_t)atoi(e);
     d->lanes_min = 4;
     d->fit_force = 0;
     if (const char* e = getenv("ALACGPU_FIT")) d->fit_force = (uint32_t)atoi(e); /* experiments: 4 / 5 workgroups per CU for every batch */
-    d->order_exp = 0;
-    if (const char* e = getenv("ALACGPU_FIRST")) d->order_exp = (uint32_t)atoi(e);
     if (const char* e = getenv("ALACGPU_LANES_MIN")) d->lanes_min = (uint32_t)std::max(1, atoi(e)); /* experiments; 17: never */
     d->side = 2;
     if (const char* e = getenv("ALACGPU_SIDE")) d->side = atoi(e); /* experiments, tests */
@@ -1186,7 +1161,7 @@ int alacgpu_last_dispatch(alacgpu_decoder* d, alacgpu_dispatch* out) {
              (lean && out->wide_slots) ? (d->cfg.bit_depth == 32 ? "alac_decode_w32" : "alac_decode_w24") : "");
     snprintf(out->irregular_kernels, sizeof(out->irregular_kernels), "%s",
              !out->irregular_slots ? "" : !alac::lean_config(d->dev_cfg) ? "alac_scan (whole-packet decoder)"
-             : d->cfg.num_channels > 2 ? ((d->cfg.num_channels * d->dev_cfg.bps) % 4u == 0u && d->il_four
+             : d->cfg.num_channels > 2 ? ((d->cfg.num_channels * d->dev_cfg.bps) % 4u == 0u
                                               ? "alac_scan + alac_chan_predict + alac_interleave4 (+ alac_legacy)"
                                               : "alac_scan + alac_chan_predict + alac_interleave (+ alac_legacy)")
                                        : "alac_scan + alac_interleave (+ alac_legacy)");
@@ -1214,16 +1189,6 @@ int alacgpu_synchronize(alacgpu_decoder* d) {
 }
 
 const char* alacgpu_last_error(void) { return g_err; }
-
-#ifdef ALAC_DUO_PROF
-/* profiling build only: the stamp sums of the last decode ([0..3] role A, [8..11] role B) */
-int alacgpu_debug_prof(unsigned long long* out16) {
-    if (!g_prof_plan) return ALACGPU_E_ARG;
-    if (hipDeviceSynchronize() != hipSuccess) return ALACGPU_E_HIP;
-    if (hipMemcpy(out16, g_prof_plan->prof, sizeof(g_prof_plan->prof), hipMemcpyDeviceToHost) != hipSuccess) return ALACGPU_E_HIP;
-    return ALACGPU_E_OK;
-}
-#endif
 
 const char* alacgpu_version(void) { return "alacgpu 0.6.0 gfx950"; }
 

@@ -20,10 +20,6 @@
 #ifndef ALAC_DECODE_ROLES
 #define ALAC_DECODE_ROLES 2 /* waves per workgroup: entropy, predictor (+ PCM), and with 3 a writer of its own */
 #endif
-/* the ungated kernels level the roles over the SIMDs too (pair_roles): 24-bit stereo, 65 536 packets: 3.59 -> 3.50 ms */
-#ifndef ALAC_NATURAL_BALANCE
-#define ALAC_NATURAL_BALANCE 1
-#endif
 /* decode_mode() / pair_quota(): alac_gpu.h (the host reads the same decision back: alacgpu_last_dispatch) */
 
 /* Which of a pair's two waves takes the entropy role (returns 1: the second one): whichever leaves the CU's SIMDs most
@@ -109,15 +105,8 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
         /* the writer: few instructions per step, but the other two wait for it at every chunk's barrier: it goes first
          * whenever it has something to issue (at the lowest priority it starved: 24-bit pairs 820 ticks per step in the
          * writer against 430 in the other two) */
-#ifndef ALAC_PRIO_C
-#define ALAC_PRIO_C 3
-#endif
         __builtin_amdgcn_s_setprio(ALAC_PRIO_C);
         (void)alac::decode_regular_duo<GpuWave, alac::ROLE_C, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC>(wv, cfg, ukey, live, p, size, avail, o, &frames);
-#ifdef ALAC_DUO_PROF
-        if (lane == 0)
-            for (int k = 0; k < 8; ++k) atomicAdd(&pair_args()->plan->prof[8 + k], wv.prof[k]);
-#endif
         return;
     }
 #else
@@ -158,10 +147,6 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
         else if (na_max >= 6u && na_max != 31u) __builtin_amdgcn_s_setprio(ALAC_PRIO_B_MID);
         else __builtin_amdgcn_s_setprio(ALAC_PRIO_B_SHORT);
         (void)alac::decode_regular_duo<GpuWave, alac::ROLE_B, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC>(wv, cfg, ukey, live, p, size, avail, o, &frames);
-#ifdef ALAC_DUO_PROF
-        if (lane == 0)
-            for (int k = 0; k < 8; ++k) atomicAdd(&pair_args()->plan->prof[16 + k], wv.prof[k]);
-#endif
         return;
     }
     /* the entropy chain is serial: it issues whenever it can, shorter predictor waves (many independent
@@ -173,10 +158,6 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
         else __builtin_amdgcn_s_setprio(ALAC_PRIO_A);
     }
     const int32_t st = alac::decode_regular_duo<GpuWave, alac::ROLE_A, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC>(wv, cfg, ukey, live, p, size, avail, o, &frames);
-#ifdef ALAC_DUO_PROF
-    if (lane == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&pair_args()->plan->prof[k], wv.prof[k]);
-#endif
     if (live) {
         PairArgsPtr kb = pair_args();
         kb->frames_out[pkt] = frames;
@@ -184,14 +165,11 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
     }
 }
 
-#ifndef ALAC_PLACE_DIAG
-#define ALAC_PLACE_DIAG 0
-#endif
-
 #if !ALAC_DECODE_GATED
 
 __global__ void __launch_bounds__(ALAC_DECODE_ROLES * kWave, ALAC_DECODE_WAVES) ALAC_DECODE_KERNEL(PairArgs) {
-#if ALAC_NATURAL_BALANCE && ALAC_DECODE_ROLES == 2
+#if ALAC_DECODE_ROLES == 2
+    /* the ungated pairs level the roles over the SIMDs too (pair_roles): 24-bit stereo, 65 536 packets: 3.59 -> 3.50 ms */
     __shared__ uint32_t s_swap, s_simd1;
     if (threadIdx.x == kWave) {
         uint32_t id;
@@ -235,13 +213,6 @@ __global__ void __launch_bounds__(ALAC_DECODE_ROLES * kWave, ALAC_DECODE_WAVES) 
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             const uint32_t cu = ((xcc & 7u) << 6) | (((id >> 13) & 3u) << 4) | ((id >> 8) & 15u);
             const uint32_t k = atomicAdd(&plan->gate[ALAC_DECODE_WIDE][cu], 1u) & 3u;
-#if ALAC_PLACE_DIAG
-            {   /* experiment builds only: where and when (alacgpu_pair_placement's record of the gated kernel) */
-                uint32_t* rec = ka->claims + 4u * (first + bid);
-                rec[0] = 0x80000000u | (cu << 8) | (k << 4);
-                rec[1] = (uint32_t)__builtin_amdgcn_s_memtime();
-            }
-#endif
             uint32_t spare = k; /* (waves that do not sit on four different SIMDs: by wave number) */
             for (uint32_t w = 0; w < 4u; ++w)
                 if (s_simd[w] == k) spare = w;
@@ -252,7 +223,7 @@ __global__ void __launch_bounds__(ALAC_DECODE_ROLES * kWave, ALAC_DECODE_WAVES) 
         role = rel == 0u ? 3u : rel - 1u;
     }
 #endif
-#if ALAC_NATURAL_BALANCE && ALAC_DECODE_ROLES == 2
+#if ALAC_DECODE_ROLES == 2
     if (threadIdx.x == 0) {
         uint32_t id, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id));
@@ -272,9 +243,6 @@ __global__ void __launch_bounds__(ALAC_DECODE_ROLES * kWave, ALAC_DECODE_WAVES) 
     pair_item(ka, first + bid, threadIdx.x & (kWave - 1u), (uint32_t)__builtin_amdgcn_readfirstlane((int)role), items <= ka->n_cu + ka->n_cu / 8u);
 #else
     pair_item(ka, first + bid, threadIdx.x & (kWave - 1u), (uint32_t)__builtin_amdgcn_readfirstlane((int)role));
-#endif
-#if ALAC_PLACE_DIAG
-    if ((threadIdx.x & (kWave - 1u)) == 0u) atomicMax(pair_args()->claims + 4u * (first + bid) + 2u, (uint32_t)__builtin_amdgcn_s_memtime());
 #endif
 }
 

@@ -193,7 +193,7 @@ static __device__ __forceinline__ void interleave_body(alac::DevCfg cfg, const u
         const uint32_t *__restrict__ sizes, const uint32_t *__restrict__ perm, const Plan *__restrict__ plan,                         \
         const alac::ChanDesc *__restrict__ cd, const alac::PktDesc *__restrict__ pd, const int32_t *__restrict__ rows, uint64_t row_stride, \
         uint8_t *__restrict__ out, uint64_t out_stride, uint32_t blocks_per_pkt
-/* one frame per lane (streams of one or two channels: escape elements only, no rows; and ALACGPU_IL4=0) */
+/* one frame per lane (streams of one or two channels: escape elements only, no rows; and frames that are not whole dwords) */
 __global__ void __launch_bounds__(256) alac_interleave(ALAC_IL_ARGS) {
     interleave_body<false>(cfg, blob, blob_bytes, offsets, sizes, perm, plan, cd, pd, rows, row_stride, out, out_stride, blocks_per_pkt);
 }
