@@ -150,7 +150,9 @@ int alacgpu_decode_packet(alacgpu_decoder* dec, const uint8_t* packet, size_t pa
  * PCM of packet i is written at out + i*out_stride (out_stride >= frame bytes);
  * frames_out[i] = the packet's sample-frame count (0 on failure), status[i] = status word.
  * A failing packet's slot and the bytes of a slot behind a partial frame read as zero (decoder.go:120,127: DecodePacket
- * hands back a prefix of a zeroed frame buffer); a failing packet does not affect others.
+ * hands back a prefix of a zeroed frame buffer); a failing packet does not affect others. Only [0, frame bytes) of a slot
+ * is written: the bytes [frame bytes, out_stride) of every slot, and everything in front of the first slot or behind the
+ * last one, stay the caller's.
  * The batch is cut into chunks that are uploaded, decoded and downloaded on three streams at once; the bytes go to
  * the device as they are. Pageable memory is staged through pinned buffers by a few copy threads
  * (ALACGPU_COPY_THREADS); blob / out / frames_out / status that the caller allocated with hipHostMalloc or registered
@@ -184,6 +186,14 @@ int alacgpu_decode_batch_wait(alacgpu_decoder* dec);
  * packets of 1-2 channel streams) run on a second stream inside the handle; it leaves the handle's stream after the
  * sort and joins it again before the decode's last event, so work a caller orders behind the handle's stream (an
  * event, a copy enqueued on alacgpu_stream()) is ordered behind those kernels as well.
+ * Footprint: packet i writes [0, d_frames_out[i] * bytes per frame) of its slot and nothing else: the bytes of a slot behind
+ * a partial frame, the bytes [frame bytes, out_stride) of every slot, and everything in front of the first slot or behind
+ * the last one are left untouched. A failing packet's slot holds unspecified bytes in [0, frame bytes): the wave pairs may
+ * have written PCM of its first samples before the error (the host entry zeroes such slots).
+ * d_out and out_stride both multiples of 16 is the fast layout. Anything else (a misaligned d_out, or a stride such as frame
+ * bytes that is not a multiple of 16) is decoded correctly, with the same bytes, but EVERY packet takes the irregular kernels
+ * (alac_scan, then alac_interleave / alac_interleave4 with byte stores, then the whole-packet decoder) and no wave-pair
+ * kernel runs; alacgpu_last_dispatch() shows narrow_slots = wide_slots = 0. That route's cost has not been measured.
  */
 int alacgpu_decode_batch_device(alacgpu_decoder* dec, const uint8_t* d_blob, size_t blob_bytes,
                                 const uint64_t* d_offsets, const uint32_t* d_sizes,

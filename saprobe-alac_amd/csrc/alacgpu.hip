@@ -929,8 +929,10 @@ int alacgpu_decode_batch(alacgpu_decoder* d, const uint8_t* blob, size_t blob_by
             const size_t pieces = std::min<size_t>(s.n, 64);
             auto body = [&](size_t k) {
                 const size_t lo = s.n * k / pieces, hi = s.n * (k + 1) / pieces;
-                if (out_stride == d_stride) {
-                    memcpy(out + (s.first + lo) * out_stride, h + lo * d_stride, (hi - lo) * d_stride - (d_stride - fb));
+                /* one copy per piece only where the rows have no gap: the staging's bytes [fb, d_stride) are stale, and the
+                 * caller's [fb, out_stride) is the caller's (a 16-byte stride over frames of fb % 16 != 0 bytes) */
+                if (out_stride == fb && d_stride == fb) {
+                    memcpy(out + (s.first + lo) * out_stride, h + lo * d_stride, (hi - lo) * fb);
                 } else {
                     for (size_t i = lo; i < hi; i++) memcpy(out + (s.first + i) * out_stride, h + i * d_stride, fb);
                 }

@@ -498,16 +498,23 @@ def test_baseline_configs_c_and_d_at_full_size(pkg, synth, oracle, gpu_decoder_f
     assert np.array_equal(ref[0], d_out[:128].cpu().numpy())
 
 
-@pytest.mark.parametrize("n,fl,profile", [(70000, 64, 0), (98304, 40, 0), (150000, 33, 3), (66000, 48, 2)])
-def test_batches_between_the_rounds_take_the_gated_pairs(pkg, synth, oracle, helpers, gpu_decoder_factory, n, fl, profile):
+@pytest.mark.parametrize("n,fl,profile,stride", [pytest.param(70000, 64, 0, 256, id="70000-64-0"),
+                                                  pytest.param(98304, 40, 0, 160, id="98304-40-0"),
+                                                  pytest.param(150000, 33, 3, 132, id="150000-33-3"),
+                                                  pytest.param(150000, 33, 3, 144, id="150000-33-3-stride144"),
+                                                  pytest.param(66000, 48, 2, 192, id="66000-48-2")])
+def test_batches_between_the_rounds_take_the_gated_pairs(pkg, synth, oracle, helpers, gpu_decoder_factory, n, fl, profile, stride):
     """16-bit batches of more than 4 x CUs wave slots but less than the next multiple (k_decode_body.inc): the gated
     kernel decodes them with five or six pairs per CU. Every regular slot is decoded exactly once by some pair, no CU
-    admits more pairs than its quota — and the PCM is the oracle's (DynDecomp / UnpcBlock / WriteStereo16, golomb.go:148, predictor.go:45, matrix.go:30)."""
+    admits more pairs than its quota — and the PCM is the oracle's (DynDecomp / UnpcBlock / WriteStereo16, golomb.go:148, predictor.go:45, matrix.go:30).
+    The dispatch read back names the route: a 16-byte multiple stride takes the 16-bit wave pairs (the gated twin between
+    four and six rounds), the 132-byte stride of 33 frames takes the irregular kernels only (alac_regular.h:
+    classify_regular), and its twin with a 144-byte stride is the wave pairs' again."""
     import torch
     cfg = oracle.make_config(fl, 16, 2)
     b = synth.gen_batch(cfg, n, profile=profile, threads=16)
     dev = torch.device("cuda:0")
-    stride = fl * 4
+    assert stride >= fl * 4
     d_blob = torch.from_numpy(b.blob).to(dev)
     d_off = torch.from_numpy(b.offsets.astype(np.int64)).to(dev)
     d_sz = torch.from_numpy(b.sizes.astype(np.int32)).to(dev)
@@ -519,12 +526,22 @@ def test_batches_between_the_rounds_take_the_gated_pairs(pkg, synth, oracle, hel
         dec.decode_batch_device(d_blob.data_ptr(), d_blob.numel(), d_off.data_ptr(), d_sz.data_ptr(), n, d_out.data_ptr(),
                                 stride, d_fr.data_ptr(), d_st.data_ptr(), sync=True)
         place = dec.pair_placement()
+        disp = dec.last_dispatch()
     ref = oracle.decode_batch(cfg, b.blob, b.offsets, b.sizes, threads=16)
     got = (d_out.cpu().numpy(), d_fr.cpu().numpy().astype(np.uint32), d_st.cpu().numpy())
     helpers.assert_same_decode(cfg, ref, got, 4, "n=%d" % n)
     tags = place[:, 0]
     owned = tags[tags != 0]
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    if stride % 16:  # no wave pair writes a row that is not 16-byte aligned: every packet is an irregular one
+        assert disp["narrow_slots"] == 0 and disp["wide_slots"] == 0 and disp["narrow_kernel"] == "", disp
+        assert disp["irregular_slots"] == disp["slots"] == len(tags) and not owned.any(), disp
+    else:
+        assert disp["narrow_slots"] > 0 and disp["narrow_kernel"] in ("alac_decode_16g", "alac_decode_16q"), disp
+        if 4 * n_cu < disp["narrow_slots"] <= 6 * n_cu:  # alac_gpu.h: decode_mode
+            assert disp["gated"] == 1 and disp["narrow_kernel"] == "alac_decode_16g", disp
+        if n_cu == 256 and n != 150000:  # the batch sizes above are chosen for an MI355X
+            assert disp["gated"] == 1, disp
     slots = len(tags)
     if slots > 4 * n_cu and slots <= 6 * n_cu:  # otherwise pair_quota leaves the batch to the ungated kernel
         assert len(owned) >= slots - 24 and (owned >> 31).all()  # all but the irregular slots, each tagged once
