@@ -252,11 +252,18 @@ ALAC_DEV void scan_channel(W& wv, const DevCfg& cfg, const B& bits, const uint8_
  *   int32_t* W::g_slot(k)            &fallback[k][lane]: general-predictor state (orders outside the class)
  * NA = predictor taps held in registers; WRAP = compile the per-lane int16 coefficient wrap.
  * Returns the status word; *frames_out = numSamples of the last element (decoder.go:206).
+ * limit (not SCAN): the packet's frame count is the LAST element's, and an element in front of it may hold more
+ * frames (a non-standard element order with shrinking partial counts): the reference writes them into its own frame
+ * buffer and hands back a prefix (decoder.go:127), but here they would land behind the packet's frames, in bytes that
+ * are the caller's (include/alacgpu.h: footprint). So an element that cannot be the last one (it does not complete
+ * the channel count) writes its frames below `limit` only, and *held says that one was cut short. Who knows the frame
+ * count (alac_legacy: the scan's) passes it; who does not runs decode_whole below.
  * ------------------------------------------------------------------------------------------------------ */
 template <class W, int NA, bool WRAP, bool SCAN = false>
 ALAC_DEV int32_t decode_wave(W& wv, const DevCfg& cfg, bool live, const uint8_t* pkt, uint32_t size, uint32_t avail,
                              uint8_t* out, uint32_t* frames_out, ChanDesc* cd = nullptr, PktDesc* pd = nullptr,
-                             int32_t* res_rows = nullptr, size_t res_stride = 0) {
+                             int32_t* res_rows = nullptr, size_t res_stride = 0, uint32_t limit = 0xffffffffu,
+                             bool* held = nullptr) {
     /* res_rows (SCAN, more than two channels): this packet's sample rows; the scan leaves every compressed channel's
      * residuals in the row of its slot for the predictor pass (wave-uniform: null for all lanes or for none) */
     /* SCAN: walk the packet exactly like a decode (same errors in the same order) but only find where every
@@ -426,6 +433,9 @@ ALAC_DEV int32_t decode_wave(W& wv, const DevCfg& cfg, bool live, const uint8_t*
         /* PCM of an element that covers the whole frame is one contiguous stream: stage it through LDS */
         staged = !SCAN && has && cfg.aligned16 != 0 && nch_e == num_chan;
         if (staged) wv.st_begin(out);
+        /* frames of this element that may be written: all of them if the walk ends behind it (decoder.go:200-202) */
+        const uint32_t wr = chan_idx + nch_e >= num_chan ? ns : umin(ns, limit);
+        if (!SCAN && held && has && wr < ns) *held = true;
 
         /* ================= phase B (wave-uniform): channels of the element, U then V ====================== */
         int32_t err = 0;
@@ -753,7 +763,7 @@ ALAC_DEV int32_t decode_wave(W& wv, const DevCfg& cfg, bool live, const uint8_t*
                                         }
                                     }
                                 }
-                            } else {
+                            } else if (i < wr) {
                                 uint8_t* dst = out + (uint64_t)i * frame_stride + out_chan * bps;
                                 store_le(dst, l, bps);
                                 if (cpe) store_le(dst + bps, r, bps);
@@ -830,6 +840,23 @@ ALAC_DEV int32_t decode_wave(W& wv, const DevCfg& cfg, bool live, const uint8_t*
     }
     *frames_out = num_samples;
     return 0;
+}
+
+/* The whole-packet decoder for callers that do not know the packet's frame count: a first pass in which only an
+ * element that ends the walk writes (every packet of a one- or two-channel stream in the standard order is done
+ * then), and for the packets that held an element back a second pass with the frame count of the first. */
+template <class W, int NA, bool WRAP>
+ALAC_DEV int32_t decode_whole(W& wv, const DevCfg& cfg, bool live, const uint8_t* pkt, uint32_t size, uint32_t avail,
+                              uint8_t* out, uint32_t* frames_out) {
+    bool held = false;
+    const int32_t st = decode_wave<W, NA, WRAP>(wv, cfg, live, pkt, size, avail, out, frames_out, nullptr, nullptr, nullptr, 0, 0u, &held);
+    const bool again = live && st == 0 && held;
+    if (wv.any(again)) {
+        uint32_t frames2 = 0;
+        (void)decode_wave<W, NA, WRAP>(wv, cfg, again, pkt, again ? size : 0u, avail, out, &frames2, nullptr, nullptr, nullptr, 0,
+                                       *frames_out);
+    }
+    return st;
 }
 
 } /* namespace alac */

@@ -74,7 +74,7 @@ static __device__ __forceinline__ void scan_slot(uint32_t b, const alac::DevCfg&
                                                         rows ? rows + (size_t)pkt * cfg.num_channels * row_stride : nullptr,
                                                         (size_t)row_stride);
     else
-        st = alac::decode_wave<GpuWave, 16, true>(wv, cfg, live, p, size, avail, o, &frames);
+        st = alac::decode_whole<GpuWave, 16, true>(wv, cfg, live, p, size, avail, o, &frames);
     if (live) {
         frames_out[pkt] = frames;
         status[pkt] = st;
@@ -133,7 +133,9 @@ static __device__ __forceinline__ void legacy_slot(uint32_t b, const alac::DevCf
     const uint32_t size = live ? sizes[pkt] : 0u;
     const uint32_t avail = avail_of(blob_bytes, off);
     uint32_t frames = 0;
-    const int32_t st = alac::decode_wave<GpuWave, 16, true>(wv, cfg, live, p, size, avail, out + (size_t)pkt * out_stride, &frames);
+    /* the scan knows the frame count: no element writes behind it (alac_wave.h: limit) */
+    const int32_t st = alac::decode_wave<GpuWave, 16, true>(wv, cfg, live, p, size, avail, out + (size_t)pkt * out_stride, &frames, nullptr,
+                                                            nullptr, nullptr, 0, live ? pd[pkt].frames : 0u);
     if (live) {
         frames_out[pkt] = frames;
         status[pkt] = st;

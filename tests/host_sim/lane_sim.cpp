@@ -238,15 +238,18 @@ extern "C" int lane_sim_decode_batch(const alacgpu_config* cfg, const uint8_t* b
                 }
                 continue;
             }
-            /* ROUTE_LEGACY: fall through to the whole-packet decoder */
+            /* ROUTE_LEGACY: the whole-packet decoder with the scan's frame count, as alac_legacy runs it */
+            status[i] = alac::decode_wave<HostWave, 16, true>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i], nullptr, nullptr, nullptr,
+                                                              0, pd.frames);
+            continue;
         }
         const uint32_t cls = variant >= 0 ? (uint32_t)variant : 3u;
         if (classes_out && variant >= 0) classes_out[i] = 1024u + cls;
         switch (cls) { /* register-tap widths of the whole-packet decoder: 4, 6, 8, or 16 with the int16 wrap */
-            case 0: status[i] = alac::decode_wave<HostWave, 4, false>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
-            case 1: status[i] = alac::decode_wave<HostWave, 6, false>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
-            case 2: status[i] = alac::decode_wave<HostWave, 8, false>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
-            default: status[i] = alac::decode_wave<HostWave, 16, true>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
+            case 0: status[i] = alac::decode_whole<HostWave, 4, false>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
+            case 1: status[i] = alac::decode_whole<HostWave, 6, false>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
+            case 2: status[i] = alac::decode_whole<HostWave, 8, false>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
+            default: status[i] = alac::decode_whole<HostWave, 16, true>(wv, dc, true, p, sizes[i], avail, o, &frames_out[i]); break;
         }
     }
     if (region) munmap(region, region_len);
