@@ -252,6 +252,44 @@ void* alacgpu_stream(alacgpu_decoder* dec);
 int alacgpu_synchronize(alacgpu_decoder* dec);
 
 /*
+ * WAVEFORMS (0.7.0): the decoder's PCM slots as planar float32 / int32 tensors, one pass of its own behind a decode (it
+ * does not touch the decode kernels or their outputs). Input is what alacgpu_decode_batch_device wrote: d_pcm / pcm_stride
+ * (its d_out / out_stride), d_frames, and d_status, which may be NULL. With
+ *     f[i]     = (d_status && d_status[i] != 0) ? 0 : min(d_frames[i], frame_length)
+ *     start[i] = f[0] + ... + f[i - 1],   total = start[n_packets]
+ * and d_wave counted in 4-byte elements:
+ *   ALACGPU_WAVE_STREAM   d_wave is [channels][channel_stride]: frame t of packet i, channel c, goes to
+ *                         d_wave[c * channel_stride + start[i] + t] — the concatenation a file reader produces, failed packets
+ *                         contributing nothing. Nothing outside [0, total) of each channel row is written.
+ *   ALACGPU_WAVE_PACKETS  d_wave is [n_packets][channels] rows: d_wave[i * packet_stride + c * channel_stride + t]; the columns
+ *                         [f[i], frame_length) of every row are written as zero (a failed packet is a silent clip), nothing behind
+ *                         column frame_length or between the rows is touched.
+ *   ALACGPU_WAVE_FLOAT    float32 = the sample as a signed integer x 2^-(w - 1), w = 16 / 24 / 24 / 32 at depth 16 / 20 / 24 / 32
+ *                         (a 20-bit sample is the 24-bit value its three bytes hold). The integer is converted with one
+ *                         rounding to nearest even and the scale is a power of two: exact up to 24 bits, rounded once at 32.
+ *   ALACGPU_WAVE_INT      int32 = the same integer, unscaled, exact at every depth.
+ * d_starts (uint64, n_packets + 1 entries, may be NULL) receives start[]; d_starts[n_packets] = total. n_packets = 0
+ * succeeds and writes d_starts[0] = 0.
+ * ALACGPU_E_ARG before any HIP call: a NULL handle, d_pcm, d_frames or d_wave; an unknown layout or type; d_wave not
+ * 4-byte aligned; pcm_stride below the frame bytes; STREAM with channel_stride < n_packets * frame_length (the bound that,
+ * with the clamp of f[i], makes a hostile d_frames harmless); PACKETS with channel_stride < frame_length or packet_stride <
+ * channels * channel_stride.
+ * Every alignment of d_pcm, pcm_stride, d_wave and the strides gives the same values; d_pcm and pcm_stride multiples of 16
+ * is what the decode wants (see above), the pass itself loads and stores 16 bytes at a time at every alignment.
+ * Asynchronous on the handle's stream unless sync != 0, with the ordering contract of alacgpu_decode_batch_device: called
+ * behind a decode with sync = 0 it runs behind that decode, no host synchronisation in between. The scan's scratch (8 bytes
+ * per packet) is the handle's; alacgpu_reserve covers it.
+ */
+typedef enum alacgpu_wave_layout { ALACGPU_WAVE_STREAM = 0, ALACGPU_WAVE_PACKETS = 1 } alacgpu_wave_layout;
+typedef enum alacgpu_wave_type { ALACGPU_WAVE_FLOAT = 0, ALACGPU_WAVE_INT = 1 } alacgpu_wave_type;
+int alacgpu_waveform_device(alacgpu_decoder* dec, const uint8_t* d_pcm, size_t pcm_stride, const uint32_t* d_frames,
+                            const int32_t* d_status, size_t n_packets, int layout, int type, void* d_wave,
+                            size_t channel_stride, size_t packet_stride, uint64_t* d_starts, int sync);
+/* Duration of the last waveform pass in milliseconds: HIP events around its kernels (valid after a sync).
+ * alacgpu_last_kernel_ms and alacgpu_kernel_times keep counting decodes only. */
+int alacgpu_waveform_last_ms(alacgpu_decoder* dec, float* ms);
+
+/*
  * Batch ENCODER (0.6.0; the reference is decode-only). Input: one contiguous interleaved little-endian PCM stream in the
  * decoder's output format (2 / 3 / 3 / 4 bytes per sample at 16 / 20 / 24 / 32 bits; a 20-bit sample is left-aligned in
  * its 3 bytes and its low 4 bits are ignored). total_frames frames become ceil(total_frames / frame_length) packets; only

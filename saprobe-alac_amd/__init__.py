@@ -31,10 +31,12 @@ _LIB = None
 
 __all__ = [
     "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "PacketEncoder", "NewPacketEncoder", "ParseMagicCookie",
-    "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim",
+    "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
+WAVE_STREAM, WAVE_PACKETS = 0, 1  # alacgpu_wave_layout
+WAVE_FLOAT, WAVE_INT = 0, 1  # alacgpu_wave_type
 
 
 def trim():
@@ -228,6 +230,10 @@ _EXPORTS = {
                                             ctypes.POINTER(ctypes.c_size_t)]),
     "alacgpu_pair_placement": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.POINTER(ctypes.c_size_t)]),
+    "alacgpu_waveform_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_waveform_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     "alacgpu_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "alacgpu_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "alacgpu_encoder_create": (ctypes.c_int, [ctypes.POINTER(PacketConfig), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
@@ -414,6 +420,90 @@ class PacketDecoder:
         _check(self._lib.alacgpu_decode_batch_device(self._h, d_blob, blob_bytes, d_offsets, d_sizes, n, d_out,
                                                      out_stride, d_frames, d_status, 1 if sync else 0))
 
+    def waveform_device(self, d_pcm, pcm_stride, d_frames, d_status, n, layout, wtype, d_wave, channel_stride,
+                        packet_stride=0, d_starts=None, sync=True):
+        """alacgpu_waveform_device: raw device pointers (ints). The PCM slots a device decode wrote (d_pcm / pcm_stride /
+        d_frames, d_status or None) -> a planar float32 (WAVE_FLOAT) or int32 (WAVE_INT) waveform at d_wave, strides in
+        elements: WAVE_STREAM [channels][channel_stride], the packets' frames back to back with failed packets left out;
+        WAVE_PACKETS [n][channels] rows of FrameLength columns, zero behind a packet's frames. d_starts (n + 1 uint64, or
+        None) gets the packets' first columns and the total. Runs on the handle's stream, behind a decode with sync=False."""
+        _check(self._lib.alacgpu_waveform_device(self._h, d_pcm, pcm_stride, d_frames, d_status, n, layout, wtype, d_wave,
+                                                 channel_stride, packet_stride, d_starts, 1 if sync else 0))
+
+    def waveform_last_ms(self):
+        """alacgpu_waveform_last_ms: HIP events around the kernels of the last waveform pass."""
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_waveform_last_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def decode_waveform(self, blob, offsets, sizes=None, layout="stream", dtype=None):
+        """Decode and convert on the device -> (wave, frames, status), torch tensors on the handle's device.
+
+        blob: the packets' bytes, offsets: packet i's first byte (n entries with `sizes`, n + 1 without); numpy arrays or
+        bytes are uploaded, CUDA tensors are used where they are. layout "stream": wave is [channels, total], the packets'
+        frames back to back, failed packets (status != 0) left out; "packets": [n, channels, FrameLength], zero behind a
+        packet's frames. dtype torch.float32 (samples x 2^-(w - 1), torchaudio's scale) or torch.int32 (the integers)."""
+        return self._decode_waveform(blob, offsets, sizes, layout, dtype)
+
+    def _decode_waveform(self, blob, offsets, sizes, layout, dtype, into=None):
+        """decode_waveform; into = (tensor [channels, capacity], column): "stream" writes there, from that column on,
+        instead of allocating (load() fills one tensor window by window)."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.int32):
+            raise ValueError("dtype must be torch.float32 or torch.int32")
+        if layout not in ("stream", "packets"):
+            raise ValueError("layout must be 'stream' or 'packets'")
+        dev = torch.device("cuda", self.device)
+
+        def up(x, np_dtype, t_dtype):
+            if isinstance(x, torch.Tensor):
+                return x.to(device=dev, dtype=t_dtype).contiguous()
+            if isinstance(x, (bytes, bytearray, memoryview)):
+                x = np.frombuffer(x, dtype=np.uint8)
+            a = np.ascontiguousarray(x, dtype=np_dtype)
+            if t_dtype is not torch.uint8:
+                a = a.view({8: np.int64, 4: np.int32}[a.itemsize])  # torch has no unsigned 32- / 64-bit tensors
+            return torch.from_numpy(a.copy() if not a.flags.writeable else a).to(dev)
+
+        d_blob = up(blob, np.uint8, torch.uint8)
+        d_off = up(offsets, np.uint64, torch.int64)
+        d_sz = None if sizes is None else up(sizes, np.uint32, torch.int32)
+        n = d_off.numel() - (1 if d_sz is None else 0)
+        if n < 0:
+            raise ValueError("offsets without sizes needs n + 1 entries, at least one")
+        if d_sz is not None and d_sz.numel() != n:
+            raise ValueError("offsets and sizes differ in length")
+        fl, ch = int(self.config.FrameLength), int(self.config.NumChannels)
+        stride = (self.frame_bytes + 15) // 16 * 16  # the decode's fast layout
+        pcm = torch.empty((max(n, 1), stride), dtype=torch.uint8, device=dev)
+        frames = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        starts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        col = 0
+        if layout == "stream":
+            if into is not None:
+                wave, col = into
+                if wave.dtype is not dtype or not wave.is_contiguous() or wave.shape[0] != ch or wave.shape[1] - col < n * fl:
+                    raise ValueError("the waveform buffer does not take %d packets from column %d on" % (n, col))
+            else:
+                wave = torch.empty((ch, max(n * fl, 1)), dtype=dtype, device=dev)
+            cs, ps = wave.shape[1], 0
+        else:
+            wave = torch.empty((n, ch, fl), dtype=dtype, device=dev)
+            cs, ps = fl, ch * fl
+        torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+        if n > 0:
+            self.decode_batch_device(d_blob.data_ptr() if d_blob.numel() else None, d_blob.numel(), d_off.data_ptr(),
+                                     None if d_sz is None else d_sz.data_ptr(), n, pcm.data_ptr(), stride, frames.data_ptr(),
+                                     status.data_ptr(), sync=False)
+        self.waveform_device(pcm.data_ptr(), stride, frames.data_ptr(), status.data_ptr(), n,
+                             WAVE_STREAM if layout == "stream" else WAVE_PACKETS, WAVE_FLOAT if dtype is torch.float32 else WAVE_INT,
+                             wave.data_ptr() + 4 * col, cs, ps, starts.data_ptr(), sync=True)
+        if layout == "stream":
+            wave = wave[:, col:col + int(starts[n].item())]
+        return wave, frames[:n], status[:n]
+
     def reserve(self, n_packets):
         _check(self._lib.alacgpu_reserve(self._h, n_packets))
 
@@ -568,6 +658,42 @@ def NewDecoder(source, device=0, window=1024):
     """NewDecoder (decode.go:50-76): streaming façade over the batch path, see stream.py."""
     from . import stream
     return stream.NewDecoder(source, device=device, window=window)
+
+
+def load(source, device=0, dtype=None):
+    """An ALAC M4A/MP4 file -> (waveform [channels, frames], sample_rate), the call shape of torchaudio.load: a planar
+    torch tensor on cuda:`device`, float32 in [-1, 1) (dtype=torch.int32: the integer samples). source: a path, a binary file
+    object, or the file's bytes. The track is found and configured as NewDecoder does it (ErrNoTrack / ErrConfig); the packets
+    are decoded and converted on the device in windows of 48 MB of PCM into one tensor, and the first packet that fails
+    raises the ErrDecode that Read raises when it gets there."""
+    import torch
+    from . import stream
+    dtype = torch.float32 if dtype is None else dtype
+    _, view, track, cfg = stream.open_track(source)
+    raw = np.frombuffer(view, dtype=np.uint8)
+    offs, sizes = track.offsets.astype(np.int64), track.sizes.astype(np.int64)
+    n, fl, ch = len(sizes), int(cfg.FrameLength), int(cfg.NumChannels)
+    lost = np.nonzero(offs + sizes > raw.size)[0]
+    n_ok = int(lost[0]) if len(lost) else n
+    dev = torch.device("cuda", device)
+    with NewPacketDecoder(cfg, device) as dec:
+        window = stream.window_packets(dec.frame_bytes)
+        dec.reserve(min(window, max(1, n_ok)))
+        wave = torch.empty((ch, max(n_ok * fl, 1)), dtype=dtype, device=dev)
+        total = 0
+        for w0 in range(0, n_ok, window):
+            w1 = min(w0 + window, n_ok)
+            lo, hi = int(offs[w0:w1].min()), int((offs[w0:w1] + sizes[w0:w1]).max())
+            part, _, status = dec._decode_waveform(raw[lo:hi], offs[w0:w1] - lo, sizes[w0:w1], "stream", dtype, into=(wave, total))
+            bad = torch.nonzero(status)
+            if bad.numel():
+                k = int(bad[0].item())
+                e = status_error(int(status[k].item()))
+                raise ErrDecode("decoding packet %d: %s" % (w0 + k, e), status=e.status, sentinel=e.sentinel)
+            total += part.shape[1]
+    if n_ok < n:
+        raise AlacError("reading sample %d: unexpected EOF" % n_ok)
+    return wave[:, :total], int(cfg.SampleRate)
 
 
 def FindALACTrack(data):

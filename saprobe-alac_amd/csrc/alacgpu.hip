@@ -19,12 +19,14 @@
  *   alac_task_classify / alac_plan / alac_scatter / alac_chan_predict   (> 2 channels) one wavefront per 64
  *                  (packet, channel) tasks of the same order: the predictor over the stored residuals, in place
  *   alac_interleave, alac_legacy   PCM of the scanned packets (frame order), whole-packet decoder for the rest
+ * alacgpu_waveform_device is a pass of its own behind a decode (k_wave.hip, alac_waveform.h): PCM slots -> planar waveforms.
  * The kernels live in k_sort.hip, k_scan.hip, k_dec*.hip and k_split.hip (alac_gpu.h).
  * HBM traffic per packet: compressed bytes in, PCM bytes out, plus the U-channel hand-off tile of stereo pairs
  * ((frame_length + 1) x 64 x int32 per workgroup, row-coalesced, written once and read once) or the sample rows
  * of the split pipeline.
  */
 #include "alac_gpu.h"
+#include "alac_waveform.h"
 
 using namespace alack;
 
@@ -218,6 +220,9 @@ struct alacgpu_decoder {
     size_t last_n;                                           /* the last device decode: packets, packets per wave slot, PairArgs::cap */
     uint32_t last_ppw, last_cap, last_fit5;
     uint32_t fit_force;                                      /* PairArgs::fit_force (ALACGPU_FIT) */
+    DevBuf wave_ws;                                          /* alacgpu_waveform_device: the scan's scratch */
+    hipEvent_t ev_w0, ev_w1;                                 /* around the kernels of the last waveform pass */
+    bool wave_timed;
 };
 
 namespace {
@@ -576,7 +581,7 @@ void really_destroy(alacgpu_decoder* d) {
     if (d->s_side) (void)hipStreamSynchronize(d->s_side);
     delete d->pool;
     DevBuf* bufs[] = {&d->cu_number, &d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->cd, &d->pd,
-                      &d->plan2, &d->keys2, &d->perm2, &d->rows};
+                      &d->plan2, &d->keys2, &d->perm2, &d->rows, &d->wave_ws};
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < kSlots; k++) {
         Slot& s = d->slots[k];
@@ -598,6 +603,8 @@ void really_destroy(alacgpu_decoder* d) {
     if (d->s_side) (void)hipStreamDestroy(d->s_side);
     if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
     if (d->ev_join) (void)hipEventDestroy(d->ev_join);
+    if (d->ev_w0) (void)hipEventDestroy(d->ev_w0);
+    if (d->ev_w1) (void)hipEventDestroy(d->ev_w1);
     delete d;
 }
 
@@ -613,6 +620,7 @@ void configure(alacgpu_decoder* d, const alacgpu_config* cfg, int bps) {
     d->ahead_err[0] = 0;
     d->last_n = 0;
     d->last_ppw = d->last_cap = d->last_fit5 = 0;
+    d->wave_timed = false;
     d->lanes_min = 4;
     d->fit_force = 0;
     if (const char* e = getenv("ALACGPU_FIT")) d->fit_force = (uint32_t)atoi(e); /* experiments: 4 / 5 workgroups per CU for every batch */
@@ -676,7 +684,7 @@ int alacgpu_create(const alacgpu_config* cfg, int device, alacgpu_decoder** out)
         d->n_cu = cus > 0 ? (uint32_t)cus : 256u;
     }
     d->stream = d->s_in = d->s_out = d->s_side = nullptr;
-    d->ev_fork = d->ev_join = nullptr;
+    d->ev_fork = d->ev_join = d->ev_w0 = d->ev_w1 = nullptr;
     for (uint32_t i = 0; i < kTimingSlots; i++) d->ev_start[i] = d->ev_stop[i] = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s_in, hipStreamNonBlocking);
@@ -686,6 +694,8 @@ int alacgpu_create(const alacgpu_config* cfg, int device, alacgpu_decoder** out)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s_side, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreate(&d->ev_w0);
+    if (e == hipSuccess) e = hipEventCreate(&d->ev_w1);
     for (uint32_t i = 0; i < kTimingSlots && e == hipSuccess; i++) {
         e = hipEventCreate(&d->ev_start[i]);
         if (e == hipSuccess) e = hipEventCreate(&d->ev_stop[i]);
@@ -718,7 +728,7 @@ void alacgpu_destroy(alacgpu_decoder* d) {
     if (ok) {
         for (int k = 0; k < kSlots; k++) d->slots[k].busy = false;
         std::vector<DevBuf*> dev = {&d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->cd, &d->pd,
-                                    &d->plan2, &d->keys2, &d->perm2, &d->rows};
+                                    &d->plan2, &d->keys2, &d->perm2, &d->rows, &d->wave_ws};
         std::vector<decltype(&d->slots[0].h_in)> pinned;
         for (int k = 0; k < kSlots; k++) {
             Slot& s = d->slots[k];
@@ -826,6 +836,7 @@ size_t alacgpu_frame_bytes(const alacgpu_decoder* d) { return d ? d->frame_bytes
 int alacgpu_reserve(alacgpu_decoder* d, size_t n) {
     if (!d) return ALACGPU_E_ARG;
     HIP_TRY(hipSetDevice(d->device));
+    if (int rc = d->wave_ws.ensure(alack::wave_scratch_bytes(n))) return rc;
     return reserve_workspace(d, n, pick_ppw(n));
 }
 
@@ -1181,6 +1192,75 @@ int alacgpu_last_kernel_ms(alacgpu_decoder* d, float* ms) {
     return ALACGPU_E_OK;
 }
 
+int alacgpu_waveform_device(alacgpu_decoder* d, const uint8_t* d_pcm, size_t pcm_stride, const uint32_t* d_frames,
+                            const int32_t* d_status, size_t n, int layout, int type, void* d_wave, size_t channel_stride,
+                            size_t packet_stride, uint64_t* d_starts, int sync) {
+    if (!d || (n && (!d_pcm || !d_frames || !d_wave))) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    if ((layout != ALACGPU_WAVE_STREAM && layout != ALACGPU_WAVE_PACKETS) || (type != ALACGPU_WAVE_FLOAT && type != ALACGPU_WAVE_INT)) {
+        set_err("unknown waveform layout %d or type %d", layout, type);
+        return ALACGPU_E_ARG;
+    }
+    if (n > 0x7fffffffu) {
+        set_err("batch too large");
+        return ALACGPU_E_ARG;
+    }
+    const uint64_t fl = d->cfg.frame_length, ch = d->cfg.num_channels;
+    if (n) {
+        if (pcm_stride < d->frame_bytes) {
+            set_err("pcm_stride %zu < frame bytes %zu", pcm_stride, d->frame_bytes);
+            return ALACGPU_E_ARG;
+        }
+        if (reinterpret_cast<uintptr_t>(d_wave) % 4) {
+            set_err("d_wave is not aligned to its 4-byte elements");
+            return ALACGPU_E_ARG;
+        }
+        /* with f[i] <= frame_length (the kernels clamp) these bounds keep every column inside its row whatever d_frames holds */
+        if (layout == ALACGPU_WAVE_STREAM ? channel_stride < (uint64_t)n * fl
+                                          : (channel_stride < fl || packet_stride / ch < channel_stride)) {
+            set_err("channel_stride %zu / packet_stride %zu too small for %zu packets of %u frames", channel_stride, packet_stride, n,
+                    d->cfg.frame_length);
+            return ALACGPU_E_ARG;
+        }
+    }
+    HIP_TRY(hipSetDevice(d->device));
+    /* Growing the scratch frees it first, while an earlier pass with sync = 0 and a smaller n may still be queued on the
+     * stream and reading it: that is safe only because hipFree waits for the whole device before it lets go of the memory
+     * (the same holds for the decode's workspace, alacgpu_reserve's comment in alacgpu.h). Callers that queue passes back
+     * to back reserve for their largest batch first and never get here with a buffer to grow. */
+    if (n && (layout == ALACGPU_WAVE_STREAM || d_starts)) {
+        if (int rc = d->wave_ws.ensure(alack::wave_scratch_bytes(n))) return rc;
+    }
+    alacwf::Params p = alacwf::make_params(d->cfg.frame_length, d->cfg.bit_depth, d->cfg.num_channels, (uint32_t)layout, (uint32_t)type);
+    p.pcm = d_pcm;
+    p.pcm_stride = pcm_stride;
+    p.frames = d_frames;
+    p.status = d_status;
+    p.wave = (uint8_t*)d_wave;
+    p.channel_stride = channel_stride;
+    p.packet_stride = packet_stride;
+    p.n = n;
+    HIP_TRY(hipEventRecord(d->ev_w0, d->stream));
+    HIP_TRY(alack::wave_launch(d->stream, p, d_starts, d->wave_ws.p));
+    HIP_TRY(hipEventRecord(d->ev_w1, d->stream));
+    d->wave_timed = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(d->stream));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_waveform_last_ms(alacgpu_decoder* d, float* ms) {
+    if (!d || !ms || !d->wave_timed) {
+        set_err(!d || !ms ? "null argument" : "no waveform pass on this handle yet");
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipEventSynchronize(d->ev_w1));
+    HIP_TRY(hipEventElapsedTime(ms, d->ev_w0, d->ev_w1));
+    return ALACGPU_E_OK;
+}
+
 void* alacgpu_stream(alacgpu_decoder* d) { return d ? (void*)d->stream : nullptr; }
 
 int alacgpu_synchronize(alacgpu_decoder* d) {
@@ -1192,7 +1272,7 @@ int alacgpu_synchronize(alacgpu_decoder* d) {
 
 const char* alacgpu_last_error(void) { return g_err; }
 
-const char* alacgpu_version(void) { return "alacgpu 0.6.0 gfx950"; }
+const char* alacgpu_version(void) { return "alacgpu 0.7.0 gfx950"; }
 
 } /* extern "C" */
 

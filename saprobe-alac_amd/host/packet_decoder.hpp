@@ -83,6 +83,22 @@ public:
             throw std::runtime_error(alacgpu_last_error());
     }
 
+    // Waveforms (alacgpu_waveform_device): the PCM slots of a device decode -> a planar float32 / int32 tensor in the caller's
+    // device buffer, on the handle's stream (behind an alacgpu_decode_batch_device(..., sync = 0) with no host sync in
+    // between). Strides in elements; d_status and d_starts may be null. Layout and element type: include/alacgpu.h.
+    void WaveformDevice(const uint8_t* d_pcm, size_t pcm_stride, const uint32_t* d_frames, const int32_t* d_status, size_t n,
+                        alacgpu_wave_layout layout, alacgpu_wave_type type, void* d_wave, size_t channel_stride,
+                        size_t packet_stride = 0, uint64_t* d_starts = nullptr, bool sync = true) {
+        if (alacgpu_waveform_device(h_.get(), d_pcm, pcm_stride, d_frames, d_status, n, layout, type, d_wave, channel_stride,
+                                    packet_stride, d_starts, sync ? 1 : 0) != ALACGPU_E_OK)
+            throw std::runtime_error(alacgpu_last_error());
+    }
+    float WaveformLastMs() {
+        float ms = 0;
+        if (alacgpu_waveform_last_ms(h_.get(), &ms) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        return ms;
+    }
+
     alacgpu_decoder* handle() const { return h_.get(); }
     // alacgpu_trim(): destroyed decoders leave streams, events and small buffers (<= 2 GB of device memory and
     // 64 MB of pinned memory each, four per device) in a per-process pool for the next one; this frees them

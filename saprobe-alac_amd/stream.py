@@ -36,32 +36,44 @@ def _as_buffer(source):
     return source
 
 
+def open_track(source):
+    """What NewDecoder does before it decodes (decode.go:50-59): the file in memory, its ALAC track and the track's
+    configuration -> (data, view, track, config). Raises ErrNoTrack / ErrConfig with the reference's wrapping."""
+    data = _as_buffer(source)
+    view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(data)
+    try:
+        track = mp4.find_alac_track(view)
+    except mp4.Mp4Error as e:  # decode.go:52-54
+        err = ErrNoTrack("%s: %s" % (ErrNoTrackText, e))
+        err.sentinel = e.sentinel
+        raise err from None
+    try:
+        config = ParseMagicCookie(track.cookie)
+    except ErrConfig as e:  # decode.go:57-59
+        err = ErrConfig("parsing ALAC config: %s" % e)
+        err.sentinel = e.sentinel
+        raise err from None
+    return data, view, track, config
+
+
+def window_packets(frame_bytes):
+    """Packets per batch decode of a file: as many as make 48 MB of PCM, at least 64 (host/stream_decoder.hpp)."""
+    return max(64, (48 << 20) // max(1, frame_bytes))
+
+
 class Decoder:
     """Streams decoded PCM from an ALAC M4A/MP4 source (decode.go:32-45). `window` = packets per batch decode; 0: as many
     as make 48 MB of PCM (host/stream_decoder.hpp)."""
 
     def __init__(self, source, device=0, window=0):
-        self._data = _as_buffer(source)
-        self._view = memoryview(self._data).cast("B") if not isinstance(self._data, np.ndarray) else memoryview(self._data)
-        try:
-            track = mp4.find_alac_track(self._view)
-        except mp4.Mp4Error as e:  # decode.go:52-54
-            err = ErrNoTrack("%s: %s" % (ErrNoTrackText, e))
-            err.sentinel = e.sentinel
-            raise err from None
-        try:
-            self.config = ParseMagicCookie(track.cookie)
-        except ErrConfig as e:  # decode.go:57-59
-            err = ErrConfig("parsing ALAC config: %s" % e)
-            err.sentinel = e.sentinel
-            raise err from None
+        self._data, self._view, track, self.config = open_track(source)
         self._dec = NewPacketDecoder(self.config, device)
         self._decs = (self._dec, NewPacketDecoder(self.config, device))  # destroyed handles are pooled by the library
         for d in self._decs:
-            d.reserve(min(int(window) if int(window) > 0 else max(64, (48 << 20) // max(1, self._dec.frame_bytes)), max(1, len(track.sizes))))
+            d.reserve(min(int(window) if int(window) > 0 else window_packets(self._dec.frame_bytes), max(1, len(track.sizes))))
         self._offsets, self._sizes = track.offsets, track.sizes
         self._bpf = self.config.NumChannels * bytes_per_sample(self.config.BitDepth)
-        self._window = int(window) if int(window) > 0 else max(64, (48 << 20) // max(1, self._dec.frame_bytes))
+        self._window = int(window) if int(window) > 0 else window_packets(self._dec.frame_bytes)
         self._idx = 0                    # sampleIdx: next packet to hand out
         self._buf = b""                  # PCM of the packet being drained (decode.go:40-42)
         self._buf_off = 0
