@@ -10,17 +10,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <mutex>
-#include <new>
-#include <thread>
-#include <vector>
 
 #define ALAC_DEV __device__ __forceinline__
 #define ALAC_HD __host__ __device__ __forceinline__

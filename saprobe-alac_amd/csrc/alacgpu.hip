@@ -26,81 +26,21 @@
  * of the split pipeline.
  */
 #include "alac_gpu.h"
+#include "alac_host.h"
 #include "alac_waveform.h"
 
 using namespace alack;
 
 namespace {
-
 thread_local char g_err[512] = "";
+}
 
-void set_err(const char* fmt, ...) {
+void alack::set_err(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return ALACGPU_E_HIP;                                                             \
-        }                                                                                     \
-    } while (0)
-
-int bytes_per_sample(uint8_t depth) { /* BytesPerSample, internal/alac/format.go:23-34 */
-    switch (depth) {
-        case 16: return 2;
-        case 20:
-        case 24: return 3;
-        case 32: return 4;
-        default: return 0;
-    }
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return ALACGPU_E_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        HIP_TRY(hipMalloc(&p, want));
-        cap = want;
-        return ALACGPU_E_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-struct HostBuf { /* pinned staging */
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return ALACGPU_E_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
-        cap = want;
-        return ALACGPU_E_OK;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-} /* namespace */
 
 /* ---- host-side copy helpers of the host entry -------------------------------------------------------------- */
 namespace {
@@ -179,6 +119,12 @@ private:
     bool stop_ = false;
 };
 
+/* fn(k) for k in [0, pieces): on the pool if there is one, else on the caller alone */
+void copy_pieces(CopyPool* pool, size_t pieces, const std::function<void(size_t)>& fn) {
+    if (pool) pool->parallel_for(pieces, fn);
+    else for (size_t k = 0; k < pieces; k++) fn(k);
+}
+
 constexpr int kSlots = 3; /* chunks in flight in the host entry: one uploading, one decoding, one downloading */
 
 /* one chunk of the host entry: device and pinned staging for its packets and its PCM */
@@ -192,11 +138,52 @@ struct Slot {
     bool bad = false; /* the chunk holds descriptors that leave the blob (ALACGPU_ERR_RANGE, set on the way back) */
 };
 
+/* Which kernels a handle launches: chosen once per configuration (choose_kernels, called by configure). launch() launches
+ * from it and alacgpu_last_dispatch reports from it. Which of the narrow launches WORKS is not in here: that is decode_mode
+ * (alac_gpu.h), evaluated on the device and again in alacgpu_last_dispatch. */
+struct PairKernel {
+    void (*fn)(PairArgs); /* nullptr: the configuration has none */
+    const char* name;
+};
+struct Kernels {
+    bool lean;                       /* alac::lean_config: else alac_scan is the whole-packet decoder of every packet */
+    bool one_or_two;                 /* channels: with `lean`, the regular packets have kernels of their own; more: the split pipeline */
+    PairKernel quad;                 /* narrow regular keys: the four-wave kernel */
+    PairKernel gated;                /* ... and its gated twin of wave pairs (16-bit only) */
+    PairKernel wide;                 /* wide keys: wave pairs (24- and 32-bit only) */
+    decltype(&alac_interleave) interleave;
+    uint32_t interleave_lds;         /* its dynamic LDS */
+    const char* irregular;           /* alacgpu_dispatch::irregular_kernels */
+};
+#define ALAC_PAIR_KERNEL(k) PairKernel{k, #k}
+Kernels choose_kernels(const alac::DevCfg& c) {
+    Kernels k{};
+    k.lean = alac::lean_config(c); /* pb and kb only: aligned16 has no say */
+    k.one_or_two = c.num_channels <= 2;
+    k.quad = c.bit_depth == 16 ? ALAC_PAIR_KERNEL(alac_decode_16q) : c.bit_depth == 32 ? ALAC_PAIR_KERNEL(alac_decode_32q) : ALAC_PAIR_KERNEL(alac_decode_24q); /* 24: 20 and 24 */
+    k.gated = c.bit_depth == 16 ? ALAC_PAIR_KERNEL(alac_decode_16g) : PairKernel{nullptr, ""};
+    /* the wide keys (chanBits > 23: 24- and 32-bit streams without their usual shift bytes): wave pairs */
+    k.wide = c.bit_depth == 32 ? ALAC_PAIR_KERNEL(alac_decode_w32) : c.bit_depth == 24 ? ALAC_PAIR_KERNEL(alac_decode_w24) : PairKernel{nullptr, ""};
+    /* four frames per lane (k_split.hip: alac_interleave4) where the rows exist (more than two channels) and a frame is a whole
+     * number of dwords (the layouts with a register-packed form: the others build their frames byte by byte and only lose
+     * occupancy to the bigger kernel: 16-bit 3-channel 3.25 -> 3.53 ms) */
+    const bool four_frames = c.num_channels > 2 && (c.num_channels * c.bps) % 4u == 0u;
+    k.interleave = four_frames ? alac_interleave4 : alac_interleave;
+    k.interleave_lds = (four_frames ? 128u : 32u) * kWave;
+    k.irregular = !k.lean        ? "alac_scan (whole-packet decoder)"
+                  : k.one_or_two ? "alac_scan + alac_interleave (+ alac_legacy)"
+                  : four_frames  ? "alac_scan + alac_chan_predict + alac_interleave4 (+ alac_legacy)"
+                                 : "alac_scan + alac_chan_predict + alac_interleave (+ alac_legacy)";
+    return k;
+}
+#undef ALAC_PAIR_KERNEL
+
 } /* namespace */
 
 struct alacgpu_decoder {
     alacgpu_config cfg;
     alac::DevCfg dev_cfg;
+    Kernels kernels;                                          /* of this configuration */
     int device;
     size_t frame_bytes;
     hipStream_t stream;                                       /* kernels */
@@ -230,34 +217,29 @@ namespace {
 size_t plan_claims_offset() { return (sizeof(Plan) + 255u) & ~(size_t)255u; }
 size_t plan_bytes(size_t waves) { return plan_claims_offset() + waves * 4 * sizeof(uint32_t); }
 
-/* wave pairs of a pair kernel one CU holds at a time (registers and LDS, as the runtime computes it); asked once per
- * kernel: the cache is keyed by the kernel's address (every pair kernel has the same function type, so a function-local
- * static of a template on that type would be ONE cache for all of them); every device here is the same model */
-uint32_t pair_capacity(void (*kernel)(PairArgs)) {
+/* What launch() asks the runtime about a kernel, asked once per kernel: the cache is keyed by the kernel's address (every
+ * pair kernel has the same function type, so a function-local static of a template on that type would be ONE cache for
+ * all of them); every device here is the same model.
+ * pairs_per_cu: wave pairs of a pair kernel one CU holds at a time (registers and LDS, as the runtime computes it).
+ * static_lds: static LDS of a four-wave kernel (what the "fit 4" launch pads up to kQuadLdsFit4: alac_gpu.h). */
+struct KernelAttr {
+    uint32_t pairs_per_cu, static_lds;
+};
+KernelAttr kernel_attr(void (*kernel)(PairArgs)) {
     static std::mutex mu;
-    static std::vector<std::pair<const void*, int>> cache;
-    std::lock_guard<std::mutex> g(mu);
-    for (const auto& e : cache)
-        if (e.first == (const void*)kernel) return (uint32_t)e.second;
-    int v = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, (int)(2 * kWave), 0) != hipSuccess || v <= 0) v = 4;
-    cache.emplace_back((const void*)kernel, v);
-    return (uint32_t)v;
-}
-
-/* static LDS of a four-wave kernel (what the "fit 4" launch pads up to kQuadLdsFit4: alac_gpu.h), asked once per kernel */
-uint32_t quad_static_lds(void (*kernel)(PairArgs)) {
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, uint32_t>> cache;
+    static std::vector<std::pair<const void*, KernelAttr>> cache;
     std::lock_guard<std::mutex> g(mu);
     for (const auto& e : cache)
         if (e.first == (const void*)kernel) return e.second;
+    int v = 0;
     hipFuncAttributes at;
-    uint32_t v = kQuadLdsFit4; /* unknown: no pad, and no second launch */
-    if (hipFuncGetAttributes(&at, (const void*)kernel) == hipSuccess) v = (uint32_t)at.sharedSizeBytes;
+    KernelAttr a{4u, kQuadLdsFit4}; /* unknown: four pairs; no pad, and no second launch */
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, (int)(2 * kWave), 0) == hipSuccess && v > 0) a.pairs_per_cu = (uint32_t)v;
     else (void)hipGetLastError();
-    cache.emplace_back((const void*)kernel, v);
-    return v;
+    if (hipFuncGetAttributes(&at, (const void*)kernel) == hipSuccess) a.static_lds = (uint32_t)at.sharedSizeBytes;
+    else (void)hipGetLastError();
+    cache.emplace_back((const void*)kernel, a);
+    return a;
 }
 
 /* Numbers the device's compute units for the pair kernels (k_decode_body.inc): XCD by XCD, so that CU number c is on
@@ -345,6 +327,175 @@ int reserve_workspace(alacgpu_decoder* dec, size_t n, uint32_t ppw) {
     return ALACGPU_E_OK;
 }
 
+/* One decode on its way through launch(): the handle, the caller's arguments, and where the irregular packets' kernels go */
+struct Launch {
+    alacgpu_decoder* dec;
+    alac::DevCfg c; /* the handle's, with aligned16 as this call's output allows */
+    const uint8_t* d_blob; /* the caller's arguments */
+    uint64_t blob_bytes;
+    const uint64_t* d_offsets;
+    size_t n;
+    uint8_t* d_out;
+    size_t out_stride;
+    uint32_t* d_frames;
+    int32_t* d_status;
+    uint32_t ppw;
+    size_t waves;       /* max_waves of the batch */
+    hipStream_t irr;    /* the handle's stream, or s_side when forked */
+    bool forked;
+    uint32_t scan_grid; /* workgroups of alac_scan / alac_legacy */
+    Plan* plan() const { return (Plan*)dec->plan.p; }
+    const uint32_t* sz() const { return (const uint32_t*)dec->sizes_ws.p; } /* the checked sizes (alac_classify) */
+};
+
+/* s_side beside `stream`: it leaves `stream` behind the sort (ev_fork) and is back before the stop event (ev_join). Between
+ * fork() and a join() that got through, an error must not leave s_side running behind the caller's back: whoever drops the
+ * fork half-done waits for s_side. */
+struct SideFork {
+    alacgpu_decoder* dec;
+    bool open = false;
+    int fork() {
+        HIP_TRY(hipEventRecord(dec->ev_fork, dec->stream));
+        HIP_TRY(hipStreamWaitEvent(dec->s_side, dec->ev_fork, 0));
+        open = true;
+        return ALACGPU_E_OK;
+    }
+    int join() {
+        HIP_TRY(hipEventRecord(dec->ev_join, dec->s_side));
+        HIP_TRY(hipStreamWaitEvent(dec->stream, dec->ev_join, 0));
+        open = false;
+        return ALACGPU_E_OK;
+    }
+    ~SideFork() {
+        if (open) (void)hipStreamSynchronize(dec->s_side);
+    }
+};
+
+/* the sort: keys, plan, lane permutation. d_sizes may be null (packet i = blob[offsets[i], offsets[i+1])) */
+int sort_pass(const Launch& L, const uint32_t* d_sizes) {
+    alacgpu_decoder* dec = L.dec;
+    const uint32_t nb = (uint32_t)((L.n + 255) / 256);
+    HIP_TRY(hipMemsetAsync(L.plan(), 0, plan_bytes(L.waves), dec->stream));
+    hipLaunchKernelGGL(alac_classify, dim3(nb), dim3(256), 0, dec->stream, L.c, L.d_blob, L.blob_bytes, L.d_offsets, d_sizes,
+                       (uint32_t)L.n, (uint16_t*)dec->cls.p, (uint32_t*)dec->sizes_ws.p, L.d_frames, L.d_status, L.plan());
+    hipLaunchKernelGGL(alac_plan, dim3(1), dim3(kWave), 0, dec->stream, L.plan(), L.ppw);
+    hipLaunchKernelGGL(alac_scatter, dim3(nb), dim3(256), 0, dec->stream, (const uint16_t*)dec->cls.p, (uint32_t)L.n, L.plan(),
+                       (uint32_t*)dec->perm.p);
+    return ALACGPU_E_OK;
+}
+
+void scan(const Launch& L) {
+    alacgpu_decoder* dec = L.dec;
+    hipLaunchKernelGGL(alac_scan, dim3(L.scan_grid), dim3(kWave), 0, L.irr, L.c, L.d_blob, L.blob_bytes,
+                       L.d_offsets, L.sz(), (const uint32_t*)dec->perm.p, (const Plan*)L.plan(), L.d_out, (uint64_t)L.out_stride, L.d_frames,
+                       L.d_status, (int32_t*)dec->scratch_u.p, (int32_t*)dec->scratch_g.p, L.ppw, (alac::ChanDesc*)dec->cd.p,
+                       (alac::PktDesc*)dec->pd.p, dec->cfg.num_channels > 2 ? (int32_t*)dec->rows.p : (int32_t*)nullptr,
+                       (uint64_t)row_stride_of(dec->cfg.frame_length));
+}
+
+/* one of the up to three launches for the narrow regular wave slots (regular_packets) */
+void narrow_launch(const Launch& L, const PairArgs& a, uint32_t slots, uint32_t mode) {
+    alacgpu_decoder* dec = L.dec;
+    const Kernels& k = dec->kernels;
+    if (mode == kModeGated) {
+        /* as many workgroups as the device holds at once: they share the slots out among themselves */
+        if (a.cap) hipLaunchKernelGGL(k.gated.fn, dim3(std::min<uint32_t>(a.cap * dec->n_cu, slots)), dim3(2 * kWave), 0, dec->stream, a);
+        return;
+    }
+    if (mode == kModeFit5 && !a.fit5) return;
+    const uint32_t stat = kernel_attr(k.quad.fn).static_lds;
+    PairArgs q = a;
+    q.fit = mode;
+    hipLaunchKernelGGL(k.quad.fn, dim3(slots), dim3(4 * kWave), (mode == kModeFit4 && stat < kQuadLdsFit4) ? kQuadLdsFit4 - stat : 0u,
+                       dec->stream, q);
+}
+
+/* the regular packets of one or two channels, on the handle's stream */
+void regular_packets(const Launch& L) {
+    alacgpu_decoder* dec = L.dec;
+    const Kernels& k = dec->kernels;
+    const size_t n = L.n;
+    const uint32_t ppw = L.ppw;
+    /* one kernel per class of regular packets (alac_gpu.h, k_decode_body.inc): each one is launched over all the wave
+     * slots and leaves the slots of the other classes alone. gated_cap: how many pairs per CU the gated twin of the
+     * kernel can hold (0: it has none); which of the twins works is decided on the device. */
+    PairArgs a{L.c, L.d_blob, (uint64_t)L.blob_bytes, L.d_offsets, L.sz(), (const uint32_t*)dec->perm.p, L.plan(), L.d_out, (uint64_t)L.out_stride,
+               L.d_frames, L.d_status, (int32_t*)dec->scratch_u.p, (const uint32_t*)dec->cu_number.p,
+               (uint32_t*)((uint8_t*)L.plan() + plan_claims_offset()), ppw, dec->n_cu, 0u, dec->lanes_min, 4u, dec->fit_force, 0u};
+    const uint32_t slots = (uint32_t)L.waves;
+    /* The narrow regular wave slots go to ONE of up to three launches, and which one is decided on the device from the
+     * plan's count of them (alac_gpu.h: decode_mode; the host only knows an upper bound of ALL slots): the four-wave
+     * kernel padded with dynamic LDS to 34 KB per workgroup ("fit 4": four per CU), the same kernel without the pad
+     * ("fit 5"), and for 16-bit streams the gated twin of wave pairs. "Fit 4" is always launched; the other two for
+     * batches of more than 4 x CUs x 64 packets (`beyond4`), and the device is TOLD whether they are (PairArgs::fit5, cap):
+     * it never picks a launch that was not made. (Round 3, found by tools/gpu_fuzz.py: a host-side guess once skipped a
+     * launch the device then relied on.) A smaller batch whose many keys push it over 4 x CUs slots all the same runs
+     * rounds of four, as in round 3; in exchange the benchmark batch and everything below it see no empty grids at all.
+     * The launches that are not the batch's exit at once — but empty grids right IN FRONT of a wave-pair kernel cost it
+     * up to 13 % (16-bit 98 304 packets 3.15 -> 3.66 ms with the empty "fit 4" and "fit 5" grids in front of the gated
+     * twin, 24-bit stereo without shift bytes 5.2 -> 8.4 ms with both in front of alac_decode_w24; one alone, or any
+     * number behind: nothing; the four-wave launches do not care; profiles/r04_final/launch_order*.txt), so the launch
+     * the host expects to work — decode_mode() of the batch as if every packet were a narrow regular one — goes first,
+     * the wide keys' pairs second, the rest behind. A wrong guess costs speed, never correctness. */
+    const uint32_t n_cu = dec->n_cu;
+    const bool beyond4 = (n + ppw - 1) / ppw > (size_t)4 * n_cu || dec->fit_force == kModeFit5;
+    const bool has_twin = k.gated.fn && beyond4 && dec->fit_force == 0u;
+    {
+        const uint32_t stat = kernel_attr(k.quad.fn).static_lds;
+        a.fit5 = (beyond4 && (size_t)((stat + 1279u) / 1280u) * 1280u * 5u <= 163840u) ? 1u : 0u; /* 1280-byte granules of 160 KB */
+    }
+    if (has_twin) a.cap = kernel_attr(k.gated.fn).pairs_per_cu;
+    if (a.cap <= 4u) a.cap = 0u;
+    dec->last_cap = a.cap;
+    dec->last_fit5 = a.fit5;
+    const uint32_t guess = decode_mode((uint32_t)((n + ppw - 1) / ppw), n_cu, a.cap, dec->fit_force, dec->cfg.num_channels == 1, a.fit5 != 0u);
+    narrow_launch(L, a, slots, guess);
+    if (k.wide.fn) hipLaunchKernelGGL(k.wide.fn, dim3(slots), dim3(2 * kWave), 0, dec->stream, a);
+    for (uint32_t mode : {kModeFit4, kModeFit5, kModeGated})
+        if (mode != guess) narrow_launch(L, a, slots, mode);
+}
+
+/* more than two channels, behind the scan */
+int split_pipeline(const Launch& L) {
+    alacgpu_decoder* dec = L.dec;
+    /* split pipeline: one lane per channel, sorted by predictor order */
+    Plan* plan2 = (Plan*)dec->plan2.p;
+    const size_t n_slots = L.n * 8;
+    const uint32_t nb2 = (uint32_t)((n_slots + 255) / 256);
+    const uint32_t ppw2 = pick_ppw(L.n * dec->cfg.num_channels);
+    HIP_TRY(hipMemsetAsync(plan2, 0, sizeof(Plan), dec->stream));
+    hipLaunchKernelGGL(alac_task_classify, dim3(nb2), dim3(256), 0, dec->stream, L.c, (const alac::ChanDesc*)dec->cd.p,
+                       (const alac::PktDesc*)dec->pd.p, (const uint16_t*)dec->cls.p, (uint32_t)n_slots,
+                       (uint16_t*)dec->keys2.p, plan2);
+    hipLaunchKernelGGL(alac_plan, dim3(1), dim3(kWave), 0, dec->stream, plan2, ppw2);
+    hipLaunchKernelGGL(alac_scatter, dim3(nb2), dim3(256), 0, dec->stream, (const uint16_t*)dec->keys2.p,
+                       (uint32_t)n_slots, plan2, (uint32_t*)dec->perm2.p);
+    hipLaunchKernelGGL(alac_chan_predict, dim3((uint32_t)max_waves(16u, n_slots, ppw2)), dim3(kWave), 0, dec->stream, L.c,
+                       L.d_blob, L.blob_bytes, L.d_offsets, L.sz(), (const uint32_t*)dec->perm2.p, (const Plan*)plan2,
+                       (const alac::ChanDesc*)dec->cd.p, (int32_t*)dec->rows.p, (uint64_t)row_stride_of(dec->cfg.frame_length), ppw2);
+    return ALACGPU_E_OK;
+}
+
+/* the irregular packets' PCM: alac_interleave for the scanned ones, alac_legacy (the whole-packet decoder) for the rest */
+void irregular_pcm(const Launch& L) {
+    alacgpu_decoder* dec = L.dec;
+    const Kernels& k = dec->kernels;
+    const uint64_t rs = row_stride_of(dec->cfg.frame_length);
+    /* slices of a packet (k_split.hip), one wavefront's worth of frames each: one-wave blocks keep more blocks in flight
+     * per CU (the kernel waits on memory, not on arithmetic) */
+    const uint32_t bpp = (dec->cfg.frame_length + kWave - 1u) / kWave;
+    /* PCM of the split packets (with one or two channels: of the escape-only packets) */
+    /* a block takes eight slices of a packet at a time (k_split.hip: kSlices) */
+    /* (beside the regular packets' kernels: a few blocks per CU — it walks the scanned packets, a handful there) */
+    const uint32_t ib = (uint32_t)std::min<uint64_t>((uint64_t)L.n * ((bpp + 7u) / 8u), L.forked ? (uint64_t)4 * dec->n_cu : (uint64_t)32768u);
+    hipLaunchKernelGGL(k.interleave, dim3(ib), dim3(kWave), k.interleave_lds, L.irr, L.c, L.d_blob, L.blob_bytes, L.d_offsets, L.sz(),
+                       (const uint32_t*)dec->perm.p, (const Plan*)L.plan(), (const alac::ChanDesc*)dec->cd.p,
+                       (const alac::PktDesc*)dec->pd.p, (const int32_t*)dec->rows.p, rs, L.d_out, (uint64_t)L.out_stride, bpp);
+    hipLaunchKernelGGL(alac_legacy, dim3(L.scan_grid), dim3(kWave), 0, L.irr, L.c, L.d_blob, L.blob_bytes,
+                       L.d_offsets, L.sz(), (const uint32_t*)dec->perm.p, (const Plan*)L.plan(), (const alac::PktDesc*)dec->pd.p, L.d_out,
+                       (uint64_t)L.out_stride, L.d_frames, L.d_status, (int32_t*)dec->scratch_u.p, (int32_t*)dec->scratch_g.p, L.ppw);
+}
+
 /* All kernels of one decode, on the handle's stream. d_sizes may be null (packet i = blob[offsets[i], offsets[i+1])).
  * The event pair brackets everything the decode launches, the sort pre-pass included. */
 int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offsets,
@@ -360,19 +511,13 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
     dec->last_n = n;
     dec->last_ppw = ppw;
     dec->last_cap = dec->last_fit5 = 0;
-    alac::DevCfg c = dec->dev_cfg;
-    c.aligned16 = (out_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_out) % 16) == 0) ? 1u : 0u;
-    Plan* plan = (Plan*)dec->plan.p;
-    const uint32_t* sz = (const uint32_t*)dec->sizes_ws.p; /* the checked sizes (alac_classify) */
-    const uint32_t nb = (uint32_t)((n + 255) / 256);
+    const Kernels& k = dec->kernels;
+    Launch L{dec, dec->dev_cfg, d_blob, blob_bytes, d_offsets, n, d_out, out_stride, d_frames, d_status, ppw, max_waves(dec, n, ppw),
+             dec->stream, false, 0u};
+    L.c.aligned16 = (out_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_out) % 16) == 0) ? 1u : 0u;
     const uint32_t slot = (uint32_t)(dec->launches % kTimingSlots);
     HIP_TRY(hipEventRecord(dec->ev_start[slot], dec->stream));
-    HIP_TRY(hipMemsetAsync(plan, 0, plan_bytes(max_waves(dec, n, ppw)), dec->stream));
-    hipLaunchKernelGGL(alac_classify, dim3(nb), dim3(256), 0, dec->stream, c, d_blob, blob_bytes, d_offsets, d_sizes,
-                       (uint32_t)n, (uint16_t*)dec->cls.p, (uint32_t*)dec->sizes_ws.p, d_frames, d_status, plan);
-    hipLaunchKernelGGL(alac_plan, dim3(1), dim3(kWave), 0, dec->stream, plan, ppw);
-    hipLaunchKernelGGL(alac_scatter, dim3(nb), dim3(256), 0, dec->stream, (const uint16_t*)dec->cls.p, (uint32_t)n, plan,
-                       (uint32_t*)dec->perm.p);
+    if ((rc = sort_pass(L, d_sizes))) return rc;
     /* Packets of one or two channels: what the irregular ones need (alac_scan, then alac_interleave and alac_legacy: a
      * handful of waves, or none) depends on the sort alone and touches no wave slot, packet or descriptor of a regular
      * one, so it runs on a stream of its own BESIDE the workgroups of the regular packets instead of before and behind them
@@ -386,153 +531,36 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
      * the interleave grid), and every batch size forks (profiles/r04_final/side_stream.txt: 131 072 packets 3.85 / 3.77 ms in
      * line, 4.00 / 3.76 beside; 196 608: 5.62 -> 5.57; 24-bit 131 072: 4.68 -> 4.65). ALACGPU_SIDE=0: everything in line;
      * 1: round 3's limit of 6 x CUs wave slots. */
-    const bool forked = dec->cfg.num_channels <= 2 && alac::lean_config(c) &&
-                        (dec->side >= 2 || (dec->side == 1 && (n + ppw - 1) / ppw <= (size_t)6 * dec->n_cu));
+    L.forked = k.one_or_two && k.lean &&
+               (dec->side >= 2 || (dec->side == 1 && (n + ppw - 1) / ppw <= (size_t)6 * dec->n_cu));
     /* workgroups of alac_scan / alac_legacy: they walk the irregular wave slots (the first plan->irr_waves of the plan,
      * a number only the device knows). Beside the regular packets' kernels: two per CU, a handful of irregular slots is the
      * rule there; where the scan IS the decode (more than two channels, or a configuration the lean kernels do not take):
      * as many as the device holds (201 registers: two waves per SIMD; 26 KB of LDS: six workgroups per CU). */
-    const uint32_t scan_grid = (uint32_t)std::min<size_t>(max_waves(dec, n, ppw), (size_t)(forked ? 2u : 6u) * dec->n_cu);
-    hipStream_t irr = forked ? dec->s_side : dec->stream;
-    if (forked) {
-        HIP_TRY(hipEventRecord(dec->ev_fork, dec->stream));
-        HIP_TRY(hipStreamWaitEvent(dec->s_side, dec->ev_fork, 0));
-    }
+    L.scan_grid = (uint32_t)std::min<size_t>(L.waves, (size_t)(L.forked ? 2u : 6u) * dec->n_cu);
     /* from here on an error must not leave s_side running behind the caller's back */
-    auto rest = [&]() -> int {
-    auto scan = [&]() {
-        hipLaunchKernelGGL(alac_scan, dim3(scan_grid), dim3(kWave), 0, irr, c, d_blob, blob_bytes,
-                           d_offsets, sz, (const uint32_t*)dec->perm.p, (const Plan*)plan, d_out, (uint64_t)out_stride, d_frames,
-                           d_status, (int32_t*)dec->scratch_u.p, (int32_t*)dec->scratch_g.p, ppw, (alac::ChanDesc*)dec->cd.p,
-                           (alac::PktDesc*)dec->pd.p, dec->cfg.num_channels > 2 ? (int32_t*)dec->rows.p : (int32_t*)nullptr,
-                           (uint64_t)row_stride_of(dec->cfg.frame_length));
-    };
+    SideFork side{dec};
+    if (L.forked) {
+        if ((rc = side.fork())) return rc;
+        L.irr = dec->s_side;
+    }
     /* in line: irregular packets first. Beside: the regular packets' workgroups go first and fill the device (a scan
      * wave needs 201 registers and 26 KB of LDS: it finds room where the first of them have finished, long before the
      * slowest has) */
-    if (!forked) scan();
-    if (dec->cfg.num_channels <= 2 && alac::lean_config(c)) {
-        /* one kernel per class of regular packets (alac_gpu.h, k_decode_body.inc): each one is launched over all the wave
-         * slots and leaves the slots of the other classes alone. gated_cap: how many pairs per CU the gated twin of the
-         * kernel can hold (0: it has none); which of the twins works is decided on the device. */
-        PairArgs a{c, d_blob, (uint64_t)blob_bytes, d_offsets, sz, (const uint32_t*)dec->perm.p, plan, d_out, (uint64_t)out_stride,
-                   d_frames, d_status, (int32_t*)dec->scratch_u.p, (const uint32_t*)dec->cu_number.p,
-                   (uint32_t*)((uint8_t*)plan + plan_claims_offset()), ppw, dec->n_cu, 0u, dec->lanes_min, 4u, dec->fit_force, 0u};
-        const uint32_t slots = (uint32_t)max_waves(dec, n, ppw);
-        auto pairs = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(slots), dim3(2 * kWave), 0, dec->stream, a); };
-        /* The narrow regular wave slots go to ONE of up to three launches, and which one is decided on the device from the
-         * plan's count of them (alac_gpu.h: decode_mode; the host only knows an upper bound of ALL slots): the four-wave
-         * kernel padded with dynamic LDS to 34 KB per workgroup ("fit 4": four per CU), the same kernel without the pad
-         * ("fit 5"), and for 16-bit streams the gated twin of wave pairs. "Fit 4" is always launched; the other two for
-         * batches of more than 4 x CUs x 64 packets (`beyond4`), and the device is TOLD whether they are (PairArgs::fit5, cap):
-         * it never picks a launch that was not made. (Round 3, found by tools/gpu_fuzz.py: a host-side guess once skipped a
-         * launch the device then relied on.) A smaller batch whose many keys push it over 4 x CUs slots all the same runs
-         * rounds of four, as in round 3; in exchange the benchmark batch and everything below it see no empty grids at all.
-         * The launches that are not the batch's exit at once — but empty grids right IN FRONT of a wave-pair kernel cost it
-         * up to 13 % (16-bit 98 304 packets 3.15 -> 3.66 ms with the empty "fit 4" and "fit 5" grids in front of the gated
-         * twin, 24-bit stereo without shift bytes 5.2 -> 8.4 ms with both in front of alac_decode_w24; one alone, or any
-         * number behind: nothing; the four-wave launches do not care; profiles/r04_final/launch_order*.txt), so the launch
-         * the host expects to work — decode_mode() of the batch as if every packet were a narrow regular one — goes first,
-         * the wide keys' pairs second, the rest behind. A wrong guess costs speed, never correctness. */
-        const uint32_t n_cu = dec->n_cu;
-        const bool beyond4 = (n + ppw - 1) / ppw > (size_t)4 * n_cu || dec->fit_force == kModeFit5;
-        const bool has_twin = dec->cfg.bit_depth == 16 && beyond4 && dec->fit_force == 0u;
-        auto quad_kernel = [&]() -> void (*)(PairArgs) {
-            return dec->cfg.bit_depth == 16 ? alac_decode_16q : dec->cfg.bit_depth == 32 ? alac_decode_32q : alac_decode_24q; /* 24: 20 and 24 */
-        };
-        {
-            const uint32_t stat = quad_static_lds(quad_kernel());
-            a.fit5 = (beyond4 && (size_t)((stat + 1279u) / 1280u) * 1280u * 5u <= 163840u) ? 1u : 0u; /* 1280-byte granules of 160 KB */
-        }
-        if (has_twin) a.cap = pair_capacity(alac_decode_16g);
-        if (a.cap <= 4u) a.cap = 0u;
-        dec->last_cap = a.cap;
-        dec->last_fit5 = a.fit5;
-        auto narrow = [&](uint32_t mode) {
-            if (mode == kModeGated) {
-                /* as many workgroups as the device holds at once: they share the slots out among themselves */
-                if (a.cap) hipLaunchKernelGGL(alac_decode_16g, dim3(std::min<uint32_t>(a.cap * n_cu, slots)), dim3(2 * kWave), 0, dec->stream, a);
-                return;
-            }
-            if (mode == kModeFit5 && !a.fit5) return;
-            const uint32_t stat = quad_static_lds(quad_kernel());
-            PairArgs q = a;
-            q.fit = mode;
-            hipLaunchKernelGGL(quad_kernel(), dim3(slots), dim3(4 * kWave), (mode == kModeFit4 && stat < kQuadLdsFit4) ? kQuadLdsFit4 - stat : 0u,
-                               dec->stream, q);
-        };
-        const uint32_t guess = decode_mode((uint32_t)((n + ppw - 1) / ppw), n_cu, a.cap, dec->fit_force, dec->cfg.num_channels == 1, a.fit5 != 0u);
-        narrow(guess);
-        /* the wide keys (chanBits > 23: 24- and 32-bit streams without their usual shift bytes): wave pairs */
-        if (dec->cfg.bit_depth == 32) pairs(alac_decode_w32);
-        else if (dec->cfg.bit_depth == 24) pairs(alac_decode_w24);
-        for (uint32_t mode : {kModeFit4, kModeFit5, kModeGated})
-            if (mode != guess) narrow(mode);
-    }
-    if (forked) scan();
+    if (!L.forked) scan(L);
+    if (k.one_or_two && k.lean) regular_packets(L);
+    if (L.forked) scan(L);
     HIP_TRY(hipGetLastError());
-    if (alac::lean_config(c)) {
+    if (k.lean) {
         /* irregular packets were only scanned by alac_scan (status, frames, channel descriptors) */
-        const uint64_t rs = row_stride_of(dec->cfg.frame_length);
-        /* slices of a packet (k_split.hip), one wavefront's worth of frames each: one-wave blocks keep more blocks in flight
-         * per CU (the kernel waits on memory, not on arithmetic) */
-        const uint32_t bpp = (dec->cfg.frame_length + kWave - 1u) / kWave;
-        if (dec->cfg.num_channels > 2) {
-            /* split pipeline: one lane per channel, sorted by predictor order */
-            Plan* plan2 = (Plan*)dec->plan2.p;
-            const size_t n_slots = n * 8;
-            const uint32_t nb2 = (uint32_t)((n_slots + 255) / 256);
-            const uint32_t ppw2 = pick_ppw(n * dec->cfg.num_channels);
-            HIP_TRY(hipMemsetAsync(plan2, 0, sizeof(Plan), dec->stream));
-            hipLaunchKernelGGL(alac_task_classify, dim3(nb2), dim3(256), 0, dec->stream, c, (const alac::ChanDesc*)dec->cd.p,
-                               (const alac::PktDesc*)dec->pd.p, (const uint16_t*)dec->cls.p, (uint32_t)n_slots,
-                               (uint16_t*)dec->keys2.p, plan2);
-            hipLaunchKernelGGL(alac_plan, dim3(1), dim3(kWave), 0, dec->stream, plan2, ppw2);
-            hipLaunchKernelGGL(alac_scatter, dim3(nb2), dim3(256), 0, dec->stream, (const uint16_t*)dec->keys2.p,
-                               (uint32_t)n_slots, plan2, (uint32_t*)dec->perm2.p);
-            hipLaunchKernelGGL(alac_chan_predict, dim3((uint32_t)max_waves(16u, n_slots, ppw2)), dim3(kWave), 0, dec->stream, c,
-                               d_blob, blob_bytes, d_offsets, sz, (const uint32_t*)dec->perm2.p, (const Plan*)plan2,
-                               (const alac::ChanDesc*)dec->cd.p, (int32_t*)dec->rows.p, rs, ppw2);
-        }
-        /* PCM of the split packets (with one or two channels: of the escape-only packets) */
-        /* a block takes eight slices of a packet at a time (k_split.hip: kSlices) */
-        /* (beside the regular packets' kernels: a few blocks per CU — it walks the scanned packets, a handful there) */
-        const uint32_t ib = (uint32_t)std::min<uint64_t>((uint64_t)n * ((bpp + 7u) / 8u), forked ? (uint64_t)4 * dec->n_cu : (uint64_t)32768u);
-        /* four frames per lane (k_split.hip: alac_interleave4) where the rows exist (more than two channels) and a frame is a whole
-         * number of dwords (the layouts with a register-packed form: the others build their frames byte by byte and only lose
-         * occupancy to the bigger kernel: 16-bit 3-channel 3.25 -> 3.53 ms) */
-        const bool four_frames = dec->cfg.num_channels > 2 && (dec->cfg.num_channels * c.bps) % 4u == 0u;
-        hipLaunchKernelGGL(four_frames ? alac_interleave4 : alac_interleave, dim3(ib), dim3(kWave), (four_frames ? 128u : 32u) * kWave, irr, c, d_blob, blob_bytes, d_offsets, sz,
-                           (const uint32_t*)dec->perm.p, (const Plan*)plan, (const alac::ChanDesc*)dec->cd.p,
-                           (const alac::PktDesc*)dec->pd.p, (const int32_t*)dec->rows.p, rs, d_out, (uint64_t)out_stride, bpp);
-        hipLaunchKernelGGL(alac_legacy, dim3(scan_grid), dim3(kWave), 0, irr, c, d_blob, blob_bytes,
-                           d_offsets, sz, (const uint32_t*)dec->perm.p, (const Plan*)plan, (const alac::PktDesc*)dec->pd.p, d_out,
-                           (uint64_t)out_stride, d_frames, d_status, (int32_t*)dec->scratch_u.p, (int32_t*)dec->scratch_g.p, ppw);
+        if (!k.one_or_two && (rc = split_pipeline(L))) return rc;
+        irregular_pcm(L);
         HIP_TRY(hipGetLastError());
     }
-    if (forked) {
-        HIP_TRY(hipEventRecord(dec->ev_join, dec->s_side));
-        HIP_TRY(hipStreamWaitEvent(dec->stream, dec->ev_join, 0));
-    }
-    return ALACGPU_E_OK;
-    };
-    rc = rest();
-    if (rc != ALACGPU_E_OK) {
-        if (forked) (void)hipStreamSynchronize(dec->s_side);
-        return rc;
-    }
+    if (L.forked && (rc = side.join())) return rc;
     HIP_TRY(hipEventRecord(dec->ev_stop[slot], dec->stream));
     dec->launches++;
     return ALACGPU_E_OK;
-}
-
-bool is_pinned(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError(); /* an ordinary (pageable) pointer: not an error */
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
 }
 
 } /* namespace */
@@ -573,47 +601,63 @@ void keep_at_most(std::vector<Buf*> bufs, size_t limit) {
     }
 }
 
+/* A handle's belongings, each kind listed ONCE: alacgpu_create makes the streams and events from these lists, alacgpu_destroy
+ * trims the buffers of a handle on its way to the pool by them, really_destroy lets go of everything by them. (cu_number is
+ * outside the trimming: only really_destroy releases it.) */
+std::vector<DevBuf*> device_buffers(alacgpu_decoder* d) {
+    std::vector<DevBuf*> v = {&d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->cd, &d->pd,
+                              &d->plan2, &d->keys2, &d->perm2, &d->rows, &d->wave_ws};
+    for (Slot& s : d->slots) v.insert(v.end(), {&s.d_in, &s.d_out});
+    return v;
+}
+std::vector<HostBuf*> pinned_buffers(alacgpu_decoder* d) {
+    std::vector<HostBuf*> v;
+    for (Slot& s : d->slots) v.insert(v.end(), {&s.h_in, &s.h_out});
+    return v;
+}
+std::vector<hipStream_t*> streams_of(alacgpu_decoder* d) { return {&d->stream, &d->s_in, &d->s_out, &d->s_side}; }
+struct EventRef {
+    hipEvent_t* ev;
+    unsigned flags;
+};
+std::vector<EventRef> events_of(alacgpu_decoder* d) {
+    std::vector<EventRef> v = {{&d->ev_fork, hipEventDisableTiming}, {&d->ev_join, hipEventDisableTiming},
+                               {&d->ev_w0, hipEventDefault}, {&d->ev_w1, hipEventDefault}};
+    for (uint32_t i = 0; i < kTimingSlots; i++) v.insert(v.end(), {{&d->ev_start[i], hipEventDefault}, {&d->ev_stop[i], hipEventDefault}});
+    for (Slot& s : d->slots)
+        v.insert(v.end(), {{&s.ev_in, hipEventDisableTiming}, {&s.ev_k, hipEventDisableTiming}, {&s.ev_out, hipEventDisableTiming}});
+    return v;
+}
+
+/* all four streams idle: nothing of this handle's last call is still running */
+bool synchronize_all(alacgpu_decoder* d) {
+    bool ok = true;
+    for (hipStream_t* s : streams_of(d))
+        if (*s && hipStreamSynchronize(*s) != hipSuccess) ok = false;
+    return ok;
+}
+
 void really_destroy(alacgpu_decoder* d) {
     (void)hipSetDevice(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    if (d->s_in) (void)hipStreamSynchronize(d->s_in);
-    if (d->s_out) (void)hipStreamSynchronize(d->s_out);
-    if (d->s_side) (void)hipStreamSynchronize(d->s_side);
+    (void)synchronize_all(d);
     delete d->pool;
-    DevBuf* bufs[] = {&d->cu_number, &d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->cd, &d->pd,
-                      &d->plan2, &d->keys2, &d->perm2, &d->rows, &d->wave_ws};
-    for (DevBuf* b : bufs) b->release();
-    for (int k = 0; k < kSlots; k++) {
-        Slot& s = d->slots[k];
-        s.d_in.release();
-        s.d_out.release();
-        s.h_in.release();
-        s.h_out.release();
-        if (s.ev_in) (void)hipEventDestroy(s.ev_in);
-        if (s.ev_k) (void)hipEventDestroy(s.ev_k);
-        if (s.ev_out) (void)hipEventDestroy(s.ev_out);
-    }
-    for (uint32_t i = 0; i < kTimingSlots; i++) {
-        if (d->ev_start[i]) (void)hipEventDestroy(d->ev_start[i]);
-        if (d->ev_stop[i]) (void)hipEventDestroy(d->ev_stop[i]);
-    }
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    if (d->s_in) (void)hipStreamDestroy(d->s_in);
-    if (d->s_out) (void)hipStreamDestroy(d->s_out);
-    if (d->s_side) (void)hipStreamDestroy(d->s_side);
-    if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
-    if (d->ev_join) (void)hipEventDestroy(d->ev_join);
-    if (d->ev_w0) (void)hipEventDestroy(d->ev_w0);
-    if (d->ev_w1) (void)hipEventDestroy(d->ev_w1);
+    d->cu_number.release();
+    for (DevBuf* b : device_buffers(d)) b->release();
+    for (HostBuf* b : pinned_buffers(d)) b->release();
+    for (const EventRef& e : events_of(d))
+        if (*e.ev) (void)hipEventDestroy(*e.ev);
+    for (hipStream_t* s : streams_of(d))
+        if (*s) (void)hipStreamDestroy(*s);
     delete d;
 }
 
 /* the per-configuration part of a handle (everything else survives in the pool) */
-void configure(alacgpu_decoder* d, const alacgpu_config* cfg, int bps) {
+void configure(alacgpu_decoder* d, const alacgpu_config* cfg) {
+    const uint32_t bps = alacwf::bytes_per_sample(cfg->bit_depth); /* BytesPerSample, internal/alac/format.go:23-34 */
     d->cfg = *cfg;
     d->frame_bytes = (size_t)cfg->frame_length * cfg->num_channels * (size_t)bps;
-    d->dev_cfg = alac::DevCfg{cfg->frame_length, cfg->bit_depth, cfg->num_channels, cfg->pb, cfg->mb, cfg->kb,
-                              (uint32_t)bps, 0u};
+    d->dev_cfg = alac::DevCfg{cfg->frame_length, cfg->bit_depth, cfg->num_channels, cfg->pb, cfg->mb, cfg->kb, bps, 0u};
+    d->kernels = choose_kernels(d->dev_cfg);
     d->launches = 0;
     d->ahead = nullptr;
     d->ahead_rc = ALACGPU_E_OK;
@@ -637,6 +681,20 @@ void configure(alacgpu_decoder* d, const alacgpu_config* cfg, int bps) {
 
 static int settle_ahead(alacgpu_decoder* d);
 
+/* what the two decode entries ask of their arguments alike */
+static int check_decode_args(const alacgpu_decoder* d, const void* blob, size_t blob_bytes, const void* offsets, size_t n, const void* out,
+                             size_t out_stride, const void* frames, const void* status) {
+    if (!d || (n && (!offsets || !out || !frames || !status)) || (blob_bytes && !blob)) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    if (out_stride < d->frame_bytes) {
+        set_err("out_stride %zu < frame bytes %zu", out_stride, d->frame_bytes);
+        return ALACGPU_E_ARG;
+    }
+    return ALACGPU_E_OK;
+}
+
 extern "C" {
 
 int alacgpu_create(const alacgpu_config* cfg, int device, alacgpu_decoder** out) {
@@ -645,19 +703,7 @@ int alacgpu_create(const alacgpu_config* cfg, int device, alacgpu_decoder** out)
         return ALACGPU_E_ARG;
     }
     *out = nullptr;
-    const int bps = bytes_per_sample(cfg->bit_depth);
-    if (bps == 0) { /* decoder.go:91-93 */
-        set_err("invalid configuration: alac: unsupported bit depth: %d", (int)cfg->bit_depth);
-        return ALACGPU_E_CONFIG;
-    }
-    if (cfg->num_channels < 1 || cfg->num_channels > 8) {
-        set_err("invalid configuration: NumChannels %d outside 1..8", (int)cfg->num_channels);
-        return ALACGPU_E_CONFIG;
-    }
-    if (cfg->frame_length == 0 || cfg->frame_length > (1u << 24)) {
-        set_err("invalid configuration: FrameLength %u", cfg->frame_length);
-        return ALACGPU_E_CONFIG;
-    }
+    if (int rc = check_config(cfg)) return rc;
     HIP_TRY(hipSetDevice(device));
     {
         std::lock_guard<std::mutex> g(g_pool_mu);
@@ -665,7 +711,7 @@ int alacgpu_create(const alacgpu_config* cfg, int device, alacgpu_decoder** out)
             if (g_pool[i]->device == device) {
                 alacgpu_decoder* d = g_pool[i];
                 g_pool.erase(g_pool.begin() + (long)i);
-                configure(d, cfg, bps);
+                configure(d, cfg);
                 *out = d;
                 return ALACGPU_E_OK;
             }
@@ -675,36 +721,20 @@ int alacgpu_create(const alacgpu_config* cfg, int device, alacgpu_decoder** out)
         set_err("out of memory");
         return ALACGPU_E_ARG;
     }
-    d->device = device;
-    d->pool = nullptr;
-    configure(d, cfg, bps);
+    d->device = device; /* (value-initialised: every stream, event and buffer of the new handle is null) */
+    configure(d, cfg);
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
         d->n_cu = cus > 0 ? (uint32_t)cus : 256u;
     }
-    d->stream = d->s_in = d->s_out = d->s_side = nullptr;
-    d->ev_fork = d->ev_join = d->ev_w0 = d->ev_w1 = nullptr;
-    for (uint32_t i = 0; i < kTimingSlots; i++) d->ev_start[i] = d->ev_stop[i] = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s_in, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s_out, hipStreamNonBlocking);
+    hipError_t e = hipSuccess;
     /* (the default priority: at the lowest one the side kernels linger until the decode's last workgroups have gone and
      * become its tail: 131 072 packets 3.85 -> 4.38 ms, 24-bit 4.68 -> 5.97; profiles/r04_final/side_stream.txt) */
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->s_side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreate(&d->ev_w0);
-    if (e == hipSuccess) e = hipEventCreate(&d->ev_w1);
-    for (uint32_t i = 0; i < kTimingSlots && e == hipSuccess; i++) {
-        e = hipEventCreate(&d->ev_start[i]);
-        if (e == hipSuccess) e = hipEventCreate(&d->ev_stop[i]);
-    }
-    for (int k = 0; k < kSlots && e == hipSuccess; k++) {
-        e = hipEventCreateWithFlags(&d->slots[k].ev_in, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d->slots[k].ev_k, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d->slots[k].ev_out, hipEventDisableTiming);
-    }
+    for (hipStream_t* st : streams_of(d))
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    for (const EventRef& ev : events_of(d))
+        if (e == hipSuccess) e = hipEventCreateWithFlags(ev.ev, ev.flags);
     if (e != hipSuccess) {
         set_err("stream/event creation failed: %s", hipGetErrorString(e));
         really_destroy(d);
@@ -723,22 +753,10 @@ void alacgpu_destroy(alacgpu_decoder* d) {
     (void)settle_ahead(d);
     (void)hipSetDevice(d->device);
     /* nothing of this handle's last call may still be running when its belongings go to the next owner */
-    bool ok = hipStreamSynchronize(d->stream) == hipSuccess && hipStreamSynchronize(d->s_in) == hipSuccess &&
-              hipStreamSynchronize(d->s_out) == hipSuccess && hipStreamSynchronize(d->s_side) == hipSuccess;
-    if (ok) {
+    if (synchronize_all(d)) {
         for (int k = 0; k < kSlots; k++) d->slots[k].busy = false;
-        std::vector<DevBuf*> dev = {&d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->cd, &d->pd,
-                                    &d->plan2, &d->keys2, &d->perm2, &d->rows, &d->wave_ws};
-        std::vector<decltype(&d->slots[0].h_in)> pinned;
-        for (int k = 0; k < kSlots; k++) {
-            Slot& s = d->slots[k];
-            dev.push_back(&s.d_in);
-            dev.push_back(&s.d_out);
-            pinned.push_back(&s.h_in);
-            pinned.push_back(&s.h_out);
-        }
-        keep_at_most(dev, kPoolKeepDevice);
-        keep_at_most(pinned, kPoolKeepPinned);
+        keep_at_most(device_buffers(d), kPoolKeepDevice);
+        keep_at_most(pinned_buffers(d), kPoolKeepPinned);
         std::lock_guard<std::mutex> g(g_pool_mu);
         size_t same = 0;
         for (alacgpu_decoder* p : g_pool) same += p->device == d->device ? 1u : 0u;
@@ -877,16 +895,10 @@ int alacgpu_decode_batch_wait(alacgpu_decoder* d) {
 int alacgpu_decode_batch_device(alacgpu_decoder* d, const uint8_t* d_blob, size_t blob_bytes, const uint64_t* d_offsets,
                                 const uint32_t* d_sizes, size_t n, uint8_t* d_out, size_t out_stride,
                                 uint32_t* d_frames, int32_t* d_status, int sync) {
-    if (!d || (n && (!d_offsets || !d_out || !d_frames || !d_status)) || (blob_bytes && !d_blob)) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
-    if (out_stride < d->frame_bytes) {
-        set_err("out_stride %zu < frame bytes %zu", out_stride, d->frame_bytes);
-        return ALACGPU_E_ARG;
-    }
+    int rc = check_decode_args(d, d_blob, blob_bytes, d_offsets, n, d_out, out_stride, d_frames, d_status);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(d->device));
-    int rc = launch(d, d_blob, (uint64_t)blob_bytes, d_offsets, d_sizes, n, d_out, out_stride, d_frames, d_status);
+    rc = launch(d, d_blob, (uint64_t)blob_bytes, d_offsets, d_sizes, n, d_out, out_stride, d_frames, d_status);
     if (rc) return rc;
     if (sync) HIP_TRY(hipStreamSynchronize(d->stream));
     return ALACGPU_E_OK;
@@ -903,14 +915,7 @@ int alacgpu_decode_batch_device(alacgpu_decoder* d, const uint8_t* d_blob, size_
  */
 int alacgpu_decode_batch(alacgpu_decoder* d, const uint8_t* blob, size_t blob_bytes, const uint64_t* offsets, size_t n,
                          uint8_t* out, size_t out_stride, uint32_t* frames_out, int32_t* status) {
-    if (!d || (n && (!offsets || !out || !frames_out || !status)) || (blob_bytes && !blob)) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
-    if (out_stride < d->frame_bytes) {
-        set_err("out_stride %zu < frame bytes %zu", out_stride, d->frame_bytes);
-        return ALACGPU_E_ARG;
-    }
+    if (int rc = check_decode_args(d, blob, blob_bytes, offsets, n, out, out_stride, frames_out, status)) return rc;
     if (n == 0) return ALACGPU_E_OK;
     auto valid = [&](size_t i) {
         const uint64_t lo = offsets[i], hi = offsets[i + 1];
@@ -948,8 +953,7 @@ int alacgpu_decode_batch(alacgpu_decoder* d, const uint8_t* blob, size_t blob_by
                     for (size_t i = lo; i < hi; i++) memcpy(out + (s.first + i) * out_stride, h + i * d_stride, fb);
                 }
             };
-            if (d->pool) d->pool->parallel_for(pieces, body);
-            else for (size_t k = 0; k < pieces; k++) body(k);
+            copy_pieces(d->pool, pieces, body);
         }
         if (s.bad)
             for (size_t i = s.first; i < s.first + s.n; i++)
@@ -1004,8 +1008,7 @@ int alacgpu_decode_batch(alacgpu_decoder* d, const uint8_t* blob, size_t blob_by
                 const size_t a = in_bytes * k / pieces, b = in_bytes * (k + 1) / pieces;
                 memcpy(hb + a, blob + lo + a, b - a);
             };
-            if (d->pool) d->pool->parallel_for(pieces, body);
-            else for (size_t k = 0; k < pieces; k++) body(k);
+            copy_pieces(d->pool, pieces, body);
             HIP_TRY(hipMemcpyAsync(d_in, s.h_in.p, meta_pad + in_bytes, hipMemcpyHostToDevice, d->s_in));
         }
         HIP_TRY(hipEventRecord(s.ev_in, d->s_in));
@@ -1157,27 +1160,21 @@ int alacgpu_last_dispatch(alacgpu_decoder* d, alacgpu_dispatch* out) {
     out->wide_slots = head.wide_waves;
     out->narrow_slots = head.total_waves - head.irr_waves - head.wide_waves;
     out->keys = head.nk;
-    const bool lean = d->cfg.num_channels <= 2 && alac::lean_config(d->dev_cfg);
+    const Kernels& k = d->kernels;
+    const bool lean = k.one_or_two && k.lean;
     /* the device's own decision (k_decode_body.inc reads the same plan and calls the same function) */
     const char* narrow = "";
     if (lean && out->narrow_slots) {
-        const char* q = d->cfg.bit_depth == 16 ? "alac_decode_16q" : d->cfg.bit_depth == 32 ? "alac_decode_32q" : "alac_decode_24q";
         const uint32_t mode = decode_mode(out->narrow_slots, d->n_cu, d->last_cap, d->fit_force, d->cfg.num_channels == 1, d->last_fit5 != 0u);
-        narrow = mode == kModeGated ? "alac_decode_16g" : q;
+        narrow = mode == kModeGated ? k.gated.name : k.quad.name;
         out->gated = mode == kModeGated ? 1u : 0u;
         out->workgroups_per_cu = mode == kModeGated ? pair_quota(out->narrow_slots, d->n_cu, d->last_cap) : mode;
         /* predictor waves on several lanes per packet (k_decode_body.inc: lanes_ok) */
         if (!out->gated && out->narrow_slots <= d->n_cu + d->n_cu / 8u && d->lanes_min <= 16u) out->lanes_per_packet = d->last_ppw <= 32u ? 4u : 2u;
     }
     snprintf(out->narrow_kernel, sizeof(out->narrow_kernel), "%s", narrow);
-    snprintf(out->wide_kernel, sizeof(out->wide_kernel), "%s",
-             (lean && out->wide_slots) ? (d->cfg.bit_depth == 32 ? "alac_decode_w32" : "alac_decode_w24") : "");
-    snprintf(out->irregular_kernels, sizeof(out->irregular_kernels), "%s",
-             !out->irregular_slots ? "" : !alac::lean_config(d->dev_cfg) ? "alac_scan (whole-packet decoder)"
-             : d->cfg.num_channels > 2 ? ((d->cfg.num_channels * d->dev_cfg.bps) % 4u == 0u
-                                              ? "alac_scan + alac_chan_predict + alac_interleave4 (+ alac_legacy)"
-                                              : "alac_scan + alac_chan_predict + alac_interleave (+ alac_legacy)")
-                                       : "alac_scan + alac_interleave (+ alac_legacy)");
+    snprintf(out->wide_kernel, sizeof(out->wide_kernel), "%s", (lean && out->wide_slots) ? k.wide.name : "");
+    snprintf(out->irregular_kernels, sizeof(out->irregular_kernels), "%s", out->irregular_slots ? k.irregular : "");
     return ALACGPU_E_OK;
 }
 
@@ -1275,8 +1272,3 @@ const char* alacgpu_last_error(void) { return g_err; }
 const char* alacgpu_version(void) { return "alacgpu 0.7.0 gfx950"; }
 
 } /* extern "C" */
-
-/* the encoder's entries (k_enc.hip) report through the same thread-local text as alacgpu_last_error */
-namespace alack {
-void set_last_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
-} /* namespace alack */

@@ -14,17 +14,13 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstring>
-#include <new>
 
 #include "alac_enc.h"
-
-namespace alack {
-void set_last_error(const char* msg); /* alacgpu.hip */
-}
+#include "alac_host.h"
 
 using namespace alacenc;
+using namespace alack;
 
 namespace {
 
@@ -135,94 +131,9 @@ __global__ void __launch_bounds__(256) alac_enc_pack(Params p, const Layout* __r
     }
 }
 
-/* ---- host side ------------------------------------------------------------------------------------------------------ */
-void set_err(const char* fmt, const char* a = "", const char* b = "") {
-    char buf[512];
-    snprintf(buf, sizeof(buf), fmt, a, b);
-    alack::set_last_error(buf);
-}
-
-#define ENC_TRY(expr)                                                        \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            set_err("%s failed: %s", #expr, hipGetErrorString(e_));          \
-            return ALACGPU_E_HIP;                                            \
-        }                                                                    \
-    } while (0)
-
-struct DevMem {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-struct PinnedMem {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-bool pinned(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError(); /* an ordinary pageable pointer */
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
-int check_config(const alacgpu_config* cfg) {
-    if (!bytes_per_sample(cfg->bit_depth)) {
-        char buf[96];
-        snprintf(buf, sizeof(buf), "invalid configuration: alac: unsupported bit depth: %d", (int)cfg->bit_depth);
-        alack::set_last_error(buf);
-        return ALACGPU_E_CONFIG;
-    }
-    if (cfg->num_channels < 1 || cfg->num_channels > 8) {
-        char buf[96];
-        snprintf(buf, sizeof(buf), "invalid configuration: NumChannels %d outside 1..8", (int)cfg->num_channels);
-        alack::set_last_error(buf);
-        return ALACGPU_E_CONFIG;
-    }
-    if (cfg->frame_length == 0 || cfg->frame_length > (1u << 24)) {
-        char buf[96];
-        snprintf(buf, sizeof(buf), "invalid configuration: FrameLength %u", cfg->frame_length);
-        alack::set_last_error(buf);
-        return ALACGPU_E_CONFIG;
-    }
-    return ALACGPU_E_OK;
-}
-
 } /* namespace */
 
+/* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
 struct alacgpu_encoder {
     alacgpu_config cfg;
     int device;
@@ -231,17 +142,17 @@ struct alacgpu_encoder {
     bool timed = false;
     uint64_t frames_done = 0;
     EncStats* stats = nullptr;
-    DevMem res, streams, lay, sums;    /* the kernels' scratch */
-    DevMem d_pcm, d_blob, d_off;       /* alacgpu_encode's device copies */
-    PinnedMem h_in, h_out, h_off;      /* alacgpu_encode's staging */
+    DevBuf res, streams, lay, sums;    /* the kernels' scratch */
+    DevBuf d_pcm, d_blob, d_off;       /* alacgpu_encode's device copies */
+    HostBuf h_in, h_out, h_off;        /* alacgpu_encode's staging */
 };
 
 namespace {
 void release(alacgpu_encoder* e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (DevMem* m : {&e->res, &e->streams, &e->lay, &e->sums, &e->d_pcm, &e->d_blob, &e->d_off}) m->release();
-    for (PinnedMem* m : {&e->h_in, &e->h_out, &e->h_off}) m->release();
+    for (DevBuf* m : {&e->res, &e->streams, &e->lay, &e->sums, &e->d_pcm, &e->d_blob, &e->d_off}) m->release();
+    for (HostBuf* m : {&e->h_in, &e->h_out, &e->h_off}) m->release();
     if (e->stats) (void)hipFree(e->stats);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
@@ -254,15 +165,15 @@ extern "C" {
 
 int alacgpu_encoder_create(const alacgpu_config* cfg, int device, alacgpu_encoder** out) {
     if (!cfg || !out) {
-        alack::set_last_error("null argument");
+        set_err("null argument");
         return ALACGPU_E_ARG;
     }
     *out = nullptr;
     if (int rc = check_config(cfg)) return rc;
-    ENC_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     alacgpu_encoder* e = new (std::nothrow) alacgpu_encoder();
     if (!e) {
-        alack::set_last_error("out of memory");
+        set_err("out of memory");
         return ALACGPU_E_ARG;
     }
     e->cfg = *cfg;
@@ -293,28 +204,28 @@ uint64_t alacgpu_encode_max_bytes(const alacgpu_encoder* e, uint64_t total_frame
 int alacgpu_encode_device(alacgpu_encoder* e, const uint8_t* d_pcm, uint64_t total_frames, uint8_t* d_blob, uint64_t blob_cap,
                           uint64_t* d_offsets, int sync) {
     if (!e || !d_offsets || (total_frames && (!d_pcm || !d_blob))) {
-        alack::set_last_error("null argument");
+        set_err("null argument");
         return ALACGPU_E_ARG;
     }
     if (blob_cap < max_bytes(e->cfg, total_frames)) {
-        alack::set_last_error("blob_cap below alacgpu_encode_max_bytes()");
+        set_err("blob_cap below alacgpu_encode_max_bytes()");
         return ALACGPU_E_ARG;
     }
     const Params p = make_params(e->cfg, total_frames);
     if (p.n_packets > kMaxPackets) {
-        alack::set_last_error("more than 2^31 - 1 packets in one encode");
+        set_err("more than 2^31 - 1 packets in one encode");
         return ALACGPU_E_ARG;
     }
-    ENC_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipSetDevice(e->device));
     const uint64_t n = p.n_packets, chains = n * p.nch;
     const uint64_t blocks = (n + kScanThreads - 1) / kScanThreads;
     if (n) {
-        ENC_TRY(e->res.ensure(chains * sizeof(ChainResult)));
-        ENC_TRY(e->streams.ensure(chains * p.chain_words * sizeof(uint32_t)));
-        ENC_TRY(e->lay.ensure(n * sizeof(Layout)));
-        ENC_TRY(e->sums.ensure(blocks * sizeof(uint64_t)));
+        if (int rc = e->res.ensure(chains * sizeof(ChainResult))) return rc;
+        if (int rc = e->streams.ensure(chains * p.chain_words * sizeof(uint32_t))) return rc;
+        if (int rc = e->lay.ensure(n * sizeof(Layout))) return rc;
+        if (int rc = e->sums.ensure(blocks * sizeof(uint64_t))) return rc;
     }
-    ENC_TRY(hipEventRecord(e->ev0, e->stream));
+    HIP_TRY(hipEventRecord(e->ev0, e->stream));
     if (n) {
         ChainResult* res = (ChainResult*)e->res.p;
         uint32_t* streams = (uint32_t*)e->streams.p;
@@ -334,63 +245,63 @@ int alacgpu_encode_device(alacgpu_encoder* e, const uint8_t* d_pcm, uint64_t tot
             hipLaunchKernelGGL(alac_enc_pack, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, e->stream, p, lay, streams, d_pcm,
                                d_offsets, d_blob, p0);
         }
-        ENC_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     } else {
-        ENC_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), e->stream));
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), e->stream));
     }
-    ENC_TRY(hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(hipEventRecord(e->ev1, e->stream));
     e->timed = true;
     e->frames_done += total_frames;
-    if (sync) ENC_TRY(hipStreamSynchronize(e->stream));
+    if (sync) HIP_TRY(hipStreamSynchronize(e->stream));
     return ALACGPU_E_OK;
 }
 
 int alacgpu_encode(alacgpu_encoder* e, const uint8_t* pcm, uint64_t total_frames, uint8_t* blob, uint64_t blob_cap,
                    uint64_t* offsets, uint64_t* blob_bytes_out) {
     if (!e || !offsets || (total_frames && (!pcm || !blob))) {
-        alack::set_last_error("null argument");
+        set_err("null argument");
         return ALACGPU_E_ARG;
     }
     const uint64_t need = max_bytes(e->cfg, total_frames);
     if (blob_cap < need) {
-        alack::set_last_error("blob_cap below alacgpu_encode_max_bytes()");
+        set_err("blob_cap below alacgpu_encode_max_bytes()");
         return ALACGPU_E_ARG;
     }
     const Params p = make_params(e->cfg, total_frames);
     if (p.n_packets > kMaxPackets) {
-        alack::set_last_error("more than 2^31 - 1 packets in one encode");
+        set_err("more than 2^31 - 1 packets in one encode");
         return ALACGPU_E_ARG;
     }
-    ENC_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipSetDevice(e->device));
     const uint64_t n = p.n_packets;
     const uint64_t pcm_bytes = total_frames * p.nch * p.bps;
-    ENC_TRY(e->d_pcm.ensure(pcm_bytes ? pcm_bytes : 1));
-    ENC_TRY(e->d_blob.ensure(need ? need : 1));
-    ENC_TRY(e->d_off.ensure((n + 1) * sizeof(uint64_t)));
-    ENC_TRY(e->h_off.ensure((n + 1) * sizeof(uint64_t)));
+    if (int rc = e->d_pcm.ensure(pcm_bytes ? pcm_bytes : 1)) return rc;
+    if (int rc = e->d_blob.ensure(need ? need : 1)) return rc;
+    if (int rc = e->d_off.ensure((n + 1) * sizeof(uint64_t))) return rc;
+    if (int rc = e->h_off.ensure((n + 1) * sizeof(uint64_t))) return rc;
     if (pcm_bytes) {
         const void* src = pcm;
-        if (!pinned(pcm)) {
-            ENC_TRY(e->h_in.ensure(pcm_bytes));
+        if (!is_pinned(pcm)) {
+            if (int rc = e->h_in.ensure(pcm_bytes)) return rc;
             memcpy(e->h_in.p, pcm, pcm_bytes);
             src = e->h_in.p;
         }
-        ENC_TRY(hipMemcpyAsync(e->d_pcm.p, src, pcm_bytes, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->d_pcm.p, src, pcm_bytes, hipMemcpyHostToDevice, e->stream));
     }
     if (int rc = alacgpu_encode_device(e, (const uint8_t*)e->d_pcm.p, total_frames, (uint8_t*)e->d_blob.p, e->d_blob.cap,
                                        (uint64_t*)e->d_off.p, 0))
         return rc;
-    ENC_TRY(hipMemcpyAsync(e->h_off.p, e->d_off.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-    ENC_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(e->h_off.p, e->d_off.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     const uint64_t total = ((const uint64_t*)e->h_off.p)[n];
     if (total) {
-        if (pinned(blob)) {
-            ENC_TRY(hipMemcpyAsync(blob, e->d_blob.p, total, hipMemcpyDeviceToHost, e->stream));
-            ENC_TRY(hipStreamSynchronize(e->stream));
+        if (is_pinned(blob)) {
+            HIP_TRY(hipMemcpyAsync(blob, e->d_blob.p, total, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
         } else {
-            ENC_TRY(e->h_out.ensure(total));
-            ENC_TRY(hipMemcpyAsync(e->h_out.p, e->d_blob.p, total, hipMemcpyDeviceToHost, e->stream));
-            ENC_TRY(hipStreamSynchronize(e->stream));
+            if (int rc = e->h_out.ensure(total)) return rc;
+            HIP_TRY(hipMemcpyAsync(e->h_out.p, e->d_blob.p, total, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
             memcpy(blob, e->h_out.p, total);
         }
     }
@@ -401,13 +312,13 @@ int alacgpu_encode(alacgpu_encoder* e, const uint8_t* pcm, uint64_t total_frames
 
 int alacgpu_encoder_cookie(alacgpu_encoder* e, uint8_t out[24]) {
     if (!e || !out) {
-        alack::set_last_error("null argument");
+        set_err("null argument");
         return ALACGPU_E_ARG;
     }
-    ENC_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipSetDevice(e->device));
     EncStats s;
-    ENC_TRY(hipStreamSynchronize(e->stream));
-    ENC_TRY(hipMemcpy(&s, e->stats, sizeof(s), hipMemcpyDeviceToHost));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(&s, e->stats, sizeof(s), hipMemcpyDeviceToHost));
     const uint64_t rate = e->frames_done ? (uint64_t)((double)s.total_bytes * 8.0 * e->cfg.sample_rate / (double)e->frames_done) : 0;
     cookie(e->cfg, s.max_packet, rate > 0xffffffffull ? 0xffffffffu : (uint32_t)rate, out);
     return ALACGPU_E_OK;
@@ -415,11 +326,11 @@ int alacgpu_encoder_cookie(alacgpu_encoder* e, uint8_t out[24]) {
 
 int alacgpu_encoder_last_kernel_ms(alacgpu_encoder* e, float* ms) {
     if (!e || !ms || !e->timed) {
-        alack::set_last_error(!e || !ms ? "null argument" : "no encode on this handle yet");
+        set_err(!e || !ms ? "null argument" : "no encode on this handle yet");
         return ALACGPU_E_ARG;
     }
-    ENC_TRY(hipEventSynchronize(e->ev1));
-    ENC_TRY(hipEventElapsedTime(ms, e->ev0, e->ev1));
+    HIP_TRY(hipEventSynchronize(e->ev1));
+    HIP_TRY(hipEventElapsedTime(ms, e->ev0, e->ev1));
     return ALACGPU_E_OK;
 }
 
@@ -427,11 +338,11 @@ void* alacgpu_encoder_stream(alacgpu_encoder* e) { return e ? (void*)e->stream :
 
 int alacgpu_encoder_synchronize(alacgpu_encoder* e) {
     if (!e) {
-        alack::set_last_error("null argument");
+        set_err("null argument");
         return ALACGPU_E_ARG;
     }
-    ENC_TRY(hipSetDevice(e->device));
-    ENC_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return ALACGPU_E_OK;
 }
 
