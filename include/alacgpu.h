@@ -324,6 +324,43 @@ uint64_t alacgpu_encode_max_bytes(const alacgpu_encoder* enc, uint64_t total_fra
 int alacgpu_encode_device(alacgpu_encoder* enc, const uint8_t* d_pcm, uint64_t total_frames, uint8_t* d_blob,
                           uint64_t blob_cap, uint64_t* d_offsets, int sync);
 
+/*
+ * WAVEFORMS IN: planar float32 / int32 tensors -> the encoder's interleaved PCM, one memory-bound pass of its own on the
+ * handle's stream (k_wavepack.hip; the inverse of alacgpu_waveform_device; the encode kernels and their outputs are
+ * untouched). d_wave is counted in 4-byte elements, layout and type are alacgpu_wave_layout / alacgpu_wave_type:
+ *   ALACGPU_WAVE_STREAM   [channels][channel_stride]: frame t of channel c is d_wave[c * channel_stride + t], t < total_frames
+ *   ALACGPU_WAVE_PACKETS  [n][channels] rows, n = ceil(total_frames / frame_length): frame t of clip i is
+ *                         d_wave[i * packet_stride + c * channel_stride + t]. Only the last clip may be short; its columns
+ *                         behind total_frames - (n - 1) * frame_length are not read.
+ * The pass writes total_frames contiguous interleaved frames (alacgpu_encode_device's input format) and nothing outside
+ * [d_pcm, d_pcm + total_frames * bytes per frame). Values, exact and deterministic, with q = the bit depth:
+ *   ALACGPU_WAVE_FLOAT    v = rint(x * 2^(q - 1)) in float32 (the product is exact, one rounding to nearest even), saturated to
+ *                         [-2^(q - 1), 2^(q - 1) - 1]; NaN gives 0. At depth 20 the three bytes hold v << 4, so what
+ *                         alacgpu_waveform_device made of a 20-bit stream comes back exactly.
+ *   ALACGPU_WAVE_INT      the int32 that alacgpu_waveform_device's INT gives (at depth 20 the 24-bit container value),
+ *                         saturated to the container's width 16 / 24 / 24 / 32; at depth 20 the low four bits are cleared.
+ * d_clipped (one uint64 on the device, may be NULL) receives the number of samples of this call that were saturated or
+ * were NaN (cleared low bits do not count); the entry clears it on the stream first. total_frames = 0 succeeds and writes
+ * *d_clipped = 0.
+ * alacgpu_encode_waveform_device is the pass into PCM scratch of the handle (total_frames x bytes per frame, grown on
+ * demand; a failed allocation is ALACGPU_E_HIP) followed by alacgpu_encode_device on the same stream, no host
+ * synchronisation in between: d_blob and d_offsets are byte for byte those of alacgpu_encode_device on that PCM.
+ * ALACGPU_E_ARG before any HIP call: a NULL handle, d_wave, d_pcm / d_blob or d_offsets; an unknown layout or type; d_wave
+ * not 4-byte aligned; STREAM with channel_stride < total_frames; PACKETS with channel_stride < frame_length or
+ * packet_stride < channels * channel_stride; blob_cap below alacgpu_encode_max_bytes(); more than 2^31 - 1 packets.
+ * Every alignment of d_wave, the strides and d_pcm gives the same bytes, 16 bytes wide in the body.
+ * Asynchronous on the handle's stream unless sync != 0, with the ordering contract of alacgpu_encode_device.
+ */
+int alacgpu_pcm_from_waveform_device(alacgpu_encoder* enc, const void* d_wave, int layout, int type, size_t channel_stride,
+                                     size_t packet_stride, uint64_t total_frames, uint8_t* d_pcm, uint64_t* d_clipped,
+                                     int sync);
+int alacgpu_encode_waveform_device(alacgpu_encoder* enc, const void* d_wave, int layout, int type, size_t channel_stride,
+                                   size_t packet_stride, uint64_t total_frames, uint8_t* d_blob, uint64_t blob_cap,
+                                   uint64_t* d_offsets, uint64_t* d_clipped, int sync);
+/* Duration of the last pack pass in milliseconds: HIP events around its kernels (valid after a sync).
+ * alacgpu_encoder_last_kernel_ms keeps timing the five encode kernels only. */
+int alacgpu_encoder_waveform_last_ms(alacgpu_encoder* enc, float* ms);
+
 /* Host buffers, blocking. pcm holds total_frames frames; blob_cap as above; offsets gets n + 1 entries; *blob_bytes_out
  * the bytes written (= offsets[n]). Buffers from alacgpu_host_alloc / hipHostMalloc / hipHostRegister are transferred in
  * place, pageable ones are staged through pinned buffers of the handle. */

@@ -31,7 +31,7 @@ _LIB = None
 
 __all__ = [
     "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "PacketEncoder", "NewPacketEncoder", "ParseMagicCookie",
-    "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load",
+    "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load", "save",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -241,6 +241,13 @@ _EXPORTS = {
     "alacgpu_encode_max_bytes": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
     "alacgpu_encode_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_pcm_from_waveform_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_encode_waveform_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_encoder_waveform_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     "alacgpu_encode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "alacgpu_encoder_cookie": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -633,6 +640,84 @@ class PacketEncoder:
         The handle's stream does not order against torch's: synchronize the inputs first."""
         _check(self._lib.alacgpu_encode_device(self._h, d_pcm, total_frames, d_blob, blob_cap, d_offsets, 1 if sync else 0))
 
+    def pcm_from_waveform_device(self, d_wave, layout, wtype, channel_stride, packet_stride, total_frames, d_pcm,
+                                 d_clipped=None, sync=True):
+        """alacgpu_pcm_from_waveform_device: raw device pointers (ints). A planar float32 (WAVE_FLOAT) or int32 (WAVE_INT)
+        waveform at d_wave, strides in elements — WAVE_STREAM [channels][channel_stride], WAVE_PACKETS [n][channels] rows of
+        FrameLength columns, the last clip possibly short — -> total_frames interleaved frames of the encoder's input
+        format at d_pcm. d_clipped (one uint64, or None) gets the count of saturated and NaN samples. Runs on the handle's
+        stream."""
+        _check(self._lib.alacgpu_pcm_from_waveform_device(self._h, d_wave, layout, wtype, channel_stride, packet_stride,
+                                                          total_frames, d_pcm, d_clipped, 1 if sync else 0))
+
+    def encode_waveform_device(self, d_wave, layout, wtype, channel_stride, packet_stride, total_frames, d_blob, blob_cap,
+                               d_offsets, d_clipped=None, sync=True):
+        """alacgpu_encode_waveform_device: pcm_from_waveform_device into the handle's scratch, then encode_device, on the
+        handle's stream with no host synchronisation in between."""
+        _check(self._lib.alacgpu_encode_waveform_device(self._h, d_wave, layout, wtype, channel_stride, packet_stride,
+                                                        total_frames, d_blob, blob_cap, d_offsets, d_clipped, 1 if sync else 0))
+
+    def waveform_last_ms(self):
+        """alacgpu_encoder_waveform_last_ms: HIP events around the kernels of the last pack pass."""
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_encoder_waveform_last_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def encode_waveform(self, wave, layout="stream", frames=None):
+        """Quantise, pack and encode on the device -> (blob, offsets, clipped).
+
+        wave: a torch tensor on any device or a numpy array, float32 (samples in [-1, 1), torchaudio's scale) or int32 (the
+        integers decode_waveform's int32 gives), [channels, T] for layout "stream" or [n, channels, FrameLength] for
+        "packets"; the time axis must be contiguous, the other strides are taken as they are. frames: the frames to encode,
+        default T or n * FrameLength. blob: uint8 CUDA tensor trimmed to offsets[n]; offsets: int64 CUDA tensor of n + 1
+        entries; clipped: how many samples were saturated or NaN."""
+        import torch
+        if layout not in ("stream", "packets"):
+            raise ValueError("layout must be 'stream' or 'packets'")
+        if isinstance(wave, np.ndarray):
+            if wave.dtype not in (np.float32, np.int32):
+                raise ValueError("wave must be float32 or int32")
+            if wave.ndim and wave.shape[-1] > 1 and wave.strides[-1] != wave.itemsize:
+                raise ValueError("the time axis of wave must be contiguous")
+            wave = torch.from_numpy(wave if wave.flags.writeable and all(s >= 0 for s in wave.strides) else wave.copy())
+        if not isinstance(wave, torch.Tensor):
+            raise ValueError("wave must be a torch tensor or a numpy array")
+        if wave.dtype not in (torch.float32, torch.int32):
+            raise ValueError("wave must be float32 or int32")
+        fl, ch = int(self.config.FrameLength), int(self.config.NumChannels)
+        if layout == "stream":
+            if wave.dim() != 2 or wave.shape[0] != ch:
+                raise ValueError("a 'stream' waveform is [%d, T]" % ch)
+            room = int(wave.shape[1])
+        else:
+            if wave.dim() != 3 or wave.shape[1] != ch or wave.shape[2] != fl:
+                raise ValueError("a 'packets' waveform is [n, %d, %d]" % (ch, fl))
+            room = int(wave.shape[0]) * fl
+        if wave.shape[-1] > 1 and wave.stride(-1) != 1:
+            raise ValueError("the time axis of wave must be contiguous")
+        frames = room if frames is None else int(frames)
+        if frames < 0 or frames > room:
+            raise ValueError("frames outside the waveform")
+        dev = torch.device("cuda", self.device)
+        wave = wave.to(dev)
+        if wave.numel() == 0 or (wave.shape[-1] > 1 and wave.stride(-1) != 1):
+            wave = wave.contiguous() if wave.numel() else torch.zeros(1, dtype=wave.dtype, device=dev)
+        if layout == "stream":
+            cs, ps = (int(wave.stride(0)) if ch > 1 and wave.numel() > 1 else max(room, 1)), 0
+        else:
+            cs = int(wave.stride(1)) if ch > 1 else fl
+            ps = int(wave.stride(0)) if wave.shape[0] > 1 else ch * cs
+        n = (frames + fl - 1) // fl
+        cap = self.max_bytes(frames)
+        blob = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        clipped = torch.zeros(1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+        self.encode_waveform_device(wave.data_ptr(), WAVE_STREAM if layout == "stream" else WAVE_PACKETS,
+                                    WAVE_FLOAT if wave.dtype is torch.float32 else WAVE_INT, cs, ps, frames, blob.data_ptr(), cap,
+                                    offsets.data_ptr(), clipped.data_ptr(), sync=True)
+        return blob[:int(offsets[n].item())], offsets, int(clipped.item())
+
     def cookie(self):
         """alacgpu_encoder_cookie: 24-byte ALACSpecificConfig (ParseMagicCookie reads it) with the largest packet and the
         average bit rate of what this encoder has written."""
@@ -694,6 +779,48 @@ def load(source, device=0, dtype=None):
     if n_ok < n:
         raise AlacError("reading sample %d: unexpected EOF" % n_ok)
     return wave[:, :total], int(cfg.SampleRate)
+
+
+def save(dest, wave, sample_rate, bits_per_sample=16, frame_length=4096, device=0, _window=None, **_container):
+    """A waveform [channels, frames] -> an ALAC M4A file, the call shape of torchaudio.save. dest: a path or a binary file
+    object. wave: a torch tensor on any device or a numpy array, float32 in [-1, 1) or int32 (the integers load(dtype=
+    torch.int32) gives). Returns how many samples were saturated or NaN. The waveform is quantised, packed and encoded on
+    cuda:`device` in packet-aligned windows of 48 MB of PCM on one encoder handle (packets are independent, so the file equals a
+    one-shot encode); the cookie is taken after the last window, so that its largest packet and bit rate cover the file."""
+    import torch
+    from . import mp4, stream
+    if isinstance(wave, np.ndarray):
+        if wave.ndim != 2:
+            raise ValueError("wave must be [channels, frames]")
+        ch, total = int(wave.shape[0]), int(wave.shape[1])
+    elif isinstance(wave, torch.Tensor):
+        if wave.dim() != 2:
+            raise ValueError("wave must be [channels, frames]")
+        ch, total = int(wave.shape[0]), int(wave.shape[1])
+    else:
+        raise ValueError("wave must be a torch tensor or a numpy array")
+    cfg = PacketConfig(FrameLength=frame_length, BitDepth=bits_per_sample, NumChannels=ch, SampleRate=sample_rate)
+    blobs, sizes, clipped = [], [], 0
+    with NewPacketEncoder(cfg, device) as enc:
+        window = _window or stream.window_packets(frame_length * enc.bytes_per_frame)
+        for f0 in range(0, total, window * frame_length):
+            f1 = min(f0 + window * frame_length, total)
+            blob, offs, c = enc.encode_waveform(wave[:, f0:f1], "stream")
+            blobs.append(blob.cpu().numpy())
+            sizes.append(np.diff(offs.cpu().numpy()))
+            clipped += c
+        cookie = enc.cookie()
+    offsets = np.zeros(1 + sum(len(s) for s in sizes), np.uint64)
+    if len(offsets) > 1:
+        offsets[1:] = np.cumsum(np.concatenate(sizes))
+    data = mp4.write_m4a(cookie, np.concatenate(blobs) if blobs else np.zeros(0, np.uint8), offsets, total, sample_rate, ch,
+                         bits_per_sample, **_container)
+    if hasattr(dest, "write"):
+        dest.write(data)
+    else:
+        with open(os.fspath(dest), "wb") as f:
+            f.write(data)
+    return clipped
 
 
 def FindALACTrack(data):

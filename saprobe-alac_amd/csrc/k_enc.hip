@@ -11,6 +11,9 @@
  *   alac_enc_pack     one wave per packet: every lane funnel-shifts the segments into one output dword at a time (byte
  *                     stores only at the packet's two unaligned ends, where the neighbours' bytes share the dword)
  * Everything is written with vector stores; the two counters of the cookie are global atomics.
+ *
+ * The waveform entries (alacgpu_pcm_from_waveform_device, alacgpu_encode_waveform_device) are host code here, beside the
+ * handle they extend; their kernel is k_wavepack.hip's (alac_wavepack.h).
  */
 #include <hip/hip_runtime.h>
 
@@ -18,6 +21,7 @@
 
 #include "alac_enc.h"
 #include "alac_host.h"
+#include "alac_wavepack.h"
 
 using namespace alacenc;
 using namespace alack;
@@ -145,17 +149,22 @@ struct alacgpu_encoder {
     DevBuf res, streams, lay, sums;    /* the kernels' scratch */
     DevBuf d_pcm, d_blob, d_off;       /* alacgpu_encode's device copies */
     HostBuf h_in, h_out, h_off;        /* alacgpu_encode's staging */
+    DevBuf wave_pcm;                   /* alacgpu_encode_waveform_device: the pack pass's PCM */
+    hipEvent_t ev_w0 = nullptr, ev_w1 = nullptr; /* around the kernels of the last pack pass */
+    bool wave_timed = false;
 };
 
 namespace {
 void release(alacgpu_encoder* e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (DevBuf* m : {&e->res, &e->streams, &e->lay, &e->sums, &e->d_pcm, &e->d_blob, &e->d_off}) m->release();
+    for (DevBuf* m : {&e->res, &e->streams, &e->lay, &e->sums, &e->d_pcm, &e->d_blob, &e->d_off, &e->wave_pcm}) m->release();
     for (HostBuf* m : {&e->h_in, &e->h_out, &e->h_off}) m->release();
     if (e->stats) (void)hipFree(e->stats);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
+    if (e->ev_w0) (void)hipEventDestroy(e->ev_w0);
+    if (e->ev_w1) (void)hipEventDestroy(e->ev_w1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -181,6 +190,8 @@ int alacgpu_encoder_create(const alacgpu_config* cfg, int device, alacgpu_encode
     hipError_t h = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (h == hipSuccess) h = hipEventCreate(&e->ev0);
     if (h == hipSuccess) h = hipEventCreate(&e->ev1);
+    if (h == hipSuccess) h = hipEventCreate(&e->ev_w0);
+    if (h == hipSuccess) h = hipEventCreate(&e->ev_w1);
     if (h == hipSuccess) h = hipMalloc((void**)&e->stats, sizeof(EncStats));
     if (h == hipSuccess) h = hipMemsetAsync(e->stats, 0, sizeof(EncStats), e->stream);
     if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
@@ -253,6 +264,95 @@ int alacgpu_encode_device(alacgpu_encoder* e, const uint8_t* d_pcm, uint64_t tot
     e->timed = true;
     e->frames_done += total_frames;
     if (sync) HIP_TRY(hipStreamSynchronize(e->stream));
+    return ALACGPU_E_OK;
+}
+
+/* ---- waveforms in (alac_wavepack.h, k_wavepack.hip) ------------------------------------------------------------------- */
+} /* extern "C" */
+
+namespace {
+/* what both waveform entries reject before any HIP call; -> the pass's parameters */
+int wave_args(const alacgpu_encoder* e, const void* d_wave, int layout, int type, size_t channel_stride, size_t packet_stride,
+              uint64_t total_frames, alacwp::Params* out) {
+    if ((layout != ALACGPU_WAVE_STREAM && layout != ALACGPU_WAVE_PACKETS) || (type != ALACGPU_WAVE_FLOAT && type != ALACGPU_WAVE_INT)) {
+        set_err("unknown waveform layout %d or type %d", layout, type);
+        return ALACGPU_E_ARG;
+    }
+    if ((uintptr_t)d_wave & 3u) {
+        set_err("d_wave is not 4-byte aligned");
+        return ALACGPU_E_ARG;
+    }
+    const uint32_t fl = e->cfg.frame_length, nch = e->cfg.num_channels;
+    if (layout == ALACGPU_WAVE_STREAM ? channel_stride < total_frames
+                                      : (channel_stride < fl || packet_stride / nch < channel_stride)) {
+        set_err("waveform strides below the tensor's extent");
+        return ALACGPU_E_ARG;
+    }
+    if (alacwp::packets_of(total_frames, fl) > kMaxPackets) {
+        set_err("more than 2^31 - 1 packets in one encode");
+        return ALACGPU_E_ARG;
+    }
+    *out = alacwp::make_params(fl, e->cfg.bit_depth, nch, (uint32_t)layout, (uint32_t)type, total_frames);
+    out->wave = (const uint8_t*)d_wave;
+    out->channel_stride = channel_stride;
+    out->packet_stride = packet_stride;
+    return ALACGPU_E_OK;
+}
+
+/* the pass on the handle's stream between its own events */
+int wave_pass(alacgpu_encoder* e, alacwp::Params p, uint8_t* d_pcm, uint64_t* d_clipped) {
+    p.pcm = d_pcm;
+    HIP_TRY(hipEventRecord(e->ev_w0, e->stream));
+    HIP_TRY(wavepack_launch(e->stream, p, d_clipped, alacwp::kTilesPerLaunch));
+    HIP_TRY(hipEventRecord(e->ev_w1, e->stream));
+    e->wave_timed = true;
+    return ALACGPU_E_OK;
+}
+} /* namespace */
+
+extern "C" {
+
+int alacgpu_pcm_from_waveform_device(alacgpu_encoder* e, const void* d_wave, int layout, int type, size_t channel_stride,
+                                     size_t packet_stride, uint64_t total_frames, uint8_t* d_pcm, uint64_t* d_clipped, int sync) {
+    if (!e || !d_wave || !d_pcm) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    alacwp::Params p;
+    if (int rc = wave_args(e, d_wave, layout, type, channel_stride, packet_stride, total_frames, &p)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = wave_pass(e, p, d_pcm, d_clipped)) return rc;
+    if (sync) HIP_TRY(hipStreamSynchronize(e->stream));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_encode_waveform_device(alacgpu_encoder* e, const void* d_wave, int layout, int type, size_t channel_stride,
+                                   size_t packet_stride, uint64_t total_frames, uint8_t* d_blob, uint64_t blob_cap,
+                                   uint64_t* d_offsets, uint64_t* d_clipped, int sync) {
+    if (!e || !d_wave || !d_blob || !d_offsets) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    alacwp::Params p;
+    if (int rc = wave_args(e, d_wave, layout, type, channel_stride, packet_stride, total_frames, &p)) return rc;
+    if (blob_cap < max_bytes(e->cfg, total_frames)) {
+        set_err("blob_cap below alacgpu_encode_max_bytes()");
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const uint64_t pcm_bytes = total_frames * p.bpf;
+    if (int rc = e->wave_pcm.ensure(pcm_bytes ? pcm_bytes : 1)) return rc;
+    if (int rc = wave_pass(e, p, (uint8_t*)e->wave_pcm.p, d_clipped)) return rc;
+    return alacgpu_encode_device(e, (const uint8_t*)e->wave_pcm.p, total_frames, d_blob, blob_cap, d_offsets, sync);
+}
+
+int alacgpu_encoder_waveform_last_ms(alacgpu_encoder* e, float* ms) {
+    if (!e || !ms || !e->wave_timed) {
+        set_err(!e || !ms ? "null argument" : "no waveform pass on this handle yet");
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipEventSynchronize(e->ev_w1));
+    HIP_TRY(hipEventElapsedTime(ms, e->ev_w0, e->ev_w1));
     return ALACGPU_E_OK;
 }
 

@@ -4,6 +4,7 @@
 //   NewPacketEncoder(config)              -> throws ErrConfig for the configs NewPacketDecoder rejects
 //   PacketEncoder::Encode(pcm, frames)    interleaved LE PCM (the decoder's output format) -> dense packets + offsets
 //   PacketEncoder::EncodeDevice(...)      device-resident, asynchronous on Stream()
+//   PacketEncoder::PcmFromWaveformDevice / EncodeWaveformDevice   planar float32 / int32 waveforms in, on the device
 //   PacketEncoder::Cookie()               24-byte ALACSpecificConfig for the encoded stream
 // Header-only; link with -lalacgpu. Every encode runs the HIP kernels: there is no CPU path.
 #pragma once
@@ -56,6 +57,32 @@ public:
                       bool sync = false) {
         if (alacgpu_encode_device(h_.get(), d_pcm, frames, d_blob, blob_cap, d_offsets, sync ? 1 : 0) != ALACGPU_E_OK)
             throw std::runtime_error(alacgpu_last_error());
+    }
+
+    // d_wave: a planar float32 (ALACGPU_WAVE_FLOAT) or int32 (ALACGPU_WAVE_INT) waveform on the device, strides in elements
+    // (ALACGPU_WAVE_STREAM [channels][channel_stride] / ALACGPU_WAVE_PACKETS [n][channels] rows) -> `frames` interleaved
+    // frames of the encoder's input format at d_pcm; d_clipped (one uint64, may be null): saturated and NaN samples
+    void PcmFromWaveformDevice(const void* d_wave, int layout, int type, size_t channel_stride, size_t packet_stride,
+                               uint64_t frames, uint8_t* d_pcm, uint64_t* d_clipped = nullptr, bool sync = false) {
+        if (alacgpu_pcm_from_waveform_device(h_.get(), d_wave, layout, type, channel_stride, packet_stride, frames, d_pcm,
+                                             d_clipped, sync ? 1 : 0) != ALACGPU_E_OK)
+            throw std::runtime_error(alacgpu_last_error());
+    }
+
+    // the same pass into the handle's scratch, then EncodeDevice, with no host synchronisation in between
+    void EncodeWaveformDevice(const void* d_wave, int layout, int type, size_t channel_stride, size_t packet_stride,
+                              uint64_t frames, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offsets,
+                              uint64_t* d_clipped = nullptr, bool sync = false) {
+        if (alacgpu_encode_waveform_device(h_.get(), d_wave, layout, type, channel_stride, packet_stride, frames, d_blob,
+                                           blob_cap, d_offsets, d_clipped, sync ? 1 : 0) != ALACGPU_E_OK)
+            throw std::runtime_error(alacgpu_last_error());
+    }
+
+    // milliseconds of the last pack pass (LastKernelMs keeps timing the encode kernels only)
+    float WaveformLastMs() {
+        float ms = 0;
+        if (alacgpu_encoder_waveform_last_ms(h_.get(), &ms) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        return ms;
     }
 
     std::array<uint8_t, 24> Cookie() {

@@ -214,3 +214,83 @@ def find_alac_track(data):
         offsets, sizes = _sample_table(buf, stbl)
         return Track(cookie, offsets, sizes)
     raise Mp4Error(ErrNoALACTrack)
+
+
+# ---- writer ---------------------------------------------------------------------------------------------------------
+def _box(fourcc, payload, large=False):
+    if large:
+        return (1).to_bytes(4, "big") + fourcc + (16 + len(payload)).to_bytes(8, "big") + payload
+    return (8 + len(payload)).to_bytes(4, "big") + fourcc + payload
+
+
+def _full(fourcc, payload, version=0, flags=0):
+    return _box(fourcc, ((version << 24) | flags).to_bytes(4, "big") + payload)
+
+
+def _be(n, *values):
+    return b"".join(int(v).to_bytes(n, "big") for v in values)
+
+
+_UNITY = _be(4, 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)  # the identity matrix of mvhd / tkhd
+
+
+def write_m4a(cookie, blob, offsets, total_frames, sample_rate, channels, bits, _co64=False, _large_mdat=False):
+    """An M4A file around encoded ALAC packets -> bytes. cookie: the 24-byte ALACSpecificConfig (PacketEncoder.cookie());
+    blob / offsets: the packets back to back and their n + 1 boundaries (PacketEncoder.encode*); total_frames: the frames
+    they hold, n - 1 packets of the cookie's frame length and the last one with the rest. Boxes: ftyp, moov, mdat; one
+    trak (tkhd, mdia: mdhd with timescale = sample rate and duration = total_frames, hdlr 'soun', minf: smhd, dinf / dref,
+    stbl: stsd with an 'alac' sample entry around the cookie's full box, stts, stsc with one chunk, stsz, stco). The chunk
+    offset goes to a co64 box and mdat gets a 64-bit size when they do not fit 32 bits; _co64 / _large_mdat force either
+    (tests)."""
+    cookie = bytes(cookie)
+    if len(cookie) != 24:
+        raise ValueError("the cookie is the 24-byte ALACSpecificConfig")
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if offsets.ndim != 1 or len(offsets) < 1:
+        raise ValueError("offsets needs n + 1 entries")
+    n = len(offsets) - 1
+    sizes = np.diff(offsets.astype(np.int64))
+    if n and (sizes.min() < 0 or sizes.max() > 0xFFFFFFFF):
+        raise ValueError("offsets must ascend")
+    body = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1) if isinstance(blob, np.ndarray) else np.frombuffer(bytes(blob), np.uint8)
+    lo, hi = int(offsets[0]), int(offsets[n])
+    if hi > body.size:
+        raise ValueError("offsets leave the blob")
+    body = body[lo:hi].tobytes()
+    total_frames, fl = int(total_frames), int.from_bytes(cookie[0:4], "big")
+    last = total_frames - (n - 1) * fl if n else 0
+    if (n == 0 and total_frames) or (n and not 0 < last <= fl):
+        raise ValueError("%d frames are not %d packets of %d" % (total_frames, n, fl))
+    wide = total_frames > 0xFFFFFFFF  # version 1 boxes: 64-bit times
+    times = lambda scale, dur: _be(8 if wide else 4, 0, 0) + _be(4, scale) + _be(8 if wide else 4, dur)  # noqa: E731
+    v = 1 if wide else 0
+    large = _large_mdat or len(body) + 8 > 0xFFFFFFFF
+
+    entry = bytes(6) + _be(2, 1)  # reserved, data reference index
+    entry += _be(2, 0, 0) + _be(4, 0) + _be(2, channels, bits, 0, 0) + _be(4, (sample_rate << 16) if sample_rate < 65536 else 0)
+    stsd = _full(b"stsd", _be(4, 1) + _box(b"alac", entry + _full(b"alac", cookie)))
+    runs = [] if n == 0 else [(n, fl)] if last == fl else [(1, last)] if n == 1 else [(n - 1, fl), (1, last)]
+    stts = _full(b"stts", _be(4, len(runs)) + b"".join(_be(4, c, d) for c, d in runs))
+    stsc = _full(b"stsc", _be(4, 1 if n else 0) + (_be(4, 1, n, 1) if n else b""))
+    stsz = _full(b"stsz", _be(4, 0, n) + sizes.astype(">u4").tobytes())
+
+    def moov(chunk, co64):
+        where = _be(4, 1 if n else 0) + (_be(8 if co64 else 4, chunk) if n else b"")
+        stbl = _box(b"stbl", stsd + stts + stsc + stsz + _full(b"co64" if co64 else b"stco", where))
+        dinf = _box(b"dinf", _full(b"dref", _be(4, 1) + _full(b"url ", b"", flags=1)))
+        minf = _box(b"minf", _full(b"smhd", bytes(4)) + dinf + stbl)
+        hdlr = _full(b"hdlr", _be(4, 0) + b"soun" + bytes(12) + b"SoundHandler\0")
+        mdhd = _full(b"mdhd", times(sample_rate, total_frames) + _be(2, 0x55C4, 0), version=v)  # language 'und'
+        tkhd = _full(b"tkhd", _be(8 if wide else 4, 0, 0) + _be(4, 1, 0) + _be(8 if wide else 4, total_frames) + bytes(8) +
+                     _be(2, 0, 0, 0x0100, 0) + _UNITY + _be(4, 0, 0), version=v, flags=7)
+        mvhd = _full(b"mvhd", times(sample_rate, total_frames) + _be(4, 0x10000) + _be(2, 0x0100) + bytes(10) + _UNITY + bytes(24) +
+                     _be(4, 2), version=v)
+        return _box(b"moov", mvhd + _box(b"trak", tkhd + _box(b"mdia", mdhd + hdlr + minf)))
+
+    ftyp = _box(b"ftyp", b"M4A " + _be(4, 0) + b"M4A mp42isom")
+    co64 = bool(_co64)
+    chunk = len(ftyp) + len(moov(0, co64)) + (16 if large else 8)
+    if chunk > 0xFFFFFFFF and not co64:
+        co64 = True
+        chunk = len(ftyp) + len(moov(0, co64)) + (16 if large else 8)
+    return ftyp + moov(chunk, co64) + _box(b"mdat", body, large=large)
