@@ -290,6 +290,45 @@ int alacgpu_waveform_device(alacgpu_decoder* dec, const uint8_t* d_pcm, size_t p
 int alacgpu_waveform_last_ms(alacgpu_decoder* dec, float* ms);
 
 /*
+ * CLIPS: a batch of fixed-length crops at arbitrary frame offsets, gathered from the decoder's PCM slots into one
+ * [n_clips][channels][clip_frames] float32 / int32 tensor: one pass of its own behind a decode, like the waveform pass (it
+ * does not touch the decode kernels or their outputs). Input is what alacgpu_waveform_device takes: d_pcm / pcm_stride,
+ * d_frames, and d_status, which may be NULL. Slot i occupies the frames [i * frame_length, (i + 1) * frame_length) of a GRID
+ * over the batch; clip j < n_clips has two 64-bit descriptors on the device: d_begin[j], its first grid frame (any frame, not
+ * only a packet boundary), and d_limit[j], the first slot that does not belong to the clip's source (a clip of file A stops in
+ * front of file B's packets). With FL = frame_length, L = clip_frames >= 1 and d_clips counted in 4-byte elements:
+ *     f[i] = (d_status && d_status[i] != 0) ? 0 : min(d_frames[i], FL)
+ *     g    = d_begin[j] + t,  i = g / FL,  r = g % FL                                      for t < L
+ *     has  = g does not overflow && i < min(d_limit[j], n_packets) && r < f[i]
+ *     d_clips[j * clip_stride + c * channel_stride + t] = has ? sample(i, r, c) : 0        ALACGPU_WAVE_FLOAT / _INT as above
+ *     d_valid[j]       (may be NULL) = the number of t < L with `has`
+ *     d_clip_status[j] (may be NULL) = d_status[i] of the lowest slot i the clip touches (i < min(d_limit[j], n_packets))
+ *                                      with d_status[i] != 0, else 0 (always 0 without d_status)
+ * Every column [0, L) of every [clip][channel] row is written, nothing behind column L or between the rows is touched. A
+ * failed or short slot inside a clip is a gap of zeros, exactly as ALACGPU_WAVE_PACKETS pads; frames behind the clip's last slot
+ * are zeros at the end, and d_valid says how many columns are samples. The descriptors are untrusted: no value of them
+ * causes a read outside the slots [0, n_packets) or behind a slot's first f[i] frames — d_begin past the batch or 2^64 - 1,
+ * d_limit 0 or above n_packets and d_frames[i] above frame_length all give zeros where they apply.
+ * n_clips = 0 succeeds and touches nothing; n_packets = 0 with clips writes zeros (and d_valid = 0).
+ * ALACGPU_E_ARG before any HIP call: a NULL handle; with n_clips > 0 a NULL d_pcm, d_frames, d_begin, d_limit or d_clips;
+ * an unknown type; clip_frames = 0; d_clips not 4-byte aligned; pcm_stride below the frame bytes (with n_packets > 0);
+ * channel_stride < clip_frames; clip_stride < channels * channel_stride; n_packets or n_clips above 2^31 - 1, or strides
+ * whose product with them overflows.
+ * Every alignment of d_pcm, pcm_stride, d_clips, the strides and d_begin gives the same values, loaded and stored 16 bytes
+ * at a time in the body. Asynchronous on the handle's stream unless sync != 0, with the ordering contract
+ * of alacgpu_decode_batch_device: called behind a decode with sync = 0 it runs behind that decode, no host synchronisation
+ * in between. The pass needs no scratch of the handle. d_valid and d_clip_status come from one lane per clip that walks the
+ * slots the clip touches, min(clip_frames / frame_length + 2, n_packets) steps: with frame lengths of a few frames and clips
+ * of millions that lane sets the pass's time; pass both as NULL where they are not needed and no such walk is launched.
+ */
+int alacgpu_clips_device(alacgpu_decoder* dec, const uint8_t* d_pcm, size_t pcm_stride, const uint32_t* d_frames,
+                         const int32_t* d_status, size_t n_packets, const uint64_t* d_begin, const uint64_t* d_limit,
+                         size_t n_clips, uint32_t clip_frames, int type, void* d_clips, size_t channel_stride,
+                         size_t clip_stride, uint32_t* d_valid, int32_t* d_clip_status, int sync);
+/* Duration of the last clip gather in milliseconds: HIP events around its kernels (valid after a sync). */
+int alacgpu_clips_last_ms(alacgpu_decoder* dec, float* ms);
+
+/*
  * Batch ENCODER (0.6.0; the reference is decode-only). Input: one contiguous interleaved little-endian PCM stream in the
  * decoder's output format (2 / 3 / 3 / 4 bytes per sample at 16 / 20 / 24 / 32 bits; a 20-bit sample is left-aligned in
  * its 3 bytes and its low 4 bits are ignored). total_frames frames become ceil(total_frames / frame_length) packets; only

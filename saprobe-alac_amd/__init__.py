@@ -32,6 +32,7 @@ _LIB = None
 __all__ = [
     "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "PacketEncoder", "NewPacketEncoder", "ParseMagicCookie",
     "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load", "save",
+    "load_clips",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -234,6 +235,11 @@ _EXPORTS = {
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
     "alacgpu_waveform_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_clips_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_clips_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     "alacgpu_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "alacgpu_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "alacgpu_encoder_create": (ctypes.c_int, [ctypes.POINTER(PacketConfig), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
@@ -452,6 +458,33 @@ class PacketDecoder:
         packet's frames. dtype torch.float32 (samples x 2^-(w - 1), torchaudio's scale) or torch.int32 (the integers)."""
         return self._decode_waveform(blob, offsets, sizes, layout, dtype)
 
+    def _upload(self, x, np_dtype, t_dtype):
+        """A numpy array, bytes or a tensor -> a contiguous tensor of t_dtype on the handle's device (CUDA tensors of that
+        type stay where they are)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(x, torch.Tensor):
+            return x.to(device=dev, dtype=t_dtype).contiguous()
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            x = np.frombuffer(x, dtype=np.uint8)
+        a = np.ascontiguousarray(x, dtype=np_dtype)
+        if t_dtype is not torch.uint8:
+            a = a.view({8: np.int64, 4: np.int32}[a.itemsize])  # torch has no unsigned 32- / 64-bit tensors
+        return torch.from_numpy(a.copy() if not a.flags.writeable else a).to(dev)
+
+    def _upload_packets(self, blob, offsets, sizes):
+        """The uploads decode_waveform and decode_clips share -> (d_blob, d_off, d_sz or None, n)."""
+        import torch
+        d_blob = self._upload(blob, np.uint8, torch.uint8)
+        d_off = self._upload(offsets, np.uint64, torch.int64)
+        d_sz = None if sizes is None else self._upload(sizes, np.uint32, torch.int32)
+        n = d_off.numel() - (1 if d_sz is None else 0)
+        if n < 0:
+            raise ValueError("offsets without sizes needs n + 1 entries, at least one")
+        if d_sz is not None and d_sz.numel() != n:
+            raise ValueError("offsets and sizes differ in length")
+        return d_blob, d_off, d_sz, n
+
     def _decode_waveform(self, blob, offsets, sizes, layout, dtype, into=None):
         """decode_waveform; into = (tensor [channels, capacity], column): "stream" writes there, from that column on,
         instead of allocating (load() fills one tensor window by window)."""
@@ -462,25 +495,7 @@ class PacketDecoder:
         if layout not in ("stream", "packets"):
             raise ValueError("layout must be 'stream' or 'packets'")
         dev = torch.device("cuda", self.device)
-
-        def up(x, np_dtype, t_dtype):
-            if isinstance(x, torch.Tensor):
-                return x.to(device=dev, dtype=t_dtype).contiguous()
-            if isinstance(x, (bytes, bytearray, memoryview)):
-                x = np.frombuffer(x, dtype=np.uint8)
-            a = np.ascontiguousarray(x, dtype=np_dtype)
-            if t_dtype is not torch.uint8:
-                a = a.view({8: np.int64, 4: np.int32}[a.itemsize])  # torch has no unsigned 32- / 64-bit tensors
-            return torch.from_numpy(a.copy() if not a.flags.writeable else a).to(dev)
-
-        d_blob = up(blob, np.uint8, torch.uint8)
-        d_off = up(offsets, np.uint64, torch.int64)
-        d_sz = None if sizes is None else up(sizes, np.uint32, torch.int32)
-        n = d_off.numel() - (1 if d_sz is None else 0)
-        if n < 0:
-            raise ValueError("offsets without sizes needs n + 1 entries, at least one")
-        if d_sz is not None and d_sz.numel() != n:
-            raise ValueError("offsets and sizes differ in length")
+        d_blob, d_off, d_sz, n = self._upload_packets(blob, offsets, sizes)
         fl, ch = int(self.config.FrameLength), int(self.config.NumChannels)
         stride = (self.frame_bytes + 15) // 16 * 16  # the decode's fast layout
         pcm = torch.empty((max(n, 1), stride), dtype=torch.uint8, device=dev)
@@ -510,6 +525,82 @@ class PacketDecoder:
         if layout == "stream":
             wave = wave[:, col:col + int(starts[n].item())]
         return wave, frames[:n], status[:n]
+
+    def clips_device(self, d_pcm, pcm_stride, d_frames, d_status, n, d_begin, d_limit, n_clips, clip_frames, wtype, d_clips,
+                     channel_stride, clip_stride, d_valid=None, d_clip_status=None, sync=True):
+        """alacgpu_clips_device: raw device pointers (ints). The PCM slots a device decode wrote (d_pcm / pcm_stride / d_frames,
+        d_status or None) -> n_clips crops of clip_frames frames at d_clips, [n_clips][channels] rows, strides in elements,
+        float32 (WAVE_FLOAT) or int32 (WAVE_INT). Slot i is the frames [i * FrameLength, (i + 1) * FrameLength) of a grid;
+        d_begin[j] (uint64) is clip j's first grid frame, d_limit[j] (uint64) the first slot behind its source. Frames a clip
+        does not find (a failed or short slot, the slots from d_limit[j] or n on) are zero; d_valid (uint32, or None) gets
+        the count of those it found, d_clip_status (int32, or None) the status of the first failed slot it touches. Runs on
+        the handle's stream, behind a decode with sync=False."""
+        _check(self._lib.alacgpu_clips_device(self._h, d_pcm, pcm_stride, d_frames, d_status, n, d_begin, d_limit, n_clips,
+                                              clip_frames, wtype, d_clips, channel_stride, clip_stride, d_valid, d_clip_status,
+                                              1 if sync else 0))
+
+    def clips_last_ms(self):
+        """alacgpu_clips_last_ms: HIP events around the kernels of the last clip gather."""
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_clips_last_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def decode_clips(self, blob, offsets, sizes=None, begin=(), limit=None, num_frames=1, dtype=None):
+        """Decode and gather on the device -> (clips [B, channels, num_frames], valid [B], clip_status [B], frames, status),
+        torch tensors on the handle's device.
+
+        blob / offsets / sizes: the packets, as decode_waveform takes them. Packet i decodes into slot i, the frames
+        [i * FrameLength, (i + 1) * FrameLength) of a grid over the batch. begin[j]: the first grid frame of clip j (any
+        frame); limit[j]: the first slot that is not clip j's source any more (None: n for every clip). Frames a clip does
+        not find are zero: valid (int32) counts the ones it found, clip_status is the status word of the first failed packet
+        it touches, or 0. One decode and one gather, no host synchronisation in between."""
+        return self._decode_clips(blob, offsets, sizes, begin, limit, num_frames, dtype)
+
+    def _decode_clips(self, blob, offsets, sizes, begin, limit, num_frames, dtype, dest=None):
+        """decode_clips; dest = (tensor, element, channel_stride, clip_stride): the clips go into that tensor's memory, clip
+        0's channel 0 at that element of it, instead of into a new one (load() and load_clips() fill one tensor window by
+        window), and None is returned for them."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.int32):
+            raise ValueError("dtype must be torch.float32 or torch.int32")
+        L = int(num_frames)
+        if L < 1 or L > 0xFFFFFFFF:
+            raise ValueError("num_frames must be 1 .. 2^32 - 1")
+        dev = torch.device("cuda", self.device)
+        d_blob, d_off, d_sz, n = self._upload_packets(blob, offsets, sizes)
+        d_begin = self._upload(begin, np.uint64, torch.int64)
+        B = d_begin.numel()
+        d_limit = torch.full((B,), n, dtype=torch.int64, device=dev) if limit is None else self._upload(limit, np.uint64, torch.int64)
+        if d_limit.numel() != B:
+            raise ValueError("begin and limit differ in length")
+        ch = int(self.config.NumChannels)
+        stride = (self.frame_bytes + 15) // 16 * 16  # the decode's fast layout
+        pcm = torch.empty((max(n, 1), stride), dtype=torch.uint8, device=dev)
+        frames = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        if dest is None:
+            clips = torch.empty((B, ch, L), dtype=dtype, device=dev)
+            ptr, cs, ps = clips.data_ptr(), L, ch * L
+        else:
+            into, at, cs, ps = dest
+            if into.dtype is not dtype or not into.is_contiguous() or cs < L or ps < ch * cs or at + (B - 1) * ps + (ch - 1) * cs + L > into.numel():
+                raise ValueError("the clips buffer does not take %d clips of %d frames from element %d on" % (B, L, at))
+            clips, ptr = None, into.data_ptr() + 4 * at
+        valid = torch.zeros(B, dtype=torch.int32, device=dev)
+        cstat = torch.zeros(B, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+        if n > 0:
+            self.decode_batch_device(d_blob.data_ptr() if d_blob.numel() else None, d_blob.numel(), d_off.data_ptr(),
+                                     None if d_sz is None else d_sz.data_ptr(), n, pcm.data_ptr(), stride, frames.data_ptr(),
+                                     status.data_ptr(), sync=False)
+        if B > 0:
+            self.clips_device(pcm.data_ptr(), stride, frames.data_ptr(), status.data_ptr(), n, d_begin.data_ptr(), d_limit.data_ptr(),
+                              B, L, WAVE_FLOAT if dtype is torch.float32 else WAVE_INT, ptr, cs, ps, valid.data_ptr(),
+                              cstat.data_ptr(), sync=True)
+        else:
+            self.synchronize()
+        return clips, valid, cstat, frames[:n], status[:n]
 
     def reserve(self, n_packets):
         _check(self._lib.alacgpu_reserve(self._h, n_packets))
@@ -745,15 +836,24 @@ def NewDecoder(source, device=0, window=1024):
     return stream.NewDecoder(source, device=device, window=window)
 
 
-def load(source, device=0, dtype=None):
+def load(source, device=0, dtype=None, frame_offset=0, num_frames=-1):
     """An ALAC M4A/MP4 file -> (waveform [channels, frames], sample_rate), the call shape of torchaudio.load: a planar
     torch tensor on cuda:`device`, float32 in [-1, 1) (dtype=torch.int32: the integer samples). source: a path, a binary file
     object, or the file's bytes. The track is found and configured as NewDecoder does it (ErrNoTrack / ErrConfig); the packets
     are decoded and converted on the device in windows of 48 MB of PCM into one tensor, and the first packet that fails
-    raises the ErrDecode that Read raises when it gets there."""
+    raises the ErrDecode that Read raises when it gets there.
+    frame_offset / num_frames, as in torchaudio.load: the frames [frame_offset, frame_offset + num_frames) of the file, fewer
+    when it ends before (none, [channels, 0], when it ends at or before frame_offset); num_frames = -1: up to the end. Only
+    the packets that cover those frames are decoded — packets are independent — and the frames are cut out of them on the
+    device (PacketDecoder.decode_clips); a failed packet outside the range is not noticed."""
     import torch
     from . import stream
     dtype = torch.float32 if dtype is None else dtype
+    frame_offset, num_frames = int(frame_offset), int(num_frames)
+    if frame_offset < 0 or num_frames < -1:
+        raise ValueError("frame_offset must be >= 0 and num_frames >= -1")
+    if frame_offset or num_frames != -1:
+        return _load_range(source, device, dtype, frame_offset, num_frames)
     _, view, track, cfg = stream.open_track(source)
     raw = np.frombuffer(view, dtype=np.uint8)
     offs, sizes = track.offsets.astype(np.int64), track.sizes.astype(np.int64)
@@ -779,6 +879,161 @@ def load(source, device=0, dtype=None):
     if n_ok < n:
         raise AlacError("reading sample %d: unexpected EOF" % n_ok)
     return wave[:, :total], int(cfg.SampleRate)
+
+
+def _load_range(source, device, dtype, frame_offset, num_frames):
+    """load() of the frames [frame_offset, frame_offset + num_frames): the covering packets in windows, one clip per window
+    gathered straight into the result. Frame k of the file is taken to be frame k % FrameLength of packet k // FrameLength,
+    which holds when every packet but the file's last is full, as encoders write them; a covering packet in front of the
+    last that turns out short raises AlacError (the full load() closes such a gap up, so the frames behind it have other
+    numbers there)."""
+    import torch
+    from . import stream
+    if dtype not in (torch.float32, torch.int32):
+        raise ValueError("dtype must be torch.float32 or torch.int32")
+    _, view, track, cfg = stream.open_track(source)
+    raw = np.frombuffer(view, dtype=np.uint8)
+    offs, sizes = track.offsets.astype(np.int64), track.sizes.astype(np.int64)
+    n, fl, ch = len(sizes), int(cfg.FrameLength), int(cfg.NumChannels)
+    lost = np.nonzero(offs + sizes > raw.size)[0]
+    n_ok = int(lost[0]) if len(lost) else n
+    stop = n * fl if num_frames < 0 else min(n * fl, frame_offset + num_frames)  # the last frame the packets could hold, + 1
+    p0, p1 = frame_offset // fl, -(-stop // fl)
+    dev = torch.device("cuda", device)
+    if p0 >= p1 or stop <= frame_offset:
+        return torch.empty((ch, 0), dtype=dtype, device=dev), int(cfg.SampleRate)
+    p1_ok = min(p1, n_ok)
+    cap = stop - frame_offset
+    wave = torch.empty((ch, cap), dtype=dtype, device=dev)
+    total = 0
+    with NewPacketDecoder(cfg, device) as dec:
+        window = stream.window_packets(dec.frame_bytes)
+        dec.reserve(min(window, max(1, p1_ok - p0)))
+        col = 0
+        for w0 in range(p0, p1_ok, window):
+            w1 = min(w0 + window, p1_ok)
+            first = max(frame_offset, w0 * fl)
+            L = min(stop, w1 * fl) - first
+            lo, hi = int(offs[w0:w1].min()), int((offs[w0:w1] + sizes[w0:w1]).max())
+            _, valid, _, frames, status = dec._decode_clips(raw[lo:hi], offs[w0:w1] - lo, sizes[w0:w1], [first - w0 * fl], None, L,
+                                                            dtype, dest=(wave, col, cap, ch * cap))
+            bad = torch.nonzero(status)
+            if bad.numel():
+                k = int(bad[0].item())
+                e = status_error(int(status[k].item()))
+                raise ErrDecode("decoding packet %d: %s" % (w0 + k, e), status=e.status, sentinel=e.sentinel)
+            short = torch.nonzero(frames[:min(w1, n - 1) - w0] != fl)
+            if short.numel():
+                k = int(short[0].item())
+                raise AlacError("packet %d holds %d of %d frames and is not the file's last: frame offsets behind it are not "
+                                "packet arithmetic" % (w0 + k, int(frames[k].item()), fl))
+            total = col + int(valid[0].item())  # the file's last packet may be short
+            col += L
+    if p1_ok < p1:
+        raise AlacError("reading sample %d: unexpected EOF" % n_ok)
+    return wave[:, :total], int(cfg.SampleRate)
+
+
+def _clip_batch(tracks, starts, first, count, fl):
+    """One decode's worth of load_clips: for clip j the byte range of its covering packets — count[j] packets from first[j]
+    on of tracks[j] = (file bytes, packet offsets, packet sizes, config) — appended to one host blob, the packets' offsets and
+    sizes in it, and the clip's descriptors on the grid of slots -> (blob, offsets, sizes, begin, limit). Every covering
+    packet must lie inside its file's bytes (load_clips checks that first): a range that left them would be cut short here
+    and the packet's bytes would run into the next clip's."""
+    parts, p_offs, p_sizes, begin, limit, at, slot = [], [], [], [], [], 0, 0
+    for j, (raw, offs, sizes, _) in enumerate(tracks):
+        begin.append(slot * fl + starts[j] % fl)
+        if count[j]:
+            o, z = offs[first[j]:first[j] + count[j]], sizes[first[j]:first[j] + count[j]]
+            lo, hi = int(o.min()), int((o + z).max())
+            if lo < 0 or hi > raw.size:
+                raise AlacError("clip %d: its packets leave the file's %d bytes" % (j, raw.size))
+            piece = raw[lo:hi]
+            parts.append(piece)
+            p_offs.append(o - lo + at)
+            p_sizes.append(z)
+            at += piece.size
+            slot += count[j]
+        limit.append(slot)
+    blob = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    offsets = np.concatenate(p_offs) if p_offs else np.zeros(0, np.int64)
+    sz = np.concatenate(p_sizes) if p_sizes else np.zeros(0, np.int64)
+    return blob, offsets, sz, begin, limit
+
+
+def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None):
+    """Fixed-length crops of many ALAC M4A/MP4 files as one batch -> (clips [B, channels, num_frames], lengths [B], sample_rate):
+    clip j is the frames [frame_offsets[j], frame_offsets[j] + num_frames) of sources[j], a planar torch tensor on
+    cuda:`device`, float32 in [-1, 1) or int32 as load() gives them. Frames behind a file's end are zero, and lengths
+    (int32, on the device) says how many of a clip's frames are the file's. sources: paths, binary file objects or the files'
+    bytes; the same object or an equal path may repeat and is opened and parsed once. All tracks must agree in FrameLength,
+    BitDepth, NumChannels, PB / MB / KB / MaxRun and SampleRate (ErrConfig names the first source that differs).
+    Only the packets that cover a clip are read, and all of them go through one upload, one decode and one gather
+    (batches above a window of 48 MB of PCM are split between clips); a failed packet raises ErrDecode with the clip and
+    the packet's index in its file, and a covering packet that lies outside its file's bytes (a truncated file) raises
+    load()'s "unexpected EOF" with the clip in front, before anything is decoded. As in load(frame_offset, num_frames),
+    frame k of a file is frame k % FrameLength of packet k // FrameLength; a short packet in front of a file's last leaves
+    zeros in the clips that cover it, and their lengths count the samples, not a prefix."""
+    import torch
+    from . import stream
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.int32):
+        raise ValueError("dtype must be torch.float32 or torch.int32")
+    sources = list(sources)
+    starts = [int(a) for a in frame_offsets]
+    L = int(num_frames)
+    if not sources or len(starts) != len(sources):
+        raise ValueError("sources and frame_offsets must have the same length, at least 1")
+    if L < 1 or any(a < 0 for a in starts):
+        raise ValueError("num_frames must be >= 1 and every frame offset >= 0")
+    opened, tracks = {}, []
+    for src in sources:
+        key = ("path", os.fspath(src)) if isinstance(src, (str, os.PathLike)) else ("object", id(src))
+        if key not in opened:
+            _, view, track, cfg = stream.open_track(src)
+            opened[key] = (np.frombuffer(view, dtype=np.uint8), track.offsets.astype(np.int64), track.sizes.astype(np.int64), cfg)
+        tracks.append(opened[key])
+    cfg = tracks[0][3]
+    same = ("FrameLength", "BitDepth", "NumChannels", "PB", "MB", "KB", "MaxRun", "SampleRate")
+    for j, t in enumerate(tracks):
+        for name in same:
+            if getattr(t[3], name) != getattr(cfg, name):
+                raise ErrConfig("source %d: %s %d differs from the first source's %d" % (j, name, getattr(t[3], name), getattr(cfg, name)))
+    fl, ch, B = int(cfg.FrameLength), int(cfg.NumChannels), len(sources)
+    # the covering packets of clip j: [first[j], first[j] + count[j]) of its file
+    first = [a // fl for a in starts]
+    count = [max(0, min(-(-(a + L) // fl), len(t[2])) - p) for a, p, t in zip(starts, first, tracks)]
+    for j, (raw, offs, sizes, _) in enumerate(tracks):
+        cover = slice(first[j], first[j] + count[j])
+        lost = np.nonzero(offs[cover] + sizes[cover] > raw.size)[0]
+        if len(lost):
+            raise AlacError("clip %d: reading sample %d: unexpected EOF" % (j, first[j] + int(lost[0])))
+    dev = torch.device("cuda", device)
+    clips = torch.empty((B, ch, L), dtype=dtype, device=dev)
+    lengths = torch.empty(B, dtype=torch.int32, device=dev)
+    with NewPacketDecoder(cfg, device) as dec:
+        window = stream.window_packets(dec.frame_bytes)
+        groups, j0, held = [], 0, 0  # batches of whole clips, each at most a window of packets (or one clip)
+        for j in range(B):
+            if j > j0 and held + count[j] > window:
+                groups.append((j0, j))
+                j0, held = j, 0
+            held += count[j]
+        groups.append((j0, B))
+        dec.reserve(max(1, max(sum(count[a:b]) for a, b in groups)))
+        for a, b in groups:
+            blob, offsets, sz, begin, limit = _clip_batch(tracks[a:b], starts[a:b], first[a:b], count[a:b], fl)
+            _, valid, cstat, _, status = dec._decode_clips(blob, offsets, sz, begin, limit, L, dtype,
+                                                           dest=(clips, a * ch * L, L, ch * L))
+            bad = torch.nonzero(cstat)
+            if bad.numel():
+                k = int(bad[0].item())
+                s0 = limit[k] - count[a + k]
+                i = int(torch.nonzero(status[s0:limit[k]])[0].item())
+                e = status_error(int(status[s0 + i].item()))
+                raise ErrDecode("clip %d: decoding packet %d: %s" % (a + k, first[a + k] + i, e), status=e.status, sentinel=e.sentinel)
+            lengths[a:b] = valid
+    return clips, lengths, int(cfg.SampleRate)
 
 
 def save(dest, wave, sample_rate, bits_per_sample=16, frame_length=4096, device=0, _window=None, **_container):

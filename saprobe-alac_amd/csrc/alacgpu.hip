@@ -20,6 +20,7 @@
  *                  (packet, channel) tasks of the same order: the predictor over the stored residuals, in place
  *   alac_interleave, alac_legacy   PCM of the scanned packets (frame order), whole-packet decoder for the rest
  * alacgpu_waveform_device is a pass of its own behind a decode (k_wave.hip, alac_waveform.h): PCM slots -> planar waveforms.
+ * alacgpu_clips_device is another (k_clips.hip, alac_clips.h): PCM slots -> [clips][channels][frames] crops at any frame offset.
  * The kernels live in k_sort.hip, k_scan.hip, k_dec*.hip and k_split.hip (alac_gpu.h).
  * HBM traffic per packet: compressed bytes in, PCM bytes out, plus the U-channel hand-off tile of stereo pairs
  * ((frame_length + 1) x 64 x int32 per workgroup, row-coalesced, written once and read once) or the sample rows
@@ -28,6 +29,7 @@
 #include "alac_gpu.h"
 #include "alac_host.h"
 #include "alac_waveform.h"
+#include "alac_clips.h"
 
 using namespace alack;
 
@@ -210,6 +212,8 @@ struct alacgpu_decoder {
     DevBuf wave_ws;                                          /* alacgpu_waveform_device: the scan's scratch */
     hipEvent_t ev_w0, ev_w1;                                 /* around the kernels of the last waveform pass */
     bool wave_timed;
+    hipEvent_t ev_c0, ev_c1;                                 /* around the kernels of the last clip gather */
+    bool clips_timed;
 };
 
 namespace {
@@ -622,7 +626,8 @@ struct EventRef {
 };
 std::vector<EventRef> events_of(alacgpu_decoder* d) {
     std::vector<EventRef> v = {{&d->ev_fork, hipEventDisableTiming}, {&d->ev_join, hipEventDisableTiming},
-                               {&d->ev_w0, hipEventDefault}, {&d->ev_w1, hipEventDefault}};
+                               {&d->ev_w0, hipEventDefault}, {&d->ev_w1, hipEventDefault},
+                               {&d->ev_c0, hipEventDefault}, {&d->ev_c1, hipEventDefault}};
     for (uint32_t i = 0; i < kTimingSlots; i++) v.insert(v.end(), {{&d->ev_start[i], hipEventDefault}, {&d->ev_stop[i], hipEventDefault}});
     for (Slot& s : d->slots)
         v.insert(v.end(), {{&s.ev_in, hipEventDisableTiming}, {&s.ev_k, hipEventDisableTiming}, {&s.ev_out, hipEventDisableTiming}});
@@ -665,6 +670,7 @@ void configure(alacgpu_decoder* d, const alacgpu_config* cfg) {
     d->last_n = 0;
     d->last_ppw = d->last_cap = d->last_fit5 = 0;
     d->wave_timed = false;
+    d->clips_timed = false;
     d->lanes_min = 4;
     d->fit_force = 0;
     if (const char* e = getenv("ALACGPU_FIT")) d->fit_force = (uint32_t)atoi(e); /* experiments: 4 / 5 workgroups per CU for every batch */
@@ -1255,6 +1261,76 @@ int alacgpu_waveform_last_ms(alacgpu_decoder* d, float* ms) {
     HIP_TRY(hipSetDevice(d->device));
     HIP_TRY(hipEventSynchronize(d->ev_w1));
     HIP_TRY(hipEventElapsedTime(ms, d->ev_w0, d->ev_w1));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_clips_device(alacgpu_decoder* d, const uint8_t* d_pcm, size_t pcm_stride, const uint32_t* d_frames,
+                         const int32_t* d_status, size_t n, const uint64_t* d_begin, const uint64_t* d_limit, size_t n_clips,
+                         uint32_t clip_frames, int type, void* d_clips, size_t channel_stride, size_t clip_stride,
+                         uint32_t* d_valid, int32_t* d_clip_status, int sync) {
+    if (!d || (n_clips && (!d_pcm || !d_frames || !d_begin || !d_limit || !d_clips))) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    if (type != ALACGPU_WAVE_FLOAT && type != ALACGPU_WAVE_INT) {
+        set_err("unknown waveform type %d", type);
+        return ALACGPU_E_ARG;
+    }
+    if (n > 0x7fffffffu || n_clips > 0x7fffffffu) {
+        set_err("batch too large");
+        return ALACGPU_E_ARG;
+    }
+    if (n_clips == 0) return ALACGPU_E_OK;
+    const uint64_t ch = d->cfg.num_channels;
+    if (clip_frames == 0) {
+        set_err("clip_frames is 0");
+        return ALACGPU_E_ARG;
+    }
+    if (n && (pcm_stride < d->frame_bytes || pcm_stride > SIZE_MAX / n)) {
+        set_err("pcm_stride %zu < frame bytes %zu, or the slots overflow", pcm_stride, d->frame_bytes);
+        return ALACGPU_E_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d_clips) % 4) {
+        set_err("d_clips is not aligned to its 4-byte elements");
+        return ALACGPU_E_ARG;
+    }
+    /* every column of a row inside the row, the rows of a clip inside the clip, and the whole tensor countable in bytes */
+    if (channel_stride < clip_frames || clip_stride / ch < channel_stride || clip_stride > (SIZE_MAX / 8) / n_clips) {
+        set_err("channel_stride %zu / clip_stride %zu too small for clips of %u frames, or the clips overflow", channel_stride, clip_stride,
+                clip_frames);
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(d->device));
+    alacclip::Params p = alacclip::make_params(d->cfg.frame_length, d->cfg.bit_depth, d->cfg.num_channels, (uint32_t)type, clip_frames);
+    p.pcm = d_pcm;
+    p.pcm_stride = pcm_stride;
+    p.frames = d_frames;
+    p.status = d_status;
+    p.n = n;
+    p.begin = d_begin;
+    p.limit = d_limit;
+    p.n_clips = n_clips;
+    p.clips = (uint8_t*)d_clips;
+    p.channel_stride = channel_stride;
+    p.clip_stride = clip_stride;
+    p.valid = d_valid;
+    p.clip_status = d_clip_status;
+    HIP_TRY(hipEventRecord(d->ev_c0, d->stream));
+    HIP_TRY(alack::clips_launch(d->stream, p));
+    HIP_TRY(hipEventRecord(d->ev_c1, d->stream));
+    d->clips_timed = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(d->stream));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_clips_last_ms(alacgpu_decoder* d, float* ms) {
+    if (!d || !ms || !d->clips_timed) {
+        set_err(!d || !ms ? "null argument" : "no clip gather on this handle yet");
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipEventSynchronize(d->ev_c1));
+    HIP_TRY(hipEventElapsedTime(ms, d->ev_c0, d->ev_c1));
     return ALACGPU_E_OK;
 }
 

@@ -99,6 +99,24 @@ public:
         return ms;
     }
 
+    // Clips (alacgpu_clips_device): n_clips crops of clip_frames frames each, gathered from the PCM slots of a device decode
+    // into [n_clips][channels][clip_frames] in the caller's device buffer, on the handle's stream. d_begin[j] = the clip's
+    // first frame on the grid of slots (slot i = frames [i * FrameLength, (i + 1) * FrameLength)), d_limit[j] = the first
+    // slot behind the clip's source. Strides in elements; d_status, d_valid and d_clip_status may be null.
+    void ClipsDevice(const uint8_t* d_pcm, size_t pcm_stride, const uint32_t* d_frames, const int32_t* d_status, size_t n,
+                     const uint64_t* d_begin, const uint64_t* d_limit, size_t n_clips, uint32_t clip_frames,
+                     alacgpu_wave_type type, void* d_clips, size_t channel_stride, size_t clip_stride,
+                     uint32_t* d_valid = nullptr, int32_t* d_clip_status = nullptr, bool sync = true) {
+        if (alacgpu_clips_device(h_.get(), d_pcm, pcm_stride, d_frames, d_status, n, d_begin, d_limit, n_clips, clip_frames, type,
+                                 d_clips, channel_stride, clip_stride, d_valid, d_clip_status, sync ? 1 : 0) != ALACGPU_E_OK)
+            throw std::runtime_error(alacgpu_last_error());
+    }
+    float ClipsLastMs() {
+        float ms = 0;
+        if (alacgpu_clips_last_ms(h_.get(), &ms) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        return ms;
+    }
+
     alacgpu_decoder* handle() const { return h_.get(); }
     // alacgpu_trim(): destroyed decoders leave streams, events and small buffers (<= 2 GB of device memory and
     // 64 MB of pinned memory each, four per device) in a per-process pool for the next one; this frees them
