@@ -418,6 +418,55 @@ int alacgpu_encoder_last_kernel_ms(alacgpu_encoder* enc, float* ms);
 void* alacgpu_encoder_stream(alacgpu_encoder* enc);
 int alacgpu_encoder_synchronize(alacgpu_encoder* enc);
 
+/*
+ * RESAMPLING: float32 rows at one sample rate -> the same rows at another, one pass on a handle of its own (k_resample.hip,
+ * alac_resample.h; no decoder or encoder is involved, and their kernels are untouched). The filter is torchaudio's
+ * sinc_interp_hann (its defaults: lowpass_filter_width 6, rolloff 0.99). With g = gcd(orig, new), o = orig / g, n = new / g,
+ * W = lowpass_filter_width:
+ *     base  = min(o, n) * rolloff,   width = ceil(W * o / base)
+ *     t     = clamp(((k - width) / o - i / n) * base, -W, W)                         phase i < n, tap k < 2 * width + o
+ *     H[i][k] = |t| == W ? 0 : sinc(pi t) * cos(pi t / (2 W))^2 * base / o           in double, sinc(0) = 1
+ *     out_frames(T) = ceil(new * T / orig)
+ *     y[m] = sum_k H[i][k] * x[j * o + k - width],  m = j * n + i,  x[.] = 0 outside [0, T)
+ * The taps of a phase that are not zero are one run; a plan keeps first[i], the k of phase i's first kept tap, and h[i][q] =
+ * float(H[i][first[i] + q]) for q < taps (the widest run). An output is acc = +0.0f; acc = fmaf(h[i][q], x[j * o + first[i] +
+ * q - width], acc) for q = 0 .. taps - 1 in that order, +0.0f for an x outside the row: the same bits on every build.
+ * alacgpu_resampler_create is ALACGPU_E_ARG, before any HIP call, when no plan can be built: a rate of 0, equal rates,
+ * lowpass_filter_width 0, rolloff outside (0, 1], n * (2 * width + 2) table entries above 64 MB, or a ratio so steep that the
+ * inputs of 64 outputs exceed the 3 840 floats a workgroup stages (192 000 -> 8 000 fits). The handle owns a stream, an event
+ * pair and the table on the device; it is single-caller, like a decoder.
+ */
+typedef struct alacgpu_resampler alacgpu_resampler;
+int alacgpu_resampler_create(int device, uint32_t orig_freq, uint32_t new_freq, uint32_t lowpass_filter_width, double rolloff,
+                             alacgpu_resampler** out);
+void alacgpu_resampler_destroy(alacgpu_resampler* rs);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernels (valid after a sync). */
+void* alacgpu_resampler_stream(alacgpu_resampler* rs);
+int alacgpu_resampler_synchronize(alacgpu_resampler* rs);
+int alacgpu_resampler_last_ms(alacgpu_resampler* rs, float* ms);
+/* ceil(new * in_frames / orig) in 64-bit integers; 0 for a NULL handle or when the product leaves 64 bits. */
+uint64_t alacgpu_resample_out_frames(const alacgpu_resampler* rs, uint64_t in_frames);
+/*
+ * rows rows of in_frames float32 frames, row r at d_in + r * in_row_stride (strides in elements), -> rows of out_frames =
+ * alacgpu_resample_out_frames(rs, in_frames) at d_out + r * out_row_stride. Exactly the columns [0, out_frames) of every
+ * output row are written, nothing between or behind the rows; nothing outside [0, in_frames) of an input row is read.
+ * rows = 0 or in_frames = 0 succeeds and touches nothing. ALACGPU_E_ARG before any HIP call: a NULL handle; with work to do a
+ * NULL d_in or d_out, a base that is not 4-byte aligned, in_row_stride < in_frames, out_row_stride < out_frames, or sizes
+ * whose products overflow. Every 4-byte-aligned base and every stride gives the same values, loaded and stored 16 bytes at a
+ * time in the body. Asynchronous on the handle's stream unless sync != 0: the input must be complete, or
+ * ordered on that stream, before the call (the stream is non-blocking: it does not order against torch's by itself).
+ */
+int alacgpu_resample_device(alacgpu_resampler* rs, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames,
+                            float* d_out, size_t out_row_stride, int sync);
+/* The plan the handle's kernel uses: its numbers, and (where the pointers are not NULL and the capacities, counted in
+ * entries, suffice: n * taps and n) the host copies of h[n][taps] and first[n]. */
+typedef struct alacgpu_resample_info {
+    uint32_t o, n, width, taps, tile_out;
+} alacgpu_resample_info;
+int alacgpu_resampler_plan(const alacgpu_resampler* rs, alacgpu_resample_info* info, float* h_out, size_t h_cap,
+                           int32_t* first_out, size_t first_cap);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

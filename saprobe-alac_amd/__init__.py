@@ -32,7 +32,7 @@ _LIB = None
 __all__ = [
     "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "PacketEncoder", "NewPacketEncoder", "ParseMagicCookie",
     "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load", "save",
-    "load_clips",
+    "load_clips", "Resampler", "NewResampler", "resample",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -260,6 +260,17 @@ _EXPORTS = {
     "alacgpu_encoder_last_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     "alacgpu_encoder_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "alacgpu_encoder_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_resampler_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double,
+                                                ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_resampler_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_resampler_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_resampler_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_resampler_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_resample_out_frames": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "alacgpu_resample_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]),
+    "alacgpu_resampler_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                              ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -830,13 +841,141 @@ def NewPacketEncoder(config, device=0):
     return PacketEncoder(config, device)
 
 
+# ---- Resampler (new: torchaudio.functional.resample's sinc_interp_hann on the device) ----------------------------------
+class ResampleInfo(ctypes.Structure):
+    """alacgpu_resample_info (include/alacgpu.h)."""
+
+    _fields_ = [("o", ctypes.c_uint32), ("n", ctypes.c_uint32), ("width", ctypes.c_uint32), ("taps", ctypes.c_uint32),
+                ("tile_out", ctypes.c_uint32)]
+
+
+class Resampler:
+    """float32 rows at orig_freq -> the same rows at new_freq on one MI355X (include/alacgpu.h: alacgpu_resampler_*):
+    torchaudio's sinc_interp_hann, its table built once per handle. ValueError when no plan can be built (equal or zero
+    rates, a width of 0, rolloff outside (0, 1], a ratio too steep for the kernel's staging buffer). Single-caller, bound to
+    one device and one stream."""
+
+    def __init__(self, orig_freq, new_freq, device=0, lowpass_filter_width=6, rolloff=0.99):
+        self._h = ctypes.c_void_p()
+        self._lib = lib()
+        for v in (orig_freq, new_freq, lowpass_filter_width):
+            if int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("the rates and the filter width are integers below 2^32")
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        _check(self._lib.alacgpu_resampler_create(device, self.orig_freq, self.new_freq, int(lowpass_filter_width), float(rolloff),
+                                                  ctypes.byref(self._h)))
+        self.device = device
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.alacgpu_resampler_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def out_frames(self, in_frames):
+        """alacgpu_resample_out_frames: ceil(new_freq * in_frames / orig_freq)."""
+        return int(self._lib.alacgpu_resample_out_frames(self._h, int(in_frames)))
+
+    def resample_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, sync=True):
+        """alacgpu_resample_device: raw device pointers (ints), strides in elements. rows rows of in_frames float32 frames ->
+        rows of out_frames(in_frames); exactly those columns of every output row are written. Runs on the handle's stream,
+        which does not order against torch's: synchronize the input first."""
+        _check(self._lib.alacgpu_resample_device(self._h, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride,
+                                                 1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_resampler_plan -> dict: o, n, width, taps, tile_out, and the host copies of the table the kernel uses, h
+        [n, taps] float32 and first [n] int32 (the tap index of each phase's first kept tap)."""
+        info = ResampleInfo()
+        _check(self._lib.alacgpu_resampler_plan(self._h, ctypes.byref(info), None, 0, None, 0))
+        h = np.zeros((info.n, info.taps), np.float32)
+        first = np.zeros(info.n, np.int32)
+        _check(self._lib.alacgpu_resampler_plan(self._h, ctypes.byref(info), h.ctypes.data, h.size, first.ctypes.data, first.size))
+        out = {k: int(getattr(info, k)) for k, _ in ResampleInfo._fields_}
+        out.update(h=h, first=first)
+        return out
+
+    def last_ms(self):
+        """alacgpu_resampler_last_ms: HIP events around the kernels of the last pass."""
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_resampler_last_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def synchronize(self):
+        _check(self._lib.alacgpu_resampler_synchronize(self._h))
+
+    def __call__(self, waveform):
+        """A float32 CUDA tensor [..., T] on the handle's device -> [..., out_frames(T)] (made contiguous, flattened to rows)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        T = int(waveform.shape[-1])
+        rows = 1
+        for d in waveform.shape[:-1]:
+            rows *= int(d)
+        x = waveform.to(dev).contiguous().reshape(rows, T)
+        frames = self.out_frames(T)
+        if T and not frames:
+            raise ValueError("%d frames are more than one pass takes" % T)
+        out = torch.empty((rows, frames), dtype=torch.float32, device=dev)
+        if rows and frames:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            self.resample_device(x.data_ptr(), T, rows, T, out.data_ptr(), frames, sync=True)
+        return out.reshape(tuple(waveform.shape[:-1]) + (frames,))
+
+
+def NewResampler(orig_freq, new_freq, device=0, lowpass_filter_width=6, rolloff=0.99):
+    """A Resampler (context manager); ValueError where no plan can be built."""
+    return Resampler(orig_freq, new_freq, device, lowpass_filter_width, rolloff)
+
+
+_RESAMPLERS = {}  # (device, orig, new, width, rolloff) -> Resampler: a plan is built once per process
+
+
+def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, device=None):
+    """torchaudio.functional.resample(waveform, orig_freq, new_freq) with its default sinc_interp_hann, on the device: a
+    float32 tensor [..., T] -> [..., ceil(new_freq * T / orig_freq)] on cuda:`device` (default: the tensor's own device, cuda:0
+    for a CPU tensor or a numpy array, which are uploaded). Equal rates return the input as it is; another dtype raises
+    ValueError. The filter table of a (device, rates, width, rolloff) is built once and kept."""
+    import torch
+    if isinstance(waveform, np.ndarray):
+        if waveform.dtype != np.float32:
+            raise ValueError("waveform must be float32")
+    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
+        raise ValueError("waveform must be a float32 torch tensor or numpy array")
+    if waveform.ndim < 1:
+        raise ValueError("waveform must be [..., T]")
+    if int(orig_freq) != orig_freq or int(new_freq) != new_freq or orig_freq <= 0 or new_freq <= 0:
+        raise ValueError("orig_freq and new_freq must be positive integers")
+    if int(orig_freq) == int(new_freq):
+        return waveform
+    if isinstance(waveform, np.ndarray):
+        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
+    if device is None:
+        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    key = (device, int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff))
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = Resampler(orig_freq, new_freq, device, lowpass_filter_width, rolloff)
+    return _RESAMPLERS[key](waveform)
+
+
 def NewDecoder(source, device=0, window=1024):
     """NewDecoder (decode.go:50-76): streaming façade over the batch path, see stream.py."""
     from . import stream
     return stream.NewDecoder(source, device=device, window=window)
 
 
-def load(source, device=0, dtype=None, frame_offset=0, num_frames=-1):
+def load(source, device=0, dtype=None, frame_offset=0, num_frames=-1, sample_rate=None):
     """An ALAC M4A/MP4 file -> (waveform [channels, frames], sample_rate), the call shape of torchaudio.load: a planar
     torch tensor on cuda:`device`, float32 in [-1, 1) (dtype=torch.int32: the integer samples). source: a path, a binary file
     object, or the file's bytes. The track is found and configured as NewDecoder does it (ErrNoTrack / ErrConfig); the packets
@@ -845,10 +984,26 @@ def load(source, device=0, dtype=None, frame_offset=0, num_frames=-1):
     frame_offset / num_frames, as in torchaudio.load: the frames [frame_offset, frame_offset + num_frames) of the file, fewer
     when it ends before (none, [channels, 0], when it ends at or before frame_offset); num_frames = -1: up to the end. Only
     the packets that cover those frames are decoded — packets are independent — and the frames are cut out of them on the
-    device (PacketDecoder.decode_clips); a failed packet outside the range is not noticed."""
+    device (PacketDecoder.decode_clips); a failed packet outside the range is not noticed.
+    sample_rate: the rate wanted. Where the file's differs, what the call gives without it is resampled on the device
+    (resample(): torchaudio's sinc_interp_hann) and sample_rate is the rate returned; frame_offset and num_frames stay in the
+    file's own frames, as in torchaudio.load. float32 only: with dtype=torch.int32 it raises ValueError."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if sample_rate is None:
+        return _load_file(source, device, dtype, frame_offset, num_frames)
+    if dtype is not torch.float32:
+        raise ValueError("sample_rate needs float32 samples: only those are resampled")
+    if int(sample_rate) != sample_rate or sample_rate <= 0:
+        raise ValueError("sample_rate must be a positive integer")
+    wave, rate = _load_file(source, device, dtype, frame_offset, num_frames)
+    return resample(wave, rate, int(sample_rate), device=device), int(sample_rate)
+
+
+def _load_file(source, device, dtype, frame_offset, num_frames):
+    """load() at the file's own rate."""
     import torch
     from . import stream
-    dtype = torch.float32 if dtype is None else dtype
     frame_offset, num_frames = int(frame_offset), int(num_frames)
     if frame_offset < 0 or num_frames < -1:
         raise ValueError("frame_offset must be >= 0 and num_frames >= -1")
@@ -961,7 +1116,7 @@ def _clip_batch(tracks, starts, first, count, fl):
     return blob, offsets, sz, begin, limit
 
 
-def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None):
+def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None, sample_rate=None):
     """Fixed-length crops of many ALAC M4A/MP4 files as one batch -> (clips [B, channels, num_frames], lengths [B], sample_rate):
     clip j is the frames [frame_offsets[j], frame_offsets[j] + num_frames) of sources[j], a planar torch tensor on
     cuda:`device`, float32 in [-1, 1) or int32 as load() gives them. Frames behind a file's end are zero, and lengths
@@ -973,12 +1128,24 @@ def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None):
     the packet's index in its file, and a covering packet that lies outside its file's bytes (a truncated file) raises
     load()'s "unexpected EOF" with the clip in front, before anything is decoded. As in load(frame_offset, num_frames),
     frame k of a file is frame k % FrameLength of packet k // FrameLength; a short packet in front of a file's last leaves
-    zeros in the clips that cover it, and their lengths count the samples, not a prefix."""
+    zeros in the clips that cover it, and their lengths count the samples, not a prefix.
+    sample_rate = R: the clips at that rate, from sources whose SampleRate may differ (every other field must still agree).
+    frame_offsets[j] stays in source j's own frames; num_frames = L counts frames at R. The sources are grouped by their rate
+    r, and each group takes one decode, one gather of Ls = ceil(L * r / R) source frames per clip (L where r = R) and one
+    resample() (torchaudio's sinc_interp_hann), of whose ceil(Ls * R / r) >= L columns the first L are kept; lengths[j] =
+    min(L, ceil(valid * R / r)) for the valid source frames of clip j. The filter sees zeros in front of a clip's first frame and
+    behind its last, not the file's neighbouring frames: exactly what cropping and then resampling gives with torchaudio.
+    float32 only (dtype=torch.int32 raises ValueError); returns (clips, lengths, R)."""
     import torch
     from . import stream
     dtype = torch.float32 if dtype is None else dtype
     if dtype not in (torch.float32, torch.int32):
         raise ValueError("dtype must be torch.float32 or torch.int32")
+    if sample_rate is not None:
+        if dtype is not torch.float32:
+            raise ValueError("sample_rate needs float32 samples: only those are resampled")
+        if int(sample_rate) != sample_rate or sample_rate <= 0:
+            raise ValueError("sample_rate must be a positive integer")
     sources = list(sources)
     starts = [int(a) for a in frame_offsets]
     L = int(num_frames)
@@ -994,12 +1161,41 @@ def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None):
             opened[key] = (np.frombuffer(view, dtype=np.uint8), track.offsets.astype(np.int64), track.sizes.astype(np.int64), cfg)
         tracks.append(opened[key])
     cfg = tracks[0][3]
-    same = ("FrameLength", "BitDepth", "NumChannels", "PB", "MB", "KB", "MaxRun", "SampleRate")
+    same = ("FrameLength", "BitDepth", "NumChannels", "PB", "MB", "KB", "MaxRun") + (("SampleRate",) if sample_rate is None else ())
     for j, t in enumerate(tracks):
         for name in same:
             if getattr(t[3], name) != getattr(cfg, name):
                 raise ErrConfig("source %d: %s %d differs from the first source's %d" % (j, name, getattr(t[3], name), getattr(cfg, name)))
-    fl, ch, B = int(cfg.FrameLength), int(cfg.NumChannels), len(sources)
+    ids = list(range(len(sources)))
+    if sample_rate is None:
+        clips, lengths = _gather_clips(tracks, starts, ids, L, device, dtype)
+        return clips, lengths, int(cfg.SampleRate)
+    R = int(sample_rate)
+    dev = torch.device("cuda", device)
+    clips = torch.empty((len(sources), int(cfg.NumChannels), L), dtype=dtype, device=dev)
+    lengths = torch.empty(len(sources), dtype=torch.int32, device=dev)
+    for r in sorted({int(t[3].SampleRate) for t in tracks}):
+        if r <= 0:
+            raise ErrConfig("a source's SampleRate is 0")
+        own = [j for j in ids if int(tracks[j][3].SampleRate) == r]
+        Ls = L if r == R else -(-L * r // R)
+        part, valid = _gather_clips([tracks[j] for j in own], [starts[j] for j in own], own, Ls, device, dtype)
+        at = torch.tensor(own, dtype=torch.int64, device=dev)
+        if r == R:
+            clips[at], lengths[at] = part, valid
+        else:
+            clips[at] = resample(part, r, R, device=device)[:, :, :L]
+            lengths[at] = torch.clamp((valid.to(torch.int64) * R + (r - 1)) // r, max=L).to(torch.int32)
+    return clips, lengths, R
+
+
+def _gather_clips(tracks, starts, ids, L, device, dtype):
+    """load_clips for sources of one configuration (tracks[0]'s): clip k, known to the caller as clip ids[k], is L frames of
+    tracks[k] from starts[k] on -> (clips [B, channels, L], lengths [B])."""
+    import torch
+    from . import stream
+    cfg = tracks[0][3]
+    fl, ch, B = int(cfg.FrameLength), int(cfg.NumChannels), len(tracks)
     # the covering packets of clip j: [first[j], first[j] + count[j]) of its file
     first = [a // fl for a in starts]
     count = [max(0, min(-(-(a + L) // fl), len(t[2])) - p) for a, p, t in zip(starts, first, tracks)]
@@ -1007,7 +1203,7 @@ def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None):
         cover = slice(first[j], first[j] + count[j])
         lost = np.nonzero(offs[cover] + sizes[cover] > raw.size)[0]
         if len(lost):
-            raise AlacError("clip %d: reading sample %d: unexpected EOF" % (j, first[j] + int(lost[0])))
+            raise AlacError("clip %d: reading sample %d: unexpected EOF" % (ids[j], first[j] + int(lost[0])))
     dev = torch.device("cuda", device)
     clips = torch.empty((B, ch, L), dtype=dtype, device=dev)
     lengths = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1031,9 +1227,9 @@ def load_clips(sources, frame_offsets, num_frames, device=0, dtype=None):
                 s0 = limit[k] - count[a + k]
                 i = int(torch.nonzero(status[s0:limit[k]])[0].item())
                 e = status_error(int(status[s0 + i].item()))
-                raise ErrDecode("clip %d: decoding packet %d: %s" % (a + k, first[a + k] + i, e), status=e.status, sentinel=e.sentinel)
+                raise ErrDecode("clip %d: decoding packet %d: %s" % (ids[a + k], first[a + k] + i, e), status=e.status, sentinel=e.sentinel)
             lengths[a:b] = valid
-    return clips, lengths, int(cfg.SampleRate)
+    return clips, lengths
 
 
 def save(dest, wave, sample_rate, bits_per_sample=16, frame_length=4096, device=0, _window=None, **_container):
