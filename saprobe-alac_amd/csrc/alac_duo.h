@@ -72,6 +72,14 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     constexpr bool EMIT_A = (EA || EC) && LAST && !RAW; /* the samples leave wave B through the queue */
     constexpr bool DO_EMIT = EMIT_A ? (EC ? DO_C : DO_A) : DO_B;
     constexpr uint32_t CH = EMIT_A ? DUO_CHUNK / 2u : DUO_CHUNK;
+    /* U16: 16-bit pairs in workgroups with a writer wave. Of l = u + (v & nzm) - ((mixRes * v) >> mixSh) and r = l - v the
+     * PCM keeps the low 16 bits, and u enters by addition only: its low half is all the writer needs. The hand-off tile
+     * then holds TWO steps per cell, row i / 2 = (u[i] & 0xffff) | (u[i + 1] << 16): the predictor wave stores every other
+     * step (U16_OUT: the U phase of such a pair, which its caller marks F16), the writer wave loads half as many dwords and
+     * unmixes two frames at a time on half-words (C16). Every other width, mono, the wave pairs without a writer wave and
+     * the split pipeline keep one int32 per step. */
+    constexpr bool U16_OUT = F16 && EC && OUT == OUT_UTILE;
+    constexpr bool C16 = F16 && EC && CPE && EMIT_A;
     const uint32_t na = GEN ? na_rt : (uint32_t)NA;
     uint32_t kb = cfg.kb;
     ALAC_OWN_REG(kb); /* its own register: cfg is an 8-dword kernel-argument tuple that would otherwise be pulled out
@@ -224,11 +232,18 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     };
     /* B: sample i (step j of chunk buffer buf) is reconstructed: history; then the U hand-off tile, the sample
      * queue to wave A, or the writer */
+    uint32_t u_even = 0; /* U16_OUT: the sample of the last even step */
     auto put = [&](uint32_t buf, uint32_t j, uint32_t i, int32_t o, int32_t u, uint64_t sw, uint32_t jj, auto fp) {
 #pragma unroll
         for (int t = NR; t >= 1; --t) hb[t] = hb[t - 1];
         hb[0] = (uint32_t)o ^ BIAS;
-        if (!LAST) *wv.u_row(i) = o; /* dead lanes write their own unused cell */
+        if (!LAST && U16_OUT) {
+            /* half-word cells, a step at a time (whole chunks: predict_chunk, one base address per group): the even step's
+             * sample waits for the odd one's; an odd number of steps ends with a lone store */
+            if (i & 1u) *wv.u_row(i >> 1) = (int32_t)ALAC_PACK_LO16(u_even, o);
+            else if (i + 1u == n_it) *wv.u_row(i >> 1) = o;
+            else u_even = (uint32_t)o;
+        } else if (!LAST) *wv.u_row(i) = o; /* dead lanes write their own unused cell */
         else if (EMIT_A) wv.rq_write(buf, CH + j, o);
         else emit(i, o, u, sw, jj, fp);
     };
@@ -352,6 +367,71 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
         }
         wv.st_step(); /* collective of wave A */
     };
+    /* C16: the writer wave of 16-bit pairs. up: the U tile's rows of the chunk it writes next, two steps per dword. They are
+     * asked for right after the chunk before has been written (the same registers: nothing to copy), a whole iteration
+     * before they are used; the wave spends most of that iteration at the barrier. */
+    uint32_t up[CH / 2u] = {};
+    auto fetch_u16 = [&](uint32_t c) {
+        if ((c + 1u) * CH <= n_it) { /* a whole chunk: one base address, immediate offsets */
+            const int32_t* const ub = wv.u_row(c * (CH / 2u));
+            const ptrdiff_t rs = wv.u_row(1u) - wv.u_row(0u);
+#pragma unroll
+            for (uint32_t k = 0; k < CH / 2u; ++k) up[k] = (uint32_t)ub[(ptrdiff_t)k * rs];
+            return;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < CH / 2u; ++k) {
+            up[k] = 0;
+            if (c * CH + 2u * k < n_it) up[k] = (uint32_t)*wv.u_row(c * (CH / 2u) + k); /* scalar: rows past n_it do not exist */
+        }
+    };
+    const bool all_mat = C16 && !wv.any(ns != 0u && mix_res == 0); /* every live lane's pair is matrixed */
+    auto emit_chunk16 = [&](uint32_t c) {
+        const uint32_t buf = c & 1u, c0 = c * CH, c_end = c0 + CH;
+        const bool ends_here = ns > c0 && ns < c_end;
+        if (c_end <= n_it && !wv.any(ends_here)) {
+            /* A whole chunk that every lane keeps whole or not at all (as FP_OK in the wave pairs): no test per step, the
+             * dwords go to fixed places of the lane's row and are counted once. Two frames at a time on half-words:
+             * matrix.go:40-41 is r = u - m, l = r + v with m = (mixRes * v) >> mixSh (32-bit), modulo 2^16 from there. */
+            const uint32_t inc = ns >= c_end ? CH : 0u;
+            int32_t vq[CH];
+#pragma unroll
+            for (uint32_t j = 0; j < CH; ++j) vq[j] = wv.rq_read(buf, CH + j);
+            const uint32_t base = wv.st_group_base(CH);
+            /* (one wave-uniform test per chunk, straight-line code behind it) */
+            auto pairs = [&](auto mat) {
+                constexpr bool MAT = decltype(mat)::value;
+#pragma unroll
+                for (uint32_t k = 0; k < CH / 2u; ++k) {
+                    const int32_t v0 = vq[2u * k], v1 = vq[2u * k + 1u];
+                    const uint32_t m = ALAC_PACK_LO16(ALAC_MUL24(mix_res, v0) >> mix_sh, ALAC_MUL24(mix_res, v1) >> mix_sh);
+                    const uint32_t v = ALAC_PACK_LO16(v0, v1);
+                    uint32_t l, r = ALAC_PK_SUB16(up[k], m);
+                    if (MAT) {
+                        l = ALAC_PK_ADD16(r, v);
+                    } else { /* matrix.go:50-51 for the lanes with mixRes 0 (m = 0): l = u, r = v */
+                        l = ALAC_PK_ADD16(r, v & nzm);
+                        r = ALAC_BFI(nzm, r, v);
+                    }
+                    wv.st_put(base, 2u * k, ALAC_PACK_LO16(l, r), inc);
+                    wv.st_put(base, 2u * k + 1u, ALAC_PACK_HI16(l, r), inc);
+                }
+            };
+            if (all_mat) pairs(fp_yes{});
+            else pairs(fp_no{});
+            wv.st_advance(inc);
+            wv.st_step();
+            return;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < CH; ++j) {
+            const uint32_t i = c0 + j;
+            if (i < n_it) emit(i, wv.rq_read(buf, CH + j), (int32_t)(up[j / 2u] >> (16u * (j & 1u))), 0ull, 0u, fp_no{});
+        }
+        wv.st_step();
+        /* a lane whose frames ended inside this chunk writes its tail out now: whole chunks to come scribble over its row */
+        if (ends_here) (void)wv.st_finish();
+    };
     /* steady-state groups of role B: UN unrolled steps. Long predictors and the wide writers (64-bit shift windows)
      * take half groups, or registers run out. For the writers, what a group needs from HBM / L2 (the U samples of its
      * frames, the 8-byte windows on their shift values) is requested one group AHEAD, into upre / spre, so that the
@@ -453,6 +533,22 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
                         }
                         continue;
                     }
+                    if (U16_OUT) {
+                        /* half-word cells: a group starts at an even step and fills UN / 2 rows, addressed from one base
+                         * by immediate offsets (rows are a constant number of cells apart: u_row) */
+                        int32_t* const ub = wv.u_row(row0 >> 1);
+                        const ptrdiff_t rs = wv.u_row(1u) - wv.u_row(0u);
+#pragma unroll
+                        for (uint32_t j = 0; j < UN; ++j) {
+                            const int32_t o = predict_q(dv[j], wrap);
+#pragma unroll
+                            for (int t = NR; t >= 1; --t) hb[t] = hb[t - 1];
+                            hb[0] = (uint32_t)o ^ BIAS;
+                            if (j & 1u) ub[(ptrdiff_t)(j >> 1) * rs] = (int32_t)ALAC_PACK_LO16(u_even, o);
+                            else u_even = (uint32_t)o;
+                        }
+                        continue;
+                    }
 #pragma unroll
                     for (uint32_t j = 0; j < UN; ++j)
                         put(buf, g + j, c * CH + g + j, predict_q(dv[j], wrap), uv[j], sv[j], j, fp);
@@ -527,7 +623,10 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
         if (DO_A && EMIT_A && !EC) {
             if (c >= 2u) emit_chunk(c - 2u);
         }
-        if (DO_C && EMIT_A) {
+        if (DO_C && C16) {
+            if (c >= 2u) emit_chunk16(c - 2u);
+            if (c >= 1u && c <= nch) fetch_u16(c - 1u);
+        } else if (DO_C && EMIT_A) {
             if (c >= 2u) {
 #pragma unroll
                 for (uint32_t j = 0; j < CH; ++j) {
@@ -574,7 +673,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
  */
 /* NAC: the order as a compile-time constant (four lanes: where top sits is then one DPP pattern and one register, without
  * a branch or a select in the step), 0: the wave-uniform run-time value na (two lanes: one select) */
-template <class W, class B, int T, int OUT, int LPP, int NAC = 0>
+template <class W, class B, int T, int OUT, int LPP, int NAC = 0, bool U16 = false>
 ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, uint32_t hdr_pos, uint32_t den_shift,
                               uint32_t chan_bits, uint32_t na_rt) {
     static_assert(LPP == 2 || LPP == 4, "lanes per packet");
@@ -667,8 +766,14 @@ ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, u
     };
     using yes = std::integral_constant<bool, true>;
     using no = std::integral_constant<bool, false>;
+    uint32_t u_even = 0; /* U16: the sample of the last even step */
     auto put = [&](uint32_t buf, uint32_t k, uint32_t i, int32_t o) {
-        if (!LAST) *wv.u_row(i) = o; /* every lane of the group stores the same value to the packet's cell */
+        if (!LAST && U16) {
+            /* half-word cells (duo_phase: U16_OUT), two steps each; an odd number of steps ends with a lone store */
+            if (i & 1u) *wv.u_row(i >> 1) = (int32_t)ALAC_PACK_LO16(u_even, o);
+            else if (i + 1u == n_it) *wv.u_row(i >> 1) = o;
+            else u_even = (uint32_t)o;
+        } else if (!LAST) *wv.u_row(i) = o; /* every lane of the group stores the same value to the packet's cell */
         else wv.rq_write(buf, CH + k, o);
     };
     auto predict_chunk = [&](uint32_t cc) {
@@ -679,6 +784,17 @@ ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, u
                 uint32_t dv[CH];
 #pragma unroll
                 for (uint32_t k = 0; k < CH; ++k) dv[k] = (uint32_t)wv.rq_read(buf, k);
+                if (!LAST && U16) { /* a whole chunk starts at an even step: CH / 2 rows from one base address */
+                    int32_t* const ub = wv.u_row(i0 >> 1);
+                    const ptrdiff_t rs = wv.u_row(1u) - wv.u_row(0u);
+#pragma unroll
+                    for (uint32_t k = 0; k < CH; ++k) {
+                        const int32_t o = step(i0 + k, dv[k], yes{}, wrap_c);
+                        if (k & 1u) ub[(ptrdiff_t)(k >> 1) * rs] = (int32_t)ALAC_PACK_LO16(u_even, o);
+                        else u_even = (uint32_t)o;
+                    }
+                    return;
+                }
 #pragma unroll
                 for (uint32_t k = 0; k < CH; ++k) put(buf, k, i0 + k, step(i0 + k, dv[k], yes{}, wrap_c));
             };
@@ -714,29 +830,29 @@ ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, u
 }
 
 /* taps per lane by the (wave-uniform) order, 3..16 (duo_lanes_key) */
-template <class W, int OUT, int LPP, class B>
+template <class W, int OUT, int LPP, bool U16 = false, class B>
 ALAC_DEV void duo_phase_lanes_na(W& wv, uint32_t na, const B& bits, uint32_t q, uint32_t n_it, uint32_t hdr_pos, uint32_t den_shift,
                                  uint32_t chan_bits) {
     if constexpr (LPP == 4) {
 #define ALAC_L4(N) \
-    case N: duo_phase_lanes<W, B, (N + 3) / 4, OUT, 4, N>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+    case N: duo_phase_lanes<W, B, (N + 3) / 4, OUT, 4, N, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
         switch (na) { /* 3..16 (duo_lanes_key) */
             ALAC_L4(3) ALAC_L4(4) ALAC_L4(5) ALAC_L4(6) ALAC_L4(7) ALAC_L4(8) ALAC_L4(9) ALAC_L4(10) ALAC_L4(11) ALAC_L4(12)
             ALAC_L4(13) ALAC_L4(14) ALAC_L4(15)
-            default: duo_phase_lanes<W, B, 4, OUT, 4, 16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            default: duo_phase_lanes<W, B, 4, OUT, 4, 16, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
         }
 #undef ALAC_L4
     } else {
         switch ((na + 1u) / 2u) {
             case 0:
             case 1:
-            case 2: duo_phase_lanes<W, B, 2, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
-            case 3: duo_phase_lanes<W, B, 3, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
-            case 4: duo_phase_lanes<W, B, 4, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
-            case 5: duo_phase_lanes<W, B, 5, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
-            case 6: duo_phase_lanes<W, B, 6, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
-            case 7: duo_phase_lanes<W, B, 7, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
-            default: duo_phase_lanes<W, B, 8, OUT, 2>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            case 2: duo_phase_lanes<W, B, 2, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            case 3: duo_phase_lanes<W, B, 3, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            case 4: duo_phase_lanes<W, B, 4, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            case 5: duo_phase_lanes<W, B, 5, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            case 6: duo_phase_lanes<W, B, 6, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            case 7: duo_phase_lanes<W, B, 7, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
+            default: duo_phase_lanes<W, B, 8, OUT, 2, 0, U16>(wv, bits, q, n_it, hdr_pos, den_shift, chan_bits, na); break;
         }
     }
 }
@@ -823,6 +939,10 @@ ALAC_DEV int32_t decode_regular_duo(W& wv, const DevCfg& cfg, uint32_t key, bool
     constexpr bool DO_A = ROLE == ROLE_A || ROLE == ROLE_BOTH, DO_B = ROLE == ROLE_B || ROLE == ROLE_BOTH;
     constexpr bool DO_C = ROLE == ROLE_C || ROLE == ROLE_BOTH;
     constexpr int WM = DEPTH_SEL == 24 ? 1 : 0; /* 24-bit streams: wide channels have 24 or 25 bits, never more (duo_phase) */
+    constexpr bool U16 = EC && DEPTH_SEL == 16; /* 16-bit streams, a writer wave: U crosses the tile as half-words (duo_phase) */
+    /* the predictor wave's cell format follows DEPTH_SEL, the writer wave's the V phase chosen below: with a writer wave the
+     * caller names its sample width, so that the two cannot disagree */
+    static_assert(!EC || DEPTH_SEL != 0, "workgroups with a writer wave are compiled per sample width");
     const BitsT<false> bits{pkt, size, avail}; /* regular packets hold at least 12 bytes (classify_regular) */
     const bool cpe = cfg.num_channels == 2;
     /* chanBits > 23: predict_wide. WIDE_SEL 0 / 1: the caller only ever passes keys of that kind (the other half is
@@ -863,7 +983,7 @@ ALAC_DEV int32_t decode_regular_duo(W& wv, const DevCfg& cfg, uint32_t key, bool
     if constexpr (LANES != 0) {
         static_assert(ROLE == ROLE_B && EC && WIDE_SEL == 0, "a predictor wave beside an entropy and a writer wave, narrow channels");
         if (cpe) {
-            duo_phase_lanes_na<W, OUT_UTILE, LANES>(wv, na_u, bits, q, n_it, hdr_u, (hu >> 8) & 0xfu, chan_bits);
+            duo_phase_lanes_na<W, OUT_UTILE, LANES, U16>(wv, na_u, bits, q, n_it, hdr_u, (hu >> 8) & 0xfu, chan_bits);
             duo_phase_lanes_na<W, OUT_STEREO, LANES>(wv, na_v, bits, q, n_it, hdr_v, (hv >> 8) & 0xfu, chan_bits);
         } else {
             duo_phase_lanes_na<W, OUT_MONO, LANES>(wv, na_u, bits, q, n_it, hdr_u, (hu >> 8) & 0xfu, chan_bits);
@@ -882,7 +1002,8 @@ ALAC_DEV int32_t decode_regular_duo(W& wv, const DevCfg& cfg, uint32_t key, bool
     s.set_pb((cfg.pb * ((hu >> 5) & 7u)) / 4u); /* decoder.go:299 */
     if (DO_A) s.rd.start(wv, live ? s.pos : s.rd.bias);
     if constexpr (WIDE_SEL != 1) if (!wide) {
-        if (cpe) duo_phase_na<W, OUT_UTILE, ROLE, false, true, false, EC>(wv, na_u, cfg, bits, s, size, ns, n_it, hdr_u, (hu >> 8) & 0xfu, chan_bits, mix_res, mix_sh, shift_pos, 0u);
+        /* (U16: the hand-off tile of 16-bit pairs with a writer wave holds half-words, duo_phase) */
+        if (cpe) duo_phase_na<W, OUT_UTILE, ROLE, U16, true, false, EC>(wv, na_u, cfg, bits, s, size, ns, n_it, hdr_u, (hu >> 8) & 0xfu, chan_bits, mix_res, mix_sh, shift_pos, 0u);
         else duo_phase_na<W, OUT_MONO, ROLE, false, true, false, EC>(wv, na_u, cfg, bits, s, size, ns, n_it, hdr_u, (hu >> 8) & 0xfu, chan_bits, 0, 0, shift_pos, sb);
     }
     if constexpr (WIDE_SEL != 0) if (wide) {

@@ -99,6 +99,22 @@ __device__ __forceinline__ int32_t alac_med3_0(int32_t x, int32_t m) {
     return r;
 }
 #define ALAC_MED3_0(x, m) alac_med3_0((int32_t)(x), (int32_t)(m))
+/* half-words (alac_duo.h: the U tile and the writer of 16-bit pairs). v_perm_b32 picks the bytes of {src0, src1}: 0-3 are
+ * src1's, 4-7 src0's */
+#define ALAC_PACK_LO16(x, y) __builtin_amdgcn_perm((uint32_t)(y), (uint32_t)(x), 0x05040100u)
+#define ALAC_PACK_HI16(x, y) __builtin_amdgcn_perm((uint32_t)(y), (uint32_t)(x), 0x07060302u)
+__device__ __forceinline__ uint32_t alac_pk_add16(uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_pk_add_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+#define ALAC_PK_ADD16(a, b) alac_pk_add16((uint32_t)(a), (uint32_t)(b))
+__device__ __forceinline__ uint32_t alac_pk_sub16(uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_pk_sub_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+#define ALAC_PK_SUB16(a, b) alac_pk_sub16((uint32_t)(a), (uint32_t)(b))
 #define ALAC_PICK(dst, src) asm volatile("v_mov_b32 %0, %1" : "+v"(dst) : "v"(src))
 #define ALAC_OWN_REG(x) asm volatile("" : "+v"(x))
 typedef uint32_t alac_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));

@@ -128,6 +128,23 @@
 /* (x >> off[4:0]) & ((1 << width[4:0]) - 1): v_bfe_u32 on the GPU */
 #define ALAC_BFE(x, off, width) ((((uint32_t)(x)) >> ((off) & 31u)) & ((1u << ((width) & 31u)) - 1u))
 #endif
+#ifndef ALAC_PACK_LO16
+/* the low halves of x and y in one dword, x below y: one v_perm_b32 on the GPU */
+#define ALAC_PACK_LO16(x, y) ((((uint32_t)(x)) & 0xffffu) | (((uint32_t)(y)) << 16))
+#endif
+#ifndef ALAC_PACK_HI16
+/* the high halves of x and y in one dword, x below y: one v_perm_b32 on the GPU */
+#define ALAC_PACK_HI16(x, y) ((((uint32_t)(x)) >> 16) | (((uint32_t)(y)) & 0xffff0000u))
+#endif
+#ifndef ALAC_PK_ADD16
+/* both halves of a dword added / subtracted on their own, modulo 2^16: v_pk_add_u16 / v_pk_sub_u16 on the GPU */
+#define ALAC_PK_ADD16(a, b) \
+    (((((uint32_t)(a)) + ((uint32_t)(b))) & 0xffffu) | (((((uint32_t)(a)) >> 16) + (((uint32_t)(b)) >> 16)) << 16))
+#endif
+#ifndef ALAC_PK_SUB16
+#define ALAC_PK_SUB16(a, b) \
+    (((((uint32_t)(a)) - ((uint32_t)(b))) & 0xffffu) | (((((uint32_t)(a)) >> 16) - (((uint32_t)(b)) >> 16)) << 16))
+#endif
 
 namespace alac {
 
