@@ -110,6 +110,8 @@ struct HostWaveMem : HostWave {
  *          -1   = route like alacgpu.hip does (wave-pair decoder of alac_duo.h for regular packets, split pipeline
  *                 for > 2 channels, whole-packet decoder otherwise);
  *          -2   = split pipeline for every non-regular packet, whatever the channel count.
+ *          -3   = routes like -1; regular packets of 16-bit streams take the wave pair WITHOUT a writer wave (k_dec16g.hip:
+ *                 the PCM is written by the predictor wave, or by the entropy wave for mono with orders 5..16).
  * classes_out (may be null) gets the sort key / route. */
 extern "C" int lane_sim_decode_batch(const alacgpu_config* cfg, const uint8_t* blob_in, size_t blob_bytes,
                                      const uint64_t* offsets, const uint32_t* sizes, size_t n, uint8_t* out,
@@ -160,7 +162,9 @@ extern "C" int lane_sim_decode_batch(const alacgpu_config* cfg, const uint8_t* b
             if (key != alac::KEY_IRREGULAR) {
                 if (classes_out) classes_out[i] = key;
                 /* the same instantiations as the GPU library's kernels, one per sample width (k_dec16 / 24 / 32.hip) */
-                if (dc.bit_depth == 16)
+                if (dc.bit_depth == 16 && variant == -3)
+                    status[i] = alac::decode_regular_duo<HostWave, alac::ROLE_BOTH, -1, 16, false>(wv, dc, key, true, p, sizes[i], avail, o, &frames_out[i]);
+                else if (dc.bit_depth == 16)
                     status[i] = alac::decode_regular_duo<HostWave, alac::ROLE_BOTH, -1, 16, true>(wv, dc, key, true, p, sizes[i], avail, o, &frames_out[i]);
                 else if (dc.bit_depth == 32)
                     status[i] = alac::decode_regular_duo<HostWave, alac::ROLE_BOTH, -1, 32, true>(wv, dc, key, true, p, sizes[i], avail, o, &frames_out[i]);

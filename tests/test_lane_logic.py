@@ -124,6 +124,32 @@ def test_wave_pair_chunk_tails(oracle, synth, lane_sim, helpers, depth, ch, fl):
         helpers.assert_same_decode(cfg, ref, got, bpf, "profile %d" % prof)
 
 
+@pytest.mark.parametrize("ch,fl", [(2, 4096), (1, 512), (2, 33), (2, 47), (2, 1000), (1, 4095)])
+def test_pair_form_without_a_writer_wave(oracle, synth, lane_sim, helpers, ch, fl):
+    """Variant -3: 16-bit regular packets through the wave pair as alac_decode_16g runs it, the PCM written by the predictor
+    wave (pairs: at fixed places in chunks that every lane keeps whole) or by the entropy wave (mono, orders 5..16: duo_emit_in_a).
+    Valid streams, then damaged ones; for mono, both writers must really be reached."""
+    cfg = oracle.make_config(fl, 16, ch)
+    bpf = ch * 2
+    rng = np.random.default_rng(fl * 10 + ch)
+    for prof in (synth.PROFILE_MUSIC, synth.PROFILE_NOISE, synth.PROFILE_QUIET, synth.PROFILE_STRESS):
+        b = synth.gen_batch(cfg, 96, profile=prof, threads=4)
+        ref = oracle.decode_batch(cfg, b.blob, b.offsets, b.sizes, threads=4)
+        got = lane_sim(cfg, b.blob, b.offsets, b.sizes, variant=-3, want_classes=True)
+        helpers.assert_same_decode(cfg, ref, got[:3], bpf, "profile %d variant -3" % prof)
+        if ch == 1 and prof == synth.PROFILE_MUSIC:
+            keys = got[3]
+            regular = keys < 1024                     # narrow regular keys: numU * 32 + numV
+            order = (keys >> 5) & 31
+            in_a = regular & (order >= 5) & (order <= 16)
+            assert in_a.sum() >= 48                   # the entropy wave writes
+            assert (regular & ~in_a).sum() >= 8       # the predictor wave writes
+        blob, offs, sizes = helpers.pack_packets(helpers.mutate_packets(b, rng, 200))
+        ref = oracle.decode_batch(cfg, blob, offs, sizes, threads=4)
+        got = lane_sim(cfg, blob, offs, sizes, variant=-3)
+        helpers.assert_same_decode(cfg, ref, got, bpf, "damaged, profile %d variant -3" % prof)
+
+
 @pytest.mark.parametrize("depth,ch,fl", [(16, 2, 256), (24, 2, 128), (16, 1, 64), (24, 8, 48), (32, 2, 64), (20, 3, 50)])
 def test_dense_blob_with_hostile_neighbours(oracle, synth, lane_sim, helpers, depth, ch, fl):
     """Packets back to back as in an mdat (internal/mp4/mp4.go:382-420): no zero pad, any alignment, the blob ends with

@@ -7,10 +7,10 @@ import pytest
 from tests import u16_handoff_cases as cases
 
 
-def run(oracle, lane_sim, helpers, cfg, packets, what):
+def run(oracle, lane_sim, helpers, cfg, packets, what, variant=-1):
     blob, offs, sizes = helpers.pack_packets(packets)
     ref = oracle.decode_batch(cfg, blob, offs, sizes, threads=4)
-    got = lane_sim(cfg, blob, offs, sizes, variant=-1, guard=True)
+    got = lane_sim(cfg, blob, offs, sizes, variant=variant, guard=True)
     helpers.assert_same_decode(cfg, ref, got, 4, what)
     return ref
 
@@ -44,4 +44,18 @@ def test_frame_counts_and_mixed_matrix(oracle, synth, lane_sim, helpers, fl):
 def test_damaged_packets(oracle, synth, lane_sim, helpers):
     cfg = oracle.make_config(4096, 16, 2)
     ref = run(oracle, lane_sim, helpers, cfg, cases.damaged_set(synth, cfg, n=36), "damaged")
+    assert (ref[2] != 0).sum() >= 3 and (ref[2] == 0).sum() >= 30
+
+
+@pytest.mark.parametrize("fl", [4096, 1000])
+def test_pair_form_without_a_writer_wave(oracle, synth, lane_sim, helpers, fl):
+    """The same sets through variant -3 (alac_decode_16g's form: no writer wave, int32 U cells): the predictor wave writes the
+    pairs at fixed places in chunks that every lane keeps whole, and a lane whose frames end inside a chunk writes its tail out
+    right behind it."""
+    cfg = oracle.make_config(fl, 16, 2)
+    ref = run(oracle, lane_sim, helpers, cfg, cases.frame_count_set(synth, cfg, n=64), "frame counts fl %d" % fl, variant=-3)
+    assert (ref[2] == 0).all() and len(np.unique(ref[1])) >= 10
+    run(oracle, lane_sim, helpers, cfg, cases.all_short_set(synth, cfg), "short packets fl %d" % fl, variant=-3)
+    run(oracle, lane_sim, helpers, cfg, cases.mixed_matrix_set(synth, cfg, n=32), "mixed matrix fl %d" % fl, variant=-3)
+    ref = run(oracle, lane_sim, helpers, cfg, cases.damaged_set(synth, cfg, n=36), "damaged fl %d" % fl, variant=-3)
     assert (ref[2] != 0).sum() >= 3 and (ref[2] == 0).sum() >= 30
