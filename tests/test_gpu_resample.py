@@ -1,9 +1,13 @@
 """alacgpu_resample_device on the GPU: bit for bit what the host build of the same header (tests/host_sim/resample_sim.cpp)
 writes, over whole sentinel-filled buffers, and within the float32 dot-product bound of the numpy float64 restatement
 (tests/resample_ref.py) run on the table the handle reports as its own; and the Python entries over it: resample(),
-load(sample_rate=) and load_clips(sample_rate=) on files of different rates.
+load(sample_rate=) and load_clips(sample_rate=) on files of different rates. The same over other filter widths, rolloffs, upsampling
+pairs and every tile_out (rr.CASES) within the running-error bound of the chain; impulses, which come out as single table entries;
+denormals, huge values, -0.0, infinities and NaNs; and host/resampler.hpp through tests/host_sim/host_shim.cpp.
 
 No test provokes a fault: the arguments the entry refuses are refused on the host, before a launch."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -27,7 +31,7 @@ def sim():
     return rr.build_resample_sim()
 
 
-def host_image(S, orig, new, x, in_off, out_off):
+def host_image(S, orig, new, x, in_off, out_off, W=6, rolloff=0.99):
     """The host build's whole output buffer for the layout of rr.layout (uint32), as tests/test_resample_host.py runs it."""
     rows, T = x.shape
     frames = rr.out_frames(orig, new, T)
@@ -39,7 +43,7 @@ def host_image(S, orig, new, x, in_off, out_off):
     img[:] = rr.SENTINEL
     for r in range(rows):
         src[in_lead + r * in_stride: in_lead + r * in_stride + T] = x[r].view(np.uint32)
-    assert S.resample_sim_run(orig, new, 6, 0.99, src.ctypes.data + 4 * in_lead, in_stride, rows, T, img.ctypes.data + 4 * out_lead,
+    assert S.resample_sim_run(orig, new, W, rolloff, src.ctypes.data + 4 * in_lead, in_stride, rows, T, img.ctypes.data + 4 * out_lead,
                               out_stride, 0) == 0
     return img.copy()
 
@@ -78,6 +82,7 @@ def test_device_equals_the_host_build_bit_for_bit(torch, pkg, sim, orig, new):
                 x = rr.signal(rng, rows, T)
                 ref = rr.resample64(x, orig, new, h=plan["h"], first=plan["first"])
                 lim = rr.bound(plan["h"], plan["first"], x, orig, new)
+                run = rr.running_bound(plan["h"], plan["first"], x, orig, new)
                 for in_off in range(4):
                     for out_off in range(4):
                         img, lead, stride, frames = device_image(torch, rs, orig, new, x, in_off, out_off)
@@ -89,7 +94,120 @@ def test_device_equals_the_host_build_bit_for_bit(torch, pkg, sim, orig, new):
                                                  % (rows, T, in_off, out_off, bad[0], lead, stride, img[bad[0]], want[bad[0]], len(bad)))
                         got = np.stack([img[lead + r * stride: lead + r * stride + frames] for r in range(rows)]).view(np.float32)
                         assert (np.abs(got.astype(np.float64) - ref) <= lim).all()
+                        assert (np.abs(got.astype(np.float64) - ref) <= run).all(), "above the running bound"
         assert rs.last_ms() > 0
+
+
+def assert_same_image(img, want, what, lead, stride):
+    if not np.array_equal(img, want):
+        bad = np.nonzero(img != want)[0]
+        raise AssertionError("%s: element %d of the buffer (rows start at %d, stride %d): got %#x, want %#x (%d differ)"
+                             % (what, bad[0], lead, stride, img[bad[0]], want[bad[0]], len(bad)))
+
+
+@pytest.mark.parametrize("orig,new,W,rolloff", rr.CASES)
+def test_device_equals_the_host_build_for_other_parameters(torch, pkg, sim, orig, new, W, rolloff):
+    """rr.CASES: upsampling pairs, other lowpass_filter_width and rolloff values, tile_out 1 024, 512, 256, 128 and 64, the
+    table of 22 051 phases, 2 to 1 551 taps; lengths above the filter's width, a row of values over nine decades, the four
+    offset pairs of rr.OFFSETS. The whole buffer equals the host build's, the rows lie within the running bound."""
+    rng = np.random.default_rng(orig + 3 * new + W)
+    paths = set()
+    with pkg.NewResampler(orig, new, 0, W, rolloff) as rs:
+        plan = rs.plan()
+        info, h32, first = rr.sim_plan(sim, orig, new, W, rolloff)
+        assert {k: plan[k] for k in info} == info and info["tile_out"] == rr.TILE_OUT.get((orig, new, W, rolloff), 1024)
+        assert np.array_equal(plan["h"].view(np.uint32), h32.view(np.uint32)) and np.array_equal(plan["first"], first)
+        for rows in (1, 5):
+            for T in [T for T in rr.sweep_frames(info, orig, new) if T > info["width"]]:
+                assert rs.out_frames(T) == rr.out_frames(orig, new, T)
+                x = rr.signal(rng, rows, T)
+                if rows > 1:
+                    x[1] = (rng.standard_normal(T) * np.exp(rng.uniform(-20.0, 0.0, T))).astype(np.float32)
+                ref = rr.resample64(x, orig, new, W, rolloff, h=plan["h"], first=plan["first"])
+                run = rr.running_bound(plan["h"], plan["first"], x, orig, new, W, rolloff)
+                for out_off, in_off in rr.OFFSETS:
+                    img, lead, stride, frames = device_image(torch, rs, orig, new, x, in_off, out_off)
+                    assert_same_image(img, host_image(sim, orig, new, x, in_off, out_off, W, rolloff),
+                                      "rows %d T %d offsets %d/%d" % (rows, T, in_off, out_off), lead, stride)
+                    got = np.stack([img[lead + r * stride: lead + r * stride + frames] for r in range(rows)]).view(np.float32)
+                    err = np.abs(got.astype(np.float64) - ref)
+                    assert (err <= run).all(), "rows %d T %d: error %g above the running bound %g" % (
+                        rows, T, err.flat[np.argmax(err - run)], run.flat[np.argmax(err - run)])
+                    paths |= rr.chain_paths(info["tile_out"], rows, frames, out_off)
+    print("%d -> %d W %d rolloff %g: tile_out %d, chains per work item %s" % (orig, new, W, rolloff, info["tile_out"], sorted(paths)))
+
+
+@pytest.mark.parametrize("orig,new,W,rolloff", [(44100, 16000, 6, 0.99), (2, 3, 6, 0.99), (192000, 8000, 6, 0.99), (16000, 44100, 6, 0.99),
+                                                (44100, 16000, 64, 0.9475), (3, 1, 6, 1.0)])
+def test_device_impulses_come_out_as_single_table_entries(torch, pkg, orig, new, W, rolloff):
+    """tests/test_resample_host.py's impulse test on the device: 1.0 (and -0.5) every 2 * width + o + 1 frames, +0.0 elsewhere,
+    over three tiles; every output is one entry of the handle's table (times -0.5) or +0.0 at the place the definition gives
+    it, the whole buffer compared as uint32."""
+    with pkg.NewResampler(orig, new, 0, W, rolloff) as rs:
+        plan = rs.plan()
+        info = {k: plan[k] for k in ("o", "n", "width", "taps", "tile_out")}
+        for amp in (1.0, -0.5):
+            x, offsets = rr.impulse_rows(info, orig, new, W, rolloff, amp)
+            want = rr.impulse_expected(plan["h"], plan["first"], offsets, x.shape[1], orig, new, W, rolloff, amp)
+            assert want.shape[1] >= 3 * info["tile_out"] and np.count_nonzero(want) > 0
+            for out_off, in_off in ((0, 0), (3, 1)):
+                img, lead, stride, frames = device_image(torch, rs, orig, new, x, in_off, out_off)
+                assert_same_image(img, rr.expected_image(want, img.size, lead, stride), "amplitude %g offsets %d/%d" % (amp, in_off, out_off),
+                                  lead, stride)
+
+
+def test_other_float_values(torch, pkg, sim):
+    """Denormals, values up to FLT_MAX / 4, -0.0, an infinity and a NaN (rr.special_rows), down and up: the device equals the
+    host build bit for bit — denormal table-times-input products and sums are kept, not flushed — except that where the host
+    build has a NaN the device has one too, whatever its payload."""
+    for orig, new in ((44100, 16000), (2, 3)):
+        with pkg.NewResampler(orig, new) as rs:
+            x = rr.special_rows(np.random.default_rng(orig), 3001)
+            for out_off, in_off in ((0, 0), (1, 3)):
+                img, lead, stride, frames = device_image(torch, rs, orig, new, x, in_off, out_off)
+                want = host_image(sim, orig, new, x, in_off, out_off)
+                rows = np.stack([want[lead + r * stride: lead + r * stride + frames] for r in range(len(x))]).view(np.float32)
+                sub = np.abs(rows[0][rows[0] != 0]) < np.float32(2.0 ** -126)
+                assert sub.sum() > 100, "the denormal row has no denormal outputs on the host"
+                assert np.isfinite(rows[:3]).all() and np.abs(rows[1]).max() > 1e37
+                nan = np.isnan(want.view(np.float32))
+                assert 0 < nan.sum() < 200 and np.isinf(rows[3]).any()
+                assert np.isnan(img.view(np.float32)[nan]).all(), "a NaN of the host build is none on the device"
+                assert_same_image(np.where(nan, 0, img), np.where(nan, 0, want), "%d -> %d offsets %d/%d" % (orig, new, in_off, out_off),
+                                  lead, stride)
+
+
+def test_cpp_resampler(torch, pkg, sim):
+    """host/resampler.hpp (alac::Resampler: OutFrames, Plan, ResampleDevice, LastMs) through the ctypes shim: the bits and the
+    plan of the Python handle, and std::invalid_argument for equal rates."""
+    from tests import test_container as tc
+    L = tc._build_shim(True, pkg)
+    L.shim_resample.restype = ctypes.c_long
+    vp, u32, sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t
+    L.shim_resample.argtypes = [u32, u32, u32, ctypes.c_double, vp, sz, sz, sz, vp, sz, vp, vp, vp, sz, vp, sz, vp]
+    L.shim_last_error.restype = ctypes.c_char_p
+    orig, new, W, rolloff, rows, T = 48000, 44100, 8, 0.95, 3, 2500
+    x = torch.from_numpy(rr.signal(np.random.default_rng(8), rows, T)).to("cuda:0")
+    with pkg.NewResampler(orig, new, 0, W, rolloff) as rs:
+        plan = rs.plan()
+        want = rs(x)
+    frames = want.shape[1]
+    out = torch.full((rows, frames + 1), -7.0, dtype=torch.float32, device="cuda:0")
+    of, ms = ctypes.c_uint64(0), ctypes.c_float(-1.0)
+    info = np.zeros(5, np.uint32)
+    h, first = np.zeros_like(plan["h"]), np.zeros_like(plan["first"])
+    torch.cuda.synchronize()
+    rc = L.shim_resample(orig, new, W, rolloff, x.data_ptr(), T, rows, T, out.data_ptr(), frames + 1, ctypes.byref(of), info.ctypes.data,
+                         h.ctypes.data, h.size, first.ctypes.data, first.size, ctypes.byref(ms))
+    assert rc == 0, L.shim_last_error()
+    assert of.value == frames == rr.out_frames(orig, new, T) and ms.value > 0
+    assert [int(v) for v in info] == [plan[k] for k in ("o", "n", "width", "taps", "tile_out")]
+    assert np.array_equal(h.view(np.uint32), plan["h"].view(np.uint32)) and np.array_equal(first, plan["first"])
+    assert torch.equal(out[:, :frames].view(torch.int32), want.view(torch.int32)) and bool((out[:, frames] == -7.0).all())
+    rc = L.shim_resample(orig, orig, W, rolloff, x.data_ptr(), T, rows, T, out.data_ptr(), frames + 1, ctypes.byref(of), info.ctypes.data,
+                         h.ctypes.data, h.size, first.ctypes.data, first.size, ctypes.byref(ms))
+    assert rc == -6 and b"no resampling plan" in L.shim_last_error()
+    assert bool((out[:, frames] == -7.0).all()) and torch.equal(out[:, :frames].view(torch.int32), want.view(torch.int32))
 
 
 def test_small_inputs_and_no_work(torch, pkg, sim):

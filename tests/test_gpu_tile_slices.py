@@ -1,0 +1,184 @@
+"""The second launch of the four tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
+alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip) and alac_wave_pack (k_wavepack.hip). Each launch gets the slice's
+first tile as first_tile; only a batch of more than 2^22 tiles has a second slice, and a launch that lost its first_tile would
+corrupt such batches alone, silently.
+
+Every test runs N = 2^22 + 4 099 items of one tile each, so the second launch starts at first_tile = 2^22 and has 4 099
+workgroups. The items' content cycles with period 7 (the clips' with 35), and 2^22 = 2 mod 7 (9 mod 35): a slice that
+started at item 0 again, or that read its inputs from the batch's start, would not continue the cycle. The expectation is that
+of the 7 (35) items, from the host build or the numpy restatement, repeated; it is compared on the device, and the sentinels in
+front of and behind the tensor must be intact. The largest test holds about 150 MB of device memory.
+
+No test provokes a fault: every pass gets buffers of the sizes its entry asks for."""
+import numpy as np
+import pytest
+
+from tests import clip_ref as cr
+from tests import resample_ref as rr
+from tests import wave_ref as wr
+from tests import wavepack_ref as pr
+
+pytestmark = pytest.mark.gpu
+
+SLICE = 1 << 22
+N = SLICE + 4099
+LEAD, TAIL = 9, 8  # elements in front of and behind a tensor: it starts one element behind a 16-byte boundary
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    if not t.cuda.is_available():
+        pytest.fail("gpu-marked test on a machine without a GPU")
+    return t
+
+
+def to_dev(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def cycled(torch, block, n):
+    """The rows of block [period, k] repeated to n rows, on the device."""
+    return to_dev(torch, block).repeat(-(-n // block.shape[0]), 1)[:n].contiguous()
+
+
+def assert_cycle(torch, body, row, what):
+    """body (1-D, on the device) is `row` (numpy, one period) over and over, the last period cut short."""
+    row = to_dev(torch, row.reshape(-1))
+    period = row.numel()
+    full = body.numel() // period
+    bad = torch.nonzero((body[:full * period].view(full, period) != row).any(dim=1))[:4].flatten().tolist()
+    assert not bad, "%s: periods %s of %d elements differ from the expectation" % (what, bad, period)
+    rest = body.numel() - full * period
+    assert torch.equal(body[full * period:], row[:rest]), "%s: the last, short period differs" % what
+
+
+def sentinel_buffer(torch, elems, fill, dtype):
+    buf = torch.full((LEAD + elems + TAIL,), fill, dtype=dtype, device="cuda:0")
+    assert buf.data_ptr() % 16 == 0
+    return buf
+
+
+def assert_guards(buf, elems, fill):
+    assert bool((buf[:LEAD] == fill).all()) and bool((buf[LEAD + elems:] == fill).all()), "a sentinel around the tensor is gone"
+
+
+def test_second_launch_of_alac_resample_rows(torch, pkg):
+    """N rows of 2 frames, 2 -> 3: 3 output frames, tiles_per_row = 1, so tile = row and the second launch has first_tile =
+    2^22. Row r is class r % 7; the expectation is the host build's output for the 7 rows.
+
+    A launch that ignored first_tile would resample rows 0 .. 4 098 again and leave the rows from 2^22 on unwritten (the
+    sentinel); one that wrote to the slice's rows but read from the batch's start would give row 2^22 + j the output of row
+    j, whose class j % 7 is not (2^22 + j) % 7."""
+    sim = rr.build_resample_sim()
+    orig, new, T = 2, 3, 2
+    frames = rr.out_frames(orig, new, T)
+    rows7 = np.random.default_rng(22).uniform(-1, 1, (7, T)).astype(np.float32)
+    rows7[3] = [1.0, -1.0]
+    want7 = np.zeros((7, frames), np.float32)
+    assert sim.resample_sim_run(orig, new, 6, 0.99, rows7.ctypes.data, T, 7, T, want7.ctypes.data, frames, 0) == 0
+    assert frames == 3 and len({w.tobytes() for w in want7}) == 7
+    x = cycled(torch, rows7, N)
+    fill = rr.SENTINEL - (1 << 32)
+    buf = sentinel_buffer(torch, N * frames, fill, torch.int32)
+    torch.cuda.synchronize()
+    with pkg.NewResampler(orig, new) as rs:
+        assert N * -(-(frames + 3) // rs.plan()["tile_out"]) > SLICE
+        rs.resample_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, frames, sync=True)
+    assert_cycle(torch, buf[LEAD:LEAD + N * frames], want7.view(np.int32), "rows")
+    assert_guards(buf, N * frames, fill)
+
+
+def test_second_launch_of_alac_clips_gather(torch, pkg):
+    """N clips of 3 frames out of 7 raw 16-bit mono slots of 32 frames (no decode in front): tiles_per_clip = 1, so tile = clip
+    and the second launch has first_tile = 2^22. begin[j] is a function of j % 35 (clips inside a slot, over slot boundaries
+    and over the grid's end); the expectation is clip_ref.ref_clips for the 35 clips.
+
+    A launch that ignored first_tile would gather clips 0 .. 4 098 again and leave the clips from 2^22 on unwritten; one that
+    took begin[] from the batch's start would give clip 2^22 + j the frames of clip j, whose begin differs since 2^22 = 9 mod
+    35. valid[] and clip_status[] come from alac_clips_meta, which is one launch: they must agree all the same."""
+    fl, L, slots = 32, 3, 7
+    rng = np.random.default_rng(35)
+    pcm = rng.integers(-32768, 32768, (slots, fl)).astype("<i2").view(np.uint8).reshape(slots, 2 * fl)
+    frames = np.full(slots, fl, np.uint32)
+    status = np.zeros(slots, np.int32)
+    begin35 = [(k * 13) % (slots * fl) for k in range(33)] + [slots * fl - 2, slots * fl - 1]  # the last two: over the grid's end
+    assert len(set(begin35)) == 35 and max(begin35) + L > slots * fl and any(b % fl > fl - L for b in begin35)
+    ref, valid35, cstat35 = cr.ref_clips(pcm, frames, status, fl, 16, 1, wr.FLOAT, begin35, [slots] * 35, L)
+    assert sorted(set(valid35.tolist())) == [1, 2, 3] and not cstat35.any()
+    d_pcm, d_fr, d_st = to_dev(torch, pcm), to_dev(torch, frames.view(np.int32)), to_dev(torch, status)
+    d_begin = cycled(torch, np.array(begin35, np.int64)[:, None], N).flatten()
+    d_limit = torch.full((N,), slots, dtype=torch.int64, device="cuda:0")
+    fill = wr.SENTINEL - (1 << 32)
+    buf = sentinel_buffer(torch, N * L, fill, torch.int32)
+    d_valid = torch.full((N,), -1, dtype=torch.int32, device="cuda:0")
+    d_cst = torch.full((N,), -1, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    with pkg.NewPacketDecoder(pkg.PacketConfig(FrameLength=fl, BitDepth=16, NumChannels=1)) as dec:
+        dec.clips_device(d_pcm.data_ptr(), 2 * fl, d_fr.data_ptr(), d_st.data_ptr(), slots, d_begin.data_ptr(), d_limit.data_ptr(), N, L,
+                         wr.FLOAT, buf.data_ptr() + 4 * LEAD, L, L, d_valid.data_ptr(), d_cst.data_ptr(), sync=True)
+    assert_cycle(torch, buf[LEAD:LEAD + N * L], ref.view(np.int32), "clips")
+    assert_guards(buf, N * L, fill)
+    assert_cycle(torch, d_valid, valid35.view(np.int32), "valid")
+    assert not bool(d_cst.any())
+
+
+@pytest.mark.parametrize("wtype", [wr.FLOAT, wr.INT], ids=["float", "int"])
+@pytest.mark.parametrize("layout", [wr.STREAM, wr.PACKETS], ids=["stream", "packets"])
+def test_second_launch_of_alac_wave_convert(torch, pkg, layout, wtype):
+    """N raw 16-bit mono slots of one frame (FrameLength 1): tiles_per_packet = 1, so tile = packet and the second launch has
+    first_tile = 2^22. Slot i is class i % 7; classes 2 and 5 have frames = 0, so that in the stream layout a packet's column
+    is starts[i] = 5 * (i / 7) + (the frames of the classes below i % 7) and not i.
+
+    A launch that ignored first_tile would convert packets 0 .. 4 098 again and leave the columns of the packets from 2^22 on
+    unwritten; one that took its slot, frames[] or starts[] from the batch's start would write packet j's sample (class j % 7,
+    not (2^22 + j) % 7) or write it to packet j's column."""
+    stride = 16
+    rng = np.random.default_rng(7)
+    slots7 = rng.integers(0, 256, (7, stride), dtype=np.uint8)  # the bytes behind a slot's one sample are garbage
+    slots7[:, :2] = np.array([-32768, 32767, 77, -1, 1, -300, 12345], "<i2").view(np.uint8).reshape(7, 2)
+    frames7 = np.array([1, 1, 0, 1, 1, 0, 1], np.uint32)
+    s_ref, starts7 = wr.ref_stream(slots7, frames7, None, 1, 16, 1, wtype)
+    p_ref = wr.ref_packets(slots7, frames7, None, 1, 16, 1, wtype)
+    assert s_ref.shape == (1, 5) and int(starts7[7]) == 5 and len(set(p_ref.flatten().tolist())) == 6
+    total = 5 * (N // 7) + int(starts7[N % 7])
+    d_pcm = torch.cat([cycled(torch, slots7, N).flatten(), torch.zeros(64, dtype=torch.uint8, device="cuda:0")])
+    d_fr = cycled(torch, frames7.view(np.int32)[:, None], N).flatten()
+    fill = wr.SENTINEL - (1 << 32)
+    buf = sentinel_buffer(torch, N, fill, torch.int32)
+    d_starts = torch.full((N + 1,), -1, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    with pkg.NewPacketDecoder(pkg.PacketConfig(FrameLength=1, BitDepth=16, NumChannels=1)) as dec:
+        dec.waveform_device(d_pcm.data_ptr(), stride, d_fr.data_ptr(), None, N, layout, wtype, buf.data_ptr() + 4 * LEAD,
+                            N if layout == wr.STREAM else 1, 0 if layout == wr.STREAM else 1, d_starts.data_ptr(), sync=True)
+    i = torch.arange(N + 1, dtype=torch.int64, device="cuda:0")
+    want_starts = (i // 7) * 5 + to_dev(torch, starts7[:7].astype(np.int64))[i % 7]
+    assert torch.equal(d_starts, want_starts), "starts differ from the closed form at %s" % torch.nonzero(d_starts != want_starts)[:4].flatten().tolist()
+    if layout == wr.STREAM:
+        assert_cycle(torch, buf[LEAD:LEAD + total], s_ref.view(np.int32), "stream")
+        assert bool((buf[LEAD + total:] == fill).all()) and bool((buf[:LEAD] == fill).all())
+    else:
+        assert_cycle(torch, buf[LEAD:LEAD + N], p_ref.view(np.int32), "packets")
+        assert_guards(buf, N, fill)
+
+
+def test_second_launch_of_alac_wave_pack(torch, pkg):
+    """N one-frame clips of a float32 waveform in the packets layout (FrameLength 1, 16-bit mono): one segment per clip and
+    tiles_per_seg = 1, so tile = clip and the second launch has first_tile = 2^22. Clip i is class i % 7; class 2 is 1.5, which
+    saturates, so the clipped count is the number of clips of class 2.
+
+    A launch that ignored first_tile would pack clips 0 .. 4 098 again, leave the samples from 2^22 on unwritten and count the
+    saturated ones among the first 4 099 twice; one that read the waveform from the batch's start would write clip j's sample
+    (class j % 7, not (2^22 + j) % 7)."""
+    x7 = np.array([0.5, -0.25, 1.5, -1.0, 3.0517578125e-05, 0.999, -0.7], np.float32)
+    ref, clipped7 = pr.pack_ref(x7[None, :], 16, pr.FLOAT)
+    assert clipped7 == 1 and ref.size == 14 and len({ref[2 * k:2 * k + 2].tobytes() for k in range(7)}) == 7
+    d_wave = cycled(torch, x7[:, None], N).flatten()
+    buf = sentinel_buffer(torch, 2 * N, pr.PCM_SENTINEL, torch.uint8)
+    d_clip = torch.full((1,), 0xDEAD, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    with pkg.NewPacketEncoder(pkg.PacketConfig(FrameLength=1, BitDepth=16, NumChannels=1)) as enc:
+        enc.pcm_from_waveform_device(d_wave.data_ptr(), pr.PACKETS, pr.FLOAT, 1, 1, N, buf.data_ptr() + LEAD, d_clip.data_ptr(), sync=True)
+    assert_cycle(torch, buf[LEAD:LEAD + 2 * N], ref, "PCM")
+    assert_guards(buf, 2 * N, pr.PCM_SENTINEL)
+    assert int(d_clip.item()) == N // 7 + (1 if N % 7 > 2 else 0)
