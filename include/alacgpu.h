@@ -467,6 +467,75 @@ typedef struct alacgpu_resample_info {
 int alacgpu_resampler_plan(const alacgpu_resampler* rs, alacgpu_resample_info* info, float* h_out, size_t h_cap,
                            int32_t* first_out, size_t first_cap);
 
+/*
+ * SPECTROGRAMS: float32 rows -> their power spectrograms or (log-)mel spectrograms, one fused pass on a handle of its own
+ * (k_mel.hip, alac_mel.h; no decoder, encoder or resampler is involved, and their kernels are untouched): what torch.stft
+ * (periodic Hann window, reflect padding), abs()^2, a matmul with torchaudio's melscale_fbanks and a log compute, without the
+ * intermediates. N = n_fft, W = win_length, h = hop_length, K = N / 2 + 1:
+ *     w[n]    = 0.5 - 0.5 cos(2 pi (n - (N - W) / 2) / W) inside the window's W samples at offset (N - W) / 2, else 0
+ *     C[k][n] = w[n] cos(2 pi ((k n) mod N) / N),  S[k][n] = w[n] sin(2 pi ((k n) mod N) / N)     in double, rounded once
+ *     frames  center: F = 1 + T / h for T > N / 2, frame f reads x[f h - N / 2 + n], reflected at both ends (index i < 0 is
+ *             -i, i >= T is 2 (T - 1) - i); otherwise F = 1 + (T - N) / h for T >= N and frame f reads x[f h + n]
+ *     p[k]    = fmaf(im, im, re * re),  re = fmaf(C[k][n], x[n], re), im = fmaf(S[k][n], x[n], im) for n = 0 .. N - 1 from +0.0f
+ *     mel[m]  = fmaf chain over q < taps of fbw[m][q] * p[first[m] + q] from +0.0f: the run of filter m's weights that are
+ *               not zero, in a window of taps (the widest run) clamped into [0, K)
+ *     log     v <= floor ? float(s log(floor)) : s * log(v); s = 10 and log10 for ALACGPU_MEL_LOG_DB
+ * Up to the log every build gives the same bits; the device's log differs from libm's in the last places.
+ * The filterbank is melscale_fbanks(K, f_min, f_max, n_mels, sample_rate, norm, mel_scale) evaluated in double, its two outer
+ * points f_min and f_max themselves. Power (|X|^2) only; no top_db and no per-row maximum: those stay with the caller.
+ * alacgpu_mel_create is ALACGPU_E_ARG, before any HIP call, when no plan can be built: n_fft outside [2, 2048], win_length
+ * outside [1, n_fft], hop_length 0, sample_rate 0, center or norm above 1, a mel_scale or log outside its values, floor not a
+ * positive float32; with a mel scale n_mels outside [1, 4096] or not 0 <= f_min < f_max; with ALACGPU_MEL_SCALE_NONE (the
+ * power spectrogram itself is the output) n_mels or norm not 0; or four frames that do not fit 64 KB of LDS. The handle owns
+ * a stream, an event pair and the tables on the device; it is single-caller, like a decoder.
+ */
+enum { ALACGPU_MEL_SCALE_NONE = 0, ALACGPU_MEL_SCALE_HTK = 1, ALACGPU_MEL_SCALE_SLANEY = 2 };
+enum { ALACGPU_MEL_LOG_NONE = 0, ALACGPU_MEL_LOG_LN = 1, ALACGPU_MEL_LOG_LOG10 = 2, ALACGPU_MEL_LOG_DB = 3 };
+typedef struct alacgpu_mel_config {
+    uint32_t sample_rate;
+    uint32_t n_fft;
+    uint32_t win_length; /* 1 .. n_fft */
+    uint32_t hop_length; /* >= 1 */
+    double f_min, f_max; /* Hz; read with a mel scale only */
+    uint32_t n_mels;     /* 0 with ALACGPU_MEL_SCALE_NONE */
+    uint32_t center;     /* 1: frames centred on f * hop_length, reflect padding; 0: frames start there */
+    uint32_t norm;       /* 0 none, 1 slaney */
+    uint32_t mel_scale;  /* ALACGPU_MEL_SCALE_* */
+    uint32_t log;        /* ALACGPU_MEL_LOG_* */
+    uint32_t reserved0;  /* 0 */
+    double floor;        /* > 0; read with a log only, but checked always */
+} alacgpu_mel_config;
+typedef struct alacgpu_mel alacgpu_mel;
+int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel** out);
+void alacgpu_mel_destroy(alacgpu_mel* mel);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernels (valid after a sync). */
+void* alacgpu_mel_stream(alacgpu_mel* mel);
+int alacgpu_mel_synchronize(alacgpu_mel* mel);
+int alacgpu_mel_last_ms(alacgpu_mel* mel, float* ms);
+/* F for rows of in_frames samples; 0 for a NULL handle, where no frame exists, or above 2^61 samples. */
+uint64_t alacgpu_mel_out_frames(const alacgpu_mel* mel, uint64_t in_frames);
+/*
+ * rows rows of in_frames float32 samples, row r at d_in + r * in_row_stride (strides in elements), -> [rows][bins][F], F =
+ * alacgpu_mel_out_frames(mel, in_frames), bins = n_mels or K: element (r, b, f) at d_out + r * out_row_stride + b *
+ * out_bin_stride + f. Exactly those elements are written, nothing in the gaps the strides leave; nothing outside [0, in_frames)
+ * of an input row is read. rows = 0 or F = 0 succeeds and touches nothing. ALACGPU_E_ARG before any HIP call: a NULL handle;
+ * with work to do a NULL d_in or d_out, a base that is not 4-byte aligned, in_row_stride < in_frames, out_bin_stride < F,
+ * out_row_stride < (bins - 1) * out_bin_stride + F, or sizes whose products overflow. Every 4-byte-aligned base and every
+ * stride gives the same values. Asynchronous on the handle's stream unless sync != 0: the input must be complete, or ordered
+ * on that stream, before the call (the stream is non-blocking: it does not order against torch's by itself).
+ */
+int alacgpu_mel_device(alacgpu_mel* mel, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
+                       size_t out_row_stride, size_t out_bin_stride, int sync);
+/* The plan the handle's kernel uses: its numbers, and (where the pointers are not NULL and the capacities, counted in
+ * entries, suffice) the host copies of the basis [2][n_freqs][n_fft] (C, then S), of the filterbank windows fbw[n_mels][taps]
+ * and of first[n_mels]. taps is 0 without a mel stage. */
+typedef struct alacgpu_mel_info {
+    uint32_t n_fft, win_length, hop_length, n_freqs, n_mels, taps, bins, tile_frames, lds_bytes;
+} alacgpu_mel_info;
+int alacgpu_mel_plan(const alacgpu_mel* mel, alacgpu_mel_info* info, float* basis_out, size_t basis_cap, float* fb_out,
+                     size_t fb_cap, int32_t* first_out, size_t first_cap);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

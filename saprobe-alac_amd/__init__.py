@@ -33,6 +33,7 @@ __all__ = [
     "PacketConfig", "PCMFormat", "PacketDecoder", "NewPacketDecoder", "PacketEncoder", "NewPacketEncoder", "ParseMagicCookie",
     "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load", "save",
     "load_clips", "Resampler", "NewResampler", "resample",
+    "MelSpectrogram", "NewMelSpectrogram", "mel_spectrogram", "spectrogram", "whisper_log_mel",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -271,6 +272,16 @@ _EXPORTS = {
                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]),
     "alacgpu_resampler_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                               ctypes.c_size_t]),
+    "alacgpu_mel_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_mel_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_mel_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_mel_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_mel_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_mel_out_frames": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "alacgpu_mel_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]),
+    "alacgpu_mel_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                        ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -967,6 +978,203 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
     if key not in _RESAMPLERS:
         _RESAMPLERS[key] = Resampler(orig_freq, new_freq, device, lowpass_filter_width, rolloff)
     return _RESAMPLERS[key](waveform)
+
+
+# ---- MelSpectrogram (new: torch.stft + |.|^2 + torchaudio's melscale_fbanks + log, one fused pass on the device) --------
+class MelConfig(ctypes.Structure):
+    """alacgpu_mel_config (include/alacgpu.h)."""
+
+    _fields_ = [("sample_rate", ctypes.c_uint32), ("n_fft", ctypes.c_uint32), ("win_length", ctypes.c_uint32),
+                ("hop_length", ctypes.c_uint32), ("f_min", ctypes.c_double), ("f_max", ctypes.c_double), ("n_mels", ctypes.c_uint32),
+                ("center", ctypes.c_uint32), ("norm", ctypes.c_uint32), ("mel_scale", ctypes.c_uint32), ("log", ctypes.c_uint32),
+                ("reserved0", ctypes.c_uint32), ("floor", ctypes.c_double)]
+
+
+class MelInfo(ctypes.Structure):
+    """alacgpu_mel_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n_fft", "win_length", "hop_length", "n_freqs", "n_mels", "taps", "bins",
+                                               "tile_frames", "lds_bytes")]
+
+
+_MEL_SCALES = {"htk": 1, "slaney": 2}
+_MEL_LOGS = {None: 0, "ln": 1, "log10": 2, "db": 3}
+
+
+def _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor):
+    """The arguments of the Python entries -> MelConfig, defaults resolved; ValueError for what is no number of its kind or no
+    name of an enum (what the numbers may be is the plan's to say)."""
+    for v in (sample_rate, n_fft) + tuple(u for u in (win_length, hop_length, n_mels) if u is not None):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("sample_rate, n_fft, win_length, hop_length and n_mels are integers in [0, 2^32)")
+    if norm not in (None, "slaney"):
+        raise ValueError("norm is None or 'slaney', not %r" % (norm,))
+    if log not in _MEL_LOGS:
+        raise ValueError("log is None, 'ln', 'log10' or 'db', not %r" % (log,))
+    if n_mels is not None and mel_scale not in _MEL_SCALES:
+        raise ValueError("mel_scale is 'htk' or 'slaney', not %r" % (mel_scale,))
+    if n_mels is not None and int(n_mels) == 0:
+        raise ValueError("n_mels is at least 1 (None gives the power spectrogram itself)")
+    win = int(n_fft) if win_length is None else int(win_length)
+    hop = win // 2 if hop_length is None else int(hop_length)
+    c = MelConfig()
+    c.sample_rate, c.n_fft, c.win_length, c.hop_length = int(sample_rate), int(n_fft), win, hop
+    c.f_min = float(f_min)
+    c.f_max = float(int(sample_rate) / 2 if f_max is None else f_max)
+    c.center = 1 if center else 0
+    c.log, c.floor = _MEL_LOGS[log], float(floor)
+    if n_mels is not None:
+        c.n_mels, c.norm, c.mel_scale = int(n_mels), 1 if norm == "slaney" else 0, _MEL_SCALES[mel_scale]
+    return c
+
+
+class MelSpectrogram:
+    """float32 rows -> their power spectrograms (n_mels None) or (log-)mel spectrograms on one MI355X (include/alacgpu.h:
+    alacgpu_mel_*): periodic Hann window, reflect padding when centred, |X|^2, torchaudio's melscale_fbanks, s log(max(v,
+    floor)); the tables are built once per handle. ValueError when no plan can be built. Single-caller, bound to one device
+    and one stream."""
+
+    def __init__(self, sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128, center=True,
+                 norm=None, mel_scale="htk", log=None, floor=1e-10, device=0):
+        self._h = ctypes.c_void_p()
+        self._lib = lib()
+        self.config = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor)
+        _check(self._lib.alacgpu_mel_create(device, ctypes.byref(self.config), ctypes.byref(self._h)))
+        self.device = device
+        self.bins = int(n_mels) if n_mels is not None else int(n_fft) // 2 + 1
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.alacgpu_mel_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def out_frames(self, in_frames):
+        """alacgpu_mel_out_frames: 1 + T / hop centred (T > n_fft / 2), 1 + (T - n_fft) / hop otherwise; 0 where no frame exists."""
+        return int(self._lib.alacgpu_mel_out_frames(self._h, int(in_frames)))
+
+    def mel_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, sync=True):
+        """alacgpu_mel_device: raw device pointers (ints), strides in elements. rows rows of in_frames float32 samples ->
+        [rows][bins][out_frames(in_frames)], element (r, b, f) at d_out + r * out_row_stride + b * out_bin_stride + f; exactly
+        those elements are written. Runs on the handle's stream, which does not order against torch's: synchronize the input
+        first."""
+        _check(self._lib.alacgpu_mel_device(self._h, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride,
+                                            1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_mel_plan -> dict: n_fft, win_length, hop_length, n_freqs, n_mels, taps, bins, tile_frames, lds_bytes, and the
+        host copies of the tables the kernel uses: basis [2, n_freqs, n_fft] float32 (C, then S), fb [n_mels, taps] float32 (each
+        filter's window) and first [n_mels] int32 (the bin of each window's first weight)."""
+        info = MelInfo()
+        _check(self._lib.alacgpu_mel_plan(self._h, ctypes.byref(info), None, 0, None, 0, None, 0))
+        basis = np.zeros((2, info.n_freqs, info.n_fft), np.float32)
+        fb = np.zeros((info.n_mels, info.taps), np.float32)
+        first = np.zeros(info.n_mels, np.int32)
+        _check(self._lib.alacgpu_mel_plan(self._h, ctypes.byref(info), basis.ctypes.data, basis.size, fb.ctypes.data, fb.size,
+                                          first.ctypes.data, first.size))
+        out = {k: int(getattr(info, k)) for k, _ in MelInfo._fields_}
+        out.update(basis=basis, fb=fb, first=first)
+        return out
+
+    def last_ms(self):
+        """alacgpu_mel_last_ms: HIP events around the kernels of the last pass."""
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_mel_last_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def synchronize(self):
+        _check(self._lib.alacgpu_mel_synchronize(self._h))
+
+    def __call__(self, waveform):
+        """A float32 tensor [..., T] -> [..., bins, out_frames(T)] on the handle's device (made contiguous, flattened to rows);
+        ValueError where T has no frame."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        T = int(waveform.shape[-1])
+        frames = self.out_frames(T)
+        if not frames:
+            raise ValueError("%d samples have no frame of n_fft %d" % (T, self.config.n_fft))
+        rows = 1
+        for d in waveform.shape[:-1]:
+            rows *= int(d)
+        x = waveform.to(dev).contiguous().reshape(rows, T)
+        out = torch.empty((rows, self.bins, frames), dtype=torch.float32, device=dev)
+        if rows:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            self.mel_device(x.data_ptr(), T, rows, T, out.data_ptr(), self.bins * frames, frames, sync=True)
+        return out.reshape(tuple(waveform.shape[:-1]) + (self.bins, frames))
+
+
+def NewMelSpectrogram(sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128, center=True,
+                      norm=None, mel_scale="htk", log=None, floor=1e-10, device=0):
+    """A MelSpectrogram (context manager); ValueError where no plan can be built."""
+    return MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor, device)
+
+
+_MELS = {}  # (device, every field of the configuration) -> MelSpectrogram: a plan is built once per process
+
+
+def mel_spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128,
+                    center=True, norm=None, mel_scale="htk", log=None, floor=1e-10, device=None):
+    """torchaudio.transforms.MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels=n_mels, center=center,
+    norm=norm, mel_scale=mel_scale)(waveform) with power 2, the periodic Hann window and reflect padding, and optionally s
+    log(max(., floor)) (log: None, "ln", "log10", "db"), in one pass on the device: a float32 tensor [..., T] (CUDA, CPU or
+    numpy; the last two are uploaded) -> [..., n_mels, F] on cuda:`device` (default: the tensor's own device, cuda:0 for a CPU
+    tensor or a numpy array). n_mels None gives the power spectrogram [..., n_fft / 2 + 1, F]. Another dtype, parameters without
+    a plan or a T without a frame raise ValueError. The tables of a (device, parameter set) are built once and kept."""
+    import torch
+    if isinstance(waveform, np.ndarray):
+        if waveform.dtype != np.float32:
+            raise ValueError("waveform must be float32")
+    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
+        raise ValueError("waveform must be a float32 torch tensor or numpy array")
+    if waveform.ndim < 1:
+        raise ValueError("waveform must be [..., T]")
+    c = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor)
+    if isinstance(waveform, np.ndarray):
+        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
+    if device is None:
+        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    key = (device,) + tuple(getattr(c, k) for k, _ in MelConfig._fields_)
+    if key not in _MELS:
+        _MELS[key] = MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log,
+                                    floor, device)
+    return _MELS[key](waveform)
+
+
+def spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_length=None, center=True, log=None, floor=1e-10, device=None):
+    """mel_spectrogram without the mel stage: the power spectrogram [..., n_fft / 2 + 1, F] (torchaudio.transforms.Spectrogram
+    with power 2), sample_rate only naming the handle."""
+    return mel_spectrogram(waveform, sample_rate, n_fft, win_length, hop_length, n_mels=None, center=center, log=log, floor=floor,
+                           device=device)
+
+
+def whisper_post(logmel):
+    """Whisper's post-processing of a log10 mel tensor [..., n_mels, F], in torch ops: drop the last frame, clamp below (the
+    maximum over [n_mels, frames]) - 8, then (x + 4) / 4."""
+    import torch
+    x = logmel[..., :-1]
+    top = x.amax(dim=(-2, -1), keepdim=True)
+    x = torch.maximum(x, top - 8.0)
+    return (x + 4.0) / 4.0
+
+
+def whisper_log_mel(waveform, n_mels=80, device=None):
+    """Whisper's log_mel_spectrogram of 16 kHz audio [..., T] -> [..., n_mels, T / 160]: the pass at n_fft 400, hop 160 with the
+    slaney scale and norm and log10 at floor 1e-10, then whisper_post."""
+    return whisper_post(mel_spectrogram(waveform, 16000, 400, 400, 160, 0.0, 8000.0, n_mels, True, "slaney", "slaney", "log10",
+                                        1e-10, device))
 
 
 def NewDecoder(source, device=0, window=1024):

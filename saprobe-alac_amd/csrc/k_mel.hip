@@ -1,0 +1,241 @@
+/*
+ * k_mel.hip — float32 rows -> power or (log-)mel spectrograms: the gfx950 kernel over csrc/alac_mel.h and the mel handle's
+ * entries (one translation unit of libalacgpu.so; nothing here touches the decode, waveform, clip, resample or encode kernels).
+ *
+ * One pass = launches of one kernel on the handle's stream:
+ *   alac_mel_rows  one workgroup per tile (tile_frames consecutive frames of one row): the tile's inputs with 16-byte loads
+ *                  into LDS, reflection and zeros resolved there; every lane the fmaf chains of blocks of 8 frames x 2 bins,
+ *                  frames from LDS, the windowed basis from global memory ([n][bin pair]: a wave reads consecutive 16 bytes);
+ *                  the powers into an LDS tile, the mel chains and the log out of it; the results through LDS into 16-byte
+ *                  stores along time
+ * No matrix instruction, no atomic; everything is written with vector stores.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "alac_host.h"
+#include "alac_mel.h"
+
+using namespace alacmel;
+using alack::set_err;
+
+namespace {
+
+/* alac_mel_rows goes in slices, each far below a dispatch's 2^32 work-items: 2^22 workgroups of 256 */
+constexpr uint64_t kTilesPerLaunch = (uint64_t)1 << 22;
+
+__global__ void __launch_bounds__(kThreads) alac_mel_rows(Params p, uint64_t first_tile) {
+    extern __shared__ __attribute__((aligned(16))) float lds[]; /* the plan's lds_floats */
+    const uint64_t b = first_tile + blockIdx.x;
+    const uint64_t row = b / p.tiles_per_row;
+    if (row >= p.rows) return;
+    const Tile t = make_tile(p, row, b - row * p.tiles_per_row);
+    if (t.count == 0) return;
+    float* ptile = lds + p.a_floats;
+    stage_tile(p, t, lds, threadIdx.x);
+    __syncthreads();
+    dft_tile(p, t, lds, ptile, threadIdx.x);
+    __syncthreads();
+    if (p.n_mels) mel_tile(p, ptile, lds, threadIdx.x); /* the output tile takes the staged inputs' place */
+    else log_tile(p, ptile, threadIdx.x);
+    __syncthreads();
+    if (p.n_mels) store_tile(p, t, lds, p.tile_frames, 1u, threadIdx.x);
+    else store_tile(p, t, ptile, 1u, p.KP, threadIdx.x);
+}
+
+} /* namespace */
+
+namespace alack {
+
+hipError_t mel_launch(hipStream_t stream, const Params& p, uint32_t lds_bytes) {
+    if (p.rows == 0 || p.out_frames == 0) return hipSuccess;
+    const uint64_t tiles = p.rows * p.tiles_per_row;
+    for (uint64_t t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
+        const uint64_t m = tiles - t0 < kTilesPerLaunch ? tiles - t0 : kTilesPerLaunch;
+        hipLaunchKernelGGL(alac_mel_rows, dim3((unsigned)m), dim3(kThreads), lds_bytes, stream, p, t0);
+    }
+    return hipGetLastError();
+}
+
+} /* namespace alack */
+
+/* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
+struct alacgpu_mel {
+    int device = 0;
+    Plan plan;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; /* around the kernels of the last pass */
+    bool timed = false;
+    float* d_bt = nullptr;
+    float* d_fbw = nullptr;
+    int32_t* d_first = nullptr;
+};
+
+namespace {
+void release(alacgpu_mel* r) {
+    (void)hipSetDevice(r->device);
+    if (r->stream) (void)hipStreamSynchronize(r->stream);
+    if (r->d_bt) (void)hipFree(r->d_bt);
+    if (r->d_fbw) (void)hipFree(r->d_fbw);
+    if (r->d_first) (void)hipFree(r->d_first);
+    if (r->ev0) (void)hipEventDestroy(r->ev0);
+    if (r->ev1) (void)hipEventDestroy(r->ev1);
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    delete r;
+}
+
+Config config_of(const alacgpu_mel_config* c) {
+    Config k;
+    k.sample_rate = c->sample_rate;
+    k.n_fft = c->n_fft;
+    k.win_length = c->win_length;
+    k.hop_length = c->hop_length;
+    k.f_min = c->f_min;
+    k.f_max = c->f_max;
+    k.n_mels = c->n_mels;
+    k.center = c->center;
+    k.norm = c->norm;
+    k.mel_scale = c->mel_scale;
+    k.log = c->log;
+    k.floor = c->floor;
+    return k;
+}
+} /* namespace */
+
+extern "C" {
+
+int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel** out) {
+    if (!out || !config) {
+        if (out) *out = nullptr;
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    *out = nullptr;
+    alacgpu_mel* r = new (std::nothrow) alacgpu_mel();
+    if (!r) {
+        set_err("out of memory");
+        return ALACGPU_E_ARG;
+    }
+    if (!make_plan(config_of(config), &r->plan)) {
+        set_err("no spectrogram plan for n_fft %u, win_length %u, hop_length %u at %u Hz, %u mels in [%g, %g) Hz, floor %g: n_fft "
+                "in [2, %u], 1 <= win_length <= n_fft, hop_length >= 1, center and norm 0 or 1, mel_scale 0..2, log 0..3, floor a "
+                "positive float32; with a mel scale 1 <= n_mels <= %u and 0 <= f_min < f_max, without one n_mels and norm 0; and "
+                "four frames within %u bytes of LDS",
+                config->n_fft, config->win_length, config->hop_length, config->sample_rate, config->n_mels, config->f_min,
+                config->f_max, config->floor, kMaxFft, kMaxMels, kLdsFloats * 4u);
+        delete r;
+        return ALACGPU_E_ARG;
+    }
+    r->device = device;
+    const Plan& pl = r->plan;
+    const size_t table = pl.bt.size() * sizeof(float);
+    const size_t fbw = (pl.fbw.empty() ? 1 : pl.fbw.size()) * sizeof(float);
+    const size_t firsts = (pl.first.empty() ? 1 : pl.first.size()) * sizeof(int32_t);
+    hipError_t h = hipSetDevice(device);
+    if (h == hipSuccess) h = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
+    if (h == hipSuccess) h = hipEventCreate(&r->ev0);
+    if (h == hipSuccess) h = hipEventCreate(&r->ev1);
+    if (h == hipSuccess) h = hipMalloc((void**)&r->d_bt, table);
+    if (h == hipSuccess) h = hipMalloc((void**)&r->d_fbw, fbw);
+    if (h == hipSuccess) h = hipMalloc((void**)&r->d_first, firsts);
+    if (h == hipSuccess) h = hipMemcpy(r->d_bt, pl.bt.data(), table, hipMemcpyHostToDevice);
+    if (h == hipSuccess && !pl.fbw.empty()) h = hipMemcpy(r->d_fbw, pl.fbw.data(), pl.fbw.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (h == hipSuccess && !pl.first.empty())
+        h = hipMemcpy(r->d_first, pl.first.data(), pl.first.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (h != hipSuccess) {
+        set_err("spectrogram handle creation failed: %s", hipGetErrorString(h));
+        release(r);
+        return ALACGPU_E_HIP;
+    }
+    *out = r;
+    return ALACGPU_E_OK;
+}
+
+void alacgpu_mel_destroy(alacgpu_mel* r) {
+    if (r) release(r);
+}
+
+void* alacgpu_mel_stream(alacgpu_mel* r) { return r ? (void*)r->stream : nullptr; }
+
+int alacgpu_mel_synchronize(alacgpu_mel* r) {
+    if (!r) return ALACGPU_E_ARG;
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_mel_last_ms(alacgpu_mel* r, float* ms) {
+    if (!r || !ms || !r->timed) {
+        set_err(!r || !ms ? "null argument" : "no spectrogram pass on this handle yet");
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipEventSynchronize(r->ev1));
+    HIP_TRY(hipEventElapsedTime(ms, r->ev0, r->ev1));
+    return ALACGPU_E_OK;
+}
+
+uint64_t alacgpu_mel_out_frames(const alacgpu_mel* r, uint64_t in_frames) {
+    if (!r || in_frames > ((uint64_t)1 << 61)) return 0;
+    return out_frames_of(r->plan.N, r->plan.hop, r->plan.cfg.center, in_frames);
+}
+
+int alacgpu_mel_plan(const alacgpu_mel* r, alacgpu_mel_info* info, float* basis_out, size_t basis_cap, float* fb_out,
+                     size_t fb_cap, int32_t* first_out, size_t first_cap) {
+    if (!r || !info) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    const Plan& pl = r->plan;
+    if ((basis_out && basis_cap < pl.basis.size()) || (fb_out && fb_cap < pl.fbw.size()) || (first_out && first_cap < pl.first.size())) {
+        set_err("capacity below the plan's %zu basis entries / %zu filterbank entries / %zu filters", pl.basis.size(), pl.fbw.size(),
+                pl.first.size());
+        return ALACGPU_E_ARG;
+    }
+    info->n_fft = pl.N;
+    info->win_length = pl.W;
+    info->hop_length = pl.hop;
+    info->n_freqs = pl.K;
+    info->n_mels = pl.n_mels;
+    info->taps = pl.n_mels ? pl.taps : 0u;
+    info->bins = pl.bins;
+    info->tile_frames = pl.tile_frames;
+    info->lds_bytes = pl.lds_floats * 4u;
+    if (basis_out) memcpy(basis_out, pl.basis.data(), pl.basis.size() * sizeof(float));
+    if (fb_out && !pl.fbw.empty()) memcpy(fb_out, pl.fbw.data(), pl.fbw.size() * sizeof(float));
+    if (first_out && !pl.first.empty()) memcpy(first_out, pl.first.data(), pl.first.size() * sizeof(int32_t));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_mel_device(alacgpu_mel* r, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
+                       size_t out_row_stride, size_t out_bin_stride, int sync) {
+    if (!r) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    if (rows == 0 || alacgpu_mel_out_frames(r, in_frames) == 0) {
+        if (rows && in_frames > ((uint64_t)1 << 61)) {
+            set_err("spectrogram: %zu frames are more than one pass takes", in_frames);
+            return ALACGPU_E_ARG;
+        }
+        return ALACGPU_E_OK;
+    }
+    Params p;
+    if (!make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, r->d_bt, r->d_fbw,
+                     r->d_first, &p)) {
+        set_err("spectrogram: a NULL or misaligned buffer, a stride (%zu in, %zu out rows, %zu out bins) below what it spans (%zu "
+                "samples, %u bins of %llu frames), or sizes that overflow", in_row_stride, out_row_stride, out_bin_stride, in_frames,
+                r->plan.bins, (unsigned long long)alacgpu_mel_out_frames(r, in_frames));
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipEventRecord(r->ev0, r->stream));
+    HIP_TRY(alack::mel_launch(r->stream, p, r->plan.lds_floats * 4u));
+    HIP_TRY(hipEventRecord(r->ev1, r->stream));
+    r->timed = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(r->stream));
+    return ALACGPU_E_OK;
+}
+
+} /* extern "C" */
