@@ -472,10 +472,12 @@ int alacgpu_resampler_plan(const alacgpu_resampler* rs, alacgpu_resample_info* i
  * (k_mel.hip, alac_mel.h; no decoder, encoder or resampler is involved, and their kernels are untouched): what torch.stft
  * (periodic Hann window, reflect padding), abs()^2, a matmul with torchaudio's melscale_fbanks and a log compute, without the
  * intermediates. N = n_fft, W = win_length, h = hop_length, K = N / 2 + 1:
- *     w[n]    = 0.5 - 0.5 cos(2 pi (n - (N - W) / 2) / W) inside the window's W samples at offset (N - W) / 2, else 0
+ *     w[n]    = 0.5 - 0.5 cos(2 pi (n - (N - W) / 2) / W) inside the window's W samples at offset (N - W) / 2, else 0; the one
+ *               sample of W = 1 is 1.0, as torch.hann_window(1) is
  *     C[k][n] = w[n] cos(2 pi ((k n) mod N) / N),  S[k][n] = w[n] sin(2 pi ((k n) mod N) / N)     in double, rounded once
- *     frames  center: F = 1 + T / h for T > N / 2, frame f reads x[f h - N / 2 + n], reflected at both ends (index i < 0 is
- *             -i, i >= T is 2 (T - 1) - i); otherwise F = 1 + (T - N) / h for T >= N and frame f reads x[f h + n]
+ *     frames  center: F = 1 + (T - (N & 1)) / h for T > N / 2 (torch.stft's count: N / 2 samples of padding on each side),
+ *             frame f reads x[f h - N / 2 + n], reflected at both ends (index i < 0 is -i, i >= T is 2 (T - 1) - i);
+ *             otherwise F = 1 + (T - N) / h for T >= N and frame f reads x[f h + n]
  *     p[k]    = fmaf(im, im, re * re),  re = fmaf(C[k][n], x[n], re), im = fmaf(S[k][n], x[n], im) for n = 0 .. N - 1 from +0.0f
  *     mel[m]  = fmaf chain over q < taps of fbw[m][q] * p[first[m] + q] from +0.0f: the run of filter m's weights that are
  *               not zero, in a window of taps (the widest run) clamped into [0, K)

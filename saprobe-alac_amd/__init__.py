@@ -1061,7 +1061,8 @@ class MelSpectrogram:
         self.close()
 
     def out_frames(self, in_frames):
-        """alacgpu_mel_out_frames: 1 + T / hop centred (T > n_fft / 2), 1 + (T - n_fft) / hop otherwise; 0 where no frame exists."""
+        """alacgpu_mel_out_frames: 1 + (T - n_fft % 2) / hop centred (T > n_fft / 2; torch.stft's count: it pads n_fft / 2 on each
+        side), 1 + (T - n_fft) / hop otherwise; 0 where no frame exists."""
         return int(self._lib.alacgpu_mel_out_frames(self._h, int(in_frames)))
 
     def mel_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, sync=True):
@@ -1097,8 +1098,8 @@ class MelSpectrogram:
         _check(self._lib.alacgpu_mel_synchronize(self._h))
 
     def __call__(self, waveform):
-        """A float32 tensor [..., T] -> [..., bins, out_frames(T)] on the handle's device (made contiguous, flattened to rows);
-        ValueError where T has no frame."""
+        """A float32 tensor [..., T] -> [..., bins, out_frames(T)] on the handle's device (made contiguous, flattened to rows):
+        1 + (T - n_fft % 2) / hop frames centred, as torch.stft has them. ValueError where T has no frame."""
         import torch
         dev = torch.device("cuda", self.device)
         T = int(waveform.shape[-1])

@@ -6,13 +6,16 @@
  * The definition. N = n_fft in [2, 2048], W = win_length in [1, N], h = hop_length >= 1, K = N / 2 + 1 bins.
  *
  *   window   periodic Hann, hann[j] = 0.5 - 0.5 cos(2 pi j / W) for j < W, at offset (N - W) / 2 within N, zero elsewhere
- *            (torch.stft's centring of a short window): w[n]
+ *            (torch.stft's centring of a short window): w[n]. W = 1 is the one sample 1.0, as torch.hann_window(1) is, not
+ *            the formula's 0.
  *   basis    C[k][n] = w[n] cos(2 pi ((k n) mod N) / N),  S[k][n] = w[n] sin(2 pi ((k n) mod N) / N): the integer reduction
  *            first, (2 pi r) / N, cos, sin and the product in double, each entry rounded to float32 once, +0.0f where w[n] is
  *            0. The window lives in the table: there is no separate multiply.
- *   frames   center: F = 1 + T / h for T > N / 2, frame f reads xr[f h - N / 2 + n], xr[i] = x[-i] for i < 0, x[2 (T - 1) -
- *            i] for i >= T (and +0.0 where that still lies outside [0, T): N odd, T = N / 2 + 1 only); otherwise F = 1 + (T -
- *            N) / h for T >= N and frame f reads x[f h + n]. out_frames(T) is 0 where no frame exists.
+ *   frames   center: F = 1 + (T - (N & 1)) / h for T > N / 2 (torch.stft's 1 + (T + 2 (N / 2) - N) / h: it pads N / 2 on
+ *            each side), frame f reads xr[f h - N / 2 + n], xr[i] = x[-i] for i < 0, x[2 (T - 1) - i] for i >= T. The last
+ *            frame reads up to T + N / 2 - 1, which reflects to T - 1 - N / 2 >= 0: every index of a frame that exists lies
+ *            in [0, T) after one reflection. Otherwise F = 1 + (T - N) / h for T >= N and frame f reads x[f h + n].
+ *            out_frames(T) is 0 where no frame exists.
  *   power    re = im = +0.0f;  for n = 0 .. N - 1:  re = fmaf(C[k][n], xr[n], re);  im = fmaf(S[k][n], xr[n], im)
  *            p[k] = fmaf(im, im, re * re)                                 the product rounded on its own
  *   mel      fb = torchaudio.functional.melscale_fbanks(K, f_min, f_max, n_mels, sample_rate, norm, mel_scale) restated in
@@ -91,7 +94,7 @@ struct Params {
 
 /* F; 0 where no frame exists */
 ALAC_WF_FN uint64_t out_frames_of(uint32_t N, uint32_t hop, uint32_t center, uint64_t T) {
-    if (center) return T > N / 2u ? 1u + T / hop : 0u;
+    if (center) return T > N / 2u ? 1u + (T - (N & 1u)) / hop : 0u;
     return T >= N ? 1u + (T - N) / hop : 0u;
 }
 
@@ -124,7 +127,8 @@ ALAC_WF_FN Tile make_tile(const Params& p, uint64_t row, uint64_t tile) {
     return t;
 }
 
-/* xr[i] of the row x: the reflection of a centred row, +0.0 for what lies outside the row even so */
+/* xr[i] of the row x: the reflection of a centred row. No frame that exists reaches outside [0, T) after it; the frames a tile
+ * stages behind the row's last do, and get +0.0 there (they are computed and never stored). */
 ALAC_WF_FN float sample_at(const Params& p, const float* x, int64_t i) {
     const int64_t T = (int64_t)p.in_frames;
     if (p.center) {
@@ -360,7 +364,7 @@ inline bool make_plan(const Config& c, Plan* out) {
     const double pi = 3.14159265358979323846;
     std::vector<double> w(N, 0.0);
     const uint32_t off = (N - W) / 2u;
-    for (uint32_t j = 0; j < W; j++) w[off + j] = 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W);
+    for (uint32_t j = 0; j < W; j++) w[off + j] = W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W);
     pl.basis.assign((size_t)2 * K * N, 0.0f);
     pl.bt.assign((size_t)N * pl.BP * 4u, 0.0f);
     for (uint32_t k = 0; k < K; k++)

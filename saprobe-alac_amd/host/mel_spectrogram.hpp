@@ -3,7 +3,7 @@
 //
 //   NewMelSpectrogram(config)             -> throws std::invalid_argument where no plan can be built
 //   MelConfig(sample_rate, n_fft, ...)    an alacgpu_mel_config with torchaudio's defaults resolved
-//   MelSpectrogram::OutFrames(T)          1 + T / hop centred, 1 + (T - n_fft) / hop otherwise; 0 where no frame exists
+//   MelSpectrogram::OutFrames(T)          1 + (T - n_fft % 2) / hop centred, 1 + (T - n_fft) / hop otherwise; 0 where no frame exists
 //   MelSpectrogram::MelDevice(...)        float32 rows on the device -> [rows][bins][frames], asynchronous on Stream() unless sync
 //   MelSpectrogram::Plan()                the numbers and the host copies of the tables the kernel uses
 // Header-only; link with -lalacgpu. Every pass runs the HIP kernel: there is no CPU path.

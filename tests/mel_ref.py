@@ -1,9 +1,10 @@
 """The spectrogram pass restated in numpy float64, independently of csrc/alac_mel.h, and the host build of
 that header for the tests.
 
-    K = N / 2 + 1;  w = periodic Hann of W samples at offset (N - W) / 2 within N
+    K = N / 2 + 1;  w = periodic Hann of W samples at offset (N - W) / 2 within N ([1.0] for W = 1, as torch.hann_window)
     C[k][n] = w[n] cos(2 pi ((k n) mod N) / N), S likewise with sin, each rounded to float32 once
-    center: F = 1 + T / h, frame f reads the reflected x at f h - N / 2 + n; otherwise F = 1 + (T - N) / h, x at f h + n
+    center: F = 1 + (T - (N & 1)) / h (torch.stft pads N / 2 on each side), frame f reads the reflected x at f h - N / 2 + n;
+    otherwise F = 1 + (T - N) / h, x at f h + n
     p[f][k] = (sum_n C[k][n] x)^2 + (sum_n S[k][n] x)^2;  mel = fb^T p, fb = torchaudio's melscale_fbanks in double
     log: s log(max(v, floor)), s = 10 for db"""
 import ctypes
@@ -67,7 +68,7 @@ class Cfg:
 def window(N, W):
     w = np.zeros(N)
     off = (N - W) // 2
-    w[off:off + W] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(W) / W)
+    w[off:off + W] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(W) / W) if W > 1 else 1.0  # torch.hann_window(1) is [1.0]
     return w
 
 
@@ -86,12 +87,12 @@ def basis32(N, W):
 
 def out_frames(cfg, T):
     if cfg.center:
-        return 1 + T // cfg.hop_length if T > cfg.n_fft // 2 else 0
+        return 1 + (T - cfg.n_fft % 2) // cfg.hop_length if T > cfg.n_fft // 2 else 0
     return 1 + (T - cfg.n_fft) // cfg.hop_length if T >= cfg.n_fft else 0
 
 
 def frames_of(cfg, x):
-    """x [R, T] -> the frames [R, F, N] float64, the reflection resolved (+0.0 where an index still lies outside the row)"""
+    """x [R, T] -> the frames [R, F, N] float64, the reflection resolved: every index lies in [0, T) after it"""
     x = np.atleast_2d(np.asarray(x, np.float64))
     T = x.shape[1]
     F = out_frames(cfg, T)
@@ -100,8 +101,8 @@ def frames_of(cfg, x):
         idx = idx - cfg.n_fft // 2
         idx = np.where(idx < 0, -idx, idx)
         idx = np.where(idx >= T, 2 * (T - 1) - idx, idx)
-    ok = (idx >= 0) & (idx < T)
-    return np.where(ok[None], x[:, np.clip(idx, 0, T - 1)], 0.0)
+    assert idx.size == 0 or (idx.min() >= 0 and idx.max() < T), "a frame reaches outside the row"
+    return x[:, idx]
 
 
 def power64(cfg, x, tables=None):
@@ -374,8 +375,9 @@ def special_rows(rng, T):
 def impulse_expected(cfg, basis32_, T, j, amp=1.0):
     """The power spectrogram [K, F] float32 of a row of +0.0 with amp at index j, bit for bit, from the table alone: every
     fmaf with a zero sample leaves its accumulator as it is, so re and im of a frame are the entries under j times amp (amp a
-    power of two: exact), or the float32 sum of two of them where the reflected margin shows j twice; p = fmaf(im, im, float32(re
-    * re)), evaluated in float64, which holds im * im exactly."""
+    power of two: exact), or, where the reflected margins show j more than once, their float32 sum taken in the order of n, one
+    rounding per fmaf; p = fmaf(im, im, float32(re * re)), evaluated in float64, which holds im * im exactly.
+    -> (want, the number of frames that see j more than once)"""
     B = np.asarray(basis32_, np.float64)
     N, h, F = cfg.n_fft, cfg.hop_length, out_frames(cfg, T)
     want = np.zeros((cfg.K, F), np.float32)
@@ -385,13 +387,15 @@ def impulse_expected(cfg, basis32_, T, j, amp=1.0):
         if cfg.center:
             idx = np.where(idx < 0, -idx, idx)
             idx = np.where(idx >= T, 2 * (T - 1) - idx, idx)
+        assert idx.min() >= 0 and idx.max() < T
         ns = np.nonzero(idx == j)[0]
-        assert len(ns) <= 2
         if not len(ns):
             continue
-        twice += len(ns) == 2
-        re = (B[0][:, ns] * amp).sum(axis=1).astype(np.float32).astype(np.float64)
-        im = (B[1][:, ns] * amp).sum(axis=1).astype(np.float32).astype(np.float64)
+        twice += len(ns) >= 2
+        re, im = np.zeros(cfg.K), np.zeros(cfg.K)
+        for n in ns:  # the sum of two float32 is exact in float64, so each step rounds once, as the fmaf does
+            re = (re + B[0][:, n] * amp).astype(np.float32).astype(np.float64)
+            im = (im + B[1][:, n] * amp).astype(np.float32).astype(np.float64)
         want[:, f] = (im * im + (re * re).astype(np.float32).astype(np.float64)).astype(np.float32)
     return want, twice
 
@@ -399,7 +403,7 @@ def impulse_expected(cfg, basis32_, T, j, amp=1.0):
 def length_for(cfg, F):
     """The shortest T with out_frames(T) == F"""
     if cfg.center:
-        return max((F - 1) * cfg.hop_length, cfg.n_fft // 2 + 1)
+        return max((F - 1) * cfg.hop_length + cfg.n_fft % 2, cfg.n_fft // 2 + 1)
     return cfg.n_fft + (F - 1) * cfg.hop_length
 
 
@@ -412,3 +416,98 @@ CASES = {
     "uncentred": Cfg(16000, 64, 24, 48, n_mels=10, mel_scale="slaney", center=False),
 }
 OFFSETS = [(0, 0), (1, 3), (2, 1), (3, 2)]  # (out_off, in_off): every misalignment of either side once
+
+# Parameter sets at the edges of csrc/alac_mel.h, each with the tile_frames its plan has (asserted where a case is used) and
+# the path it reaches: N < 4 skips the prefetch block of dft_blocks, N % 4 != 0 runs its tail, even K makes KP = K + 1 and the
+# last bin pair whole, hop > N takes the other branch of stage_tile and make_tile, tile_frames 4 runs dft_blocks<4>.
+SLANEY = dict(mel_scale="slaney", norm="slaney")
+EDGE_CASES = {
+    "n2": (Cfg(8000, 2, 1, 2), 64),                                                  # N < 4, K = 2
+    "n3": (Cfg(8000, 3, 1, 3, n_mels=2), 64),                                        # odd N < 4
+    "n6u": (Cfg(8000, 6, 2, 6, n_mels=2, center=False), 64),                         # even K, a tail of 2
+    "n7": (Cfg(8000, 7, 3, 7, n_mels=3), 64),                                        # one block of 4, a tail of 3
+    "n10": (Cfg(8000, 10, 3, 10, n_mels=4, mel_scale="slaney"), 64),                 # loop once + block + tail, even K
+    "n15": (Cfg(8000, 15, 4, 9), 64),                                                # odd N, a short window at an odd offset
+    "w1": (Cfg(8000, 8, 3, 1), 64),                                                  # win_length 1
+    "hop37": (Cfg(8000, 16, 37, 16, n_mels=3), 64),                                  # hop > N staging
+    "hop37u": (Cfg(8000, 16, 37, 16, n_mels=3, center=False), 64),
+    "onemel": (Cfg(16000, 64, 16, 64, n_mels=1), 64),                                # taps 31: the 8-wide loop and its tail
+    "band": (Cfg(16000, 128, 32, 128, n_mels=12, f_min=300.0, f_max=3400.0, **SLANEY), 64),  # windows off both ends
+    "overtop": (Cfg(16000, 64, 16, 64, n_mels=6, f_max=12000.0), 64),  # f_max above sample_rate / 2: the last filter is cut off
+                                                                       # at the last bin, a short run whose window is clamped
+    "manymels": (Cfg(16000, 16, 4, 16, n_mels=2048), 4),      # dft_blocks<4>, cheap; the output tile far above the staging
+    "n512h512": (Cfg(16000, 512, 512, n_mels=40), 16),                               # hop = N
+    "n2048h512": (Cfg(48000, 2048, 512, n_mels=64), 8),                              # tile_frames 8, 55 KB of LDS
+    "n2046u": (Cfg(48000, 2046, 700, 2000, n_mels=32, center=False, **SLANEY), 8),   # even K at size, 60 608 bytes of LDS
+    "n2048h2048": (Cfg(48000, 2048, 2048), 4),                                       # <4> at size, power only
+    "n2048h5000": (Cfg(48000, 2048, 5000), 4),                                       # <4> with hop > N
+    "n2047": (Cfg(48000, 2047, 1024, n_mels=16), 4),                                 # odd N at size, taps 360
+}
+SMALL_EDGES = [k for k, (c, _) in EDGE_CASES.items() if c.n_fft <= 128]
+LARGE_EDGES = [k for k, (c, _) in EDGE_CASES.items() if c.n_fft > 128]
+
+
+def edge_lengths(cfg, tf):
+    """T for F = tile_frames + 1, the shortest row, and F = tile_frames (n_fft above 128: the first two only)"""
+    Ts = [length_for(cfg, tf + 1), cfg.n_fft // 2 + 1 if cfg.center else cfg.n_fft, length_for(cfg, tf)]
+    return Ts if cfg.n_fft <= 128 else Ts[:2]
+
+
+def values_of(img, lay, cfg, rows, T, what=""):
+    """[rows, bins, F] float32 out of an image, and a check that everything outside it is the sentinel"""
+    got = rows_of(img, rows, cfg.bins, out_frames(cfg, T), lay[5], lay[3], lay[4])
+    assert np.array_equal(img, expected_image(got, img.size, lay[5], lay[3], lay[4])), what + ": outside the output"
+    return got
+
+
+def ceiling_share(cfg, plan, x, got, what=""):
+    """got [rows, bins, F] against the float64 restatement on the plan's tables: asserts the ceilings of bounds(), -> the largest
+    error / ceiling"""
+    if cfg.n_mels is None:
+        ref = power64(cfg, x, plan["basis"])
+        lim, _ = bounds(cfg, x, plan["basis"])
+    else:
+        dense = dense_fb(plan, cfg.K)
+        ref = mel64(cfg, x, plan["basis"], dense)
+        _, lim = bounds(cfg, x, plan["basis"], dense, plan["taps"])
+    err = np.abs(got.astype(np.float64) - ref)
+    ok = err <= lim
+    assert ok.all(), "%s: error %g above the ceiling %g" % (what, err[~ok][0], lim[~ok][0])
+    return float((err / np.maximum(lim, 1e-300)).max())
+
+
+def impulse_rows(T, js):
+    """[len(js), T] float32 of +0.0, row r with 1.0 at js[r]"""
+    x = np.zeros((len(js), T), np.float32)
+    x[np.arange(len(js)), js] = 1.0
+    return x
+
+
+def power_only(cfg):
+    return cfg.with_(n_mels=None, mel_scale=None, norm=None)
+
+
+IMPULSE_CASES = ["n2", "n3", "n6u", "n7", "n10", "n15", "tiny", "hop37", "hop37u", "n2048h2048", "n2048h512"]
+EDGE_N = list(range(0, 9)) + list(range(1019, 1029)) + list(range(2039, 2048))  # a frame's n at the window's edges and its middle
+
+
+def impulse_batch(name):
+    """-> (cfg without a mel stage, tile_frames, T, the impulses' positions): every j in [0, 3 n_fft) and [T - 2 n_fft, T) at T =
+    length_for(tile_frames + 3); for the cases of n_fft 2048 the positions frame 5 reads at the n of EDGE_N."""
+    cfg, tf = EDGE_CASES[name] if name in EDGE_CASES else (CASES[name], 64)
+    cfg = power_only(cfg)
+    T = length_for(cfg, tf + 3)
+    N = cfg.n_fft
+    if N == 2048:
+        js = [5 * cfg.hop_length - N // 2 + n for n in EDGE_N]
+    else:
+        js = sorted(set(range(0, 3 * N)) | set(range(T - 2 * N, T)))
+    assert 0 <= min(js) and max(js) < T
+    return cfg, tf, T, js
+
+
+def impulse_image(cfg, basis, T, js):
+    """[len(js), K, F] float32 of impulse_expected per row, the rows that see their impulse twice, the rows without a power"""
+    want, twice = zip(*(impulse_expected(cfg, basis, T, j) for j in js))
+    want = np.stack(want)
+    return want, sum(t > 0 for t in twice), sum(not w.any() for w in want)

@@ -1,5 +1,6 @@
 """alacgpu_mel_device on the GPU: bit for bit what the host build of the same header (tests/host_sim/mel_sim.cpp) writes, over
-whole sentinel-filled buffers with NaN between the input rows; impulses, which come out as single table entries; zeros, denormals,
+whole sentinel-filled buffers with NaN between the input rows, mr.EDGE_CASES also within the derived ceilings against the
+float64 restatement; impulses, which come out as single table entries; zeros, denormals,
 huge values, -0.0, an infinity and a NaN; the log modes against float64 in float32 ulps; the Python entries over it
 (mel_spectrogram, spectrogram, whisper_log_mel, the pass behind load_clips); and host/mel_spectrogram.hpp through
 tests/host_sim/mel_shim.cpp.
@@ -40,7 +41,7 @@ def sim():
     return mr.build_mel_sim()
 
 
-def device_image(torch, ms, cfg, x, in_off=0, out_off=0, bin_pad=0):
+def device_image(torch, ms, cfg, x, in_off=0, out_off=0, bin_pad=0, sync=True):
     rows, T = x.shape
     F = mr.out_frames(cfg, T)
     lay = mr.layout(rows, T, cfg.bins, F, in_off, out_off, bin_pad)
@@ -53,7 +54,9 @@ def device_image(torch, ms, cfg, x, in_off=0, out_off=0, bin_pad=0):
     buf = torch.full((out_elems,), mr.SENTINEL - (1 << 32), dtype=torch.int32, device=dev)
     assert src.data_ptr() % 16 == 0 and buf.data_ptr() % 16 == 0
     torch.cuda.synchronize()
-    ms.mel_device(src.data_ptr() + 4 * in_lead, in_stride, rows, T, buf.data_ptr() + 4 * out_lead, row_stride, bin_stride, sync=True)
+    ms.mel_device(src.data_ptr() + 4 * in_lead, in_stride, rows, T, buf.data_ptr() + 4 * out_lead, row_stride, bin_stride, sync=sync)
+    if not sync:
+        ms.synchronize()
     return buf.cpu().numpy().view(np.uint32), lay
 
 
@@ -109,6 +112,118 @@ def test_device_equals_the_host_build_bit_for_bit(torch, pkg, sim, name):
                                           "%s bins %d rows %d T %d offsets %d/%d" % (name, cfg.bins, rows, T, in_off, out_off), lay)
             assert ms.last_ms() > 0
             assert ms.out_frames(shortest - 1) == 0
+
+
+@pytest.mark.parametrize("name", list(mr.EDGE_CASES))
+def test_edge_cases_on_the_device(torch, pkg, sim, name):
+    """mr.EDGE_CASES, each at the tile_frames its table gives (dft_blocks<4>, tile_frames 8, hop > n_fft, the DFT loop's tail, n_fft
+    below 4, even K, odd n_fft, 60 608 bytes of LDS): the library's plan is the host build's; rows 1 and 3 at F = tile_frames + 1,
+    the shortest row and (up to n_fft 128) F = tile_frames, the device's whole buffer bit for bit the host build's at the four
+    offset pairs of mr.OFFSETS (two above n_fft 128); and the device's own values within the ceilings of mr.bounds against the
+    float64 restatement, which does not come from the header."""
+    cfg, tf = mr.EDGE_CASES[name]
+    small = name in mr.SMALL_EDGES
+    rng = np.random.default_rng(len(name) + cfg.n_fft)
+    worst = 0.0
+    with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+        plan = ms.plan()
+        assert plan["tile_frames"] == tf
+        assert same_plan(plan, mr.sim_plan(sim, cfg)), "the library's plan is not the host build's"
+        for rows in (1, 3):
+            for T in mr.edge_lengths(cfg, tf):
+                assert ms.out_frames(T) == mr.out_frames(cfg, T) > 0
+                x = mr.signal(rng, rows, T)
+                y = host_values(sim, cfg, x)
+                for k, (out_off, in_off) in enumerate(mr.OFFSETS if small else mr.OFFSETS[:2]):
+                    what = "%s rows %d T %d offsets %d/%d" % (name, rows, T, in_off, out_off)
+                    img, lay = device_image(torch, ms, cfg, x, in_off, out_off, 3 if k else 0)
+                    if k == 0:
+                        worst = max(worst, mr.ceiling_share(cfg, plan, x, mr.values_of(img, lay, cfg, rows, T, what), what))
+                    assert_same_image(img, mr.expected_image(y, img.size, lay[5], lay[3], lay[4]), what, lay)
+    print("%s: tile_frames %d, at most %.1f %% of the ceiling" % (name, tf, 100 * worst))
+
+
+@pytest.mark.parametrize("name", mr.IMPULSE_CASES)
+def test_device_impulse_at_every_n(torch, pkg, name):
+    """One launch over a batch of rows, row r of +0.0 with 1.0 at js[r] (mr.impulse_batch: every j of the first 3 n_fft and the last
+    2 n_fft samples; at n_fft 2048 the n of one frame at the window's edges and its middle): every power is fmaf(S, S, C * C) of the
+    handle's own table entries under the impulse, or of their sum where the reflected margin shows it twice, and +0.0 elsewhere;
+    the whole buffer compared as uint32. The expectation needs the table alone, not the header."""
+    cfg, tf, T, js = mr.impulse_batch(name)
+    with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+        plan = ms.plan()
+        assert plan["tile_frames"] == tf
+        want, twice, silent = mr.impulse_image(cfg, plan["basis"], T, js)
+        if cfg.n_fft < 2048:  # the positions of the large cases lie inside the row, away from both margins
+            assert (twice > 0) == (cfg.center and cfg.n_fft >= 3), "the reflected margin shows an impulse twice"
+        if name == "hop37":
+            assert silent > 0, "no impulse lies between two frames"
+        img, lay = device_image(torch, ms, cfg, mr.impulse_rows(T, js), 1, 2, 1)
+    assert_same_image(img, mr.expected_image(want, img.size, lay[5], lay[3], lay[4]), "%s: impulses at %d positions" % (name, len(js)), lay)
+
+
+@pytest.mark.parametrize("name", ["tiny", "band"])
+def test_log_modes_on_other_float_values(torch, pkg, name):
+    """ln and db over mr.special_rows, against the device's own output P with the log off: +inf where P is +inf, a NaN where P is
+    one, float32(s log(floor)) exactly where P is at or below the floor (the zeros and the denormals), within LOG_ULPS of float64 s
+    log(P) everywhere else."""
+    base = mr.CASES[name] if name in mr.CASES else mr.EDGE_CASES[name][0]
+    T = mr.length_for(base, 64 + 2)
+    x = mr.special_rows(np.random.default_rng(31), T)
+    P = None
+    for log in (None, "ln", "db"):
+        cfg = base.with_(log=log, floor=1e-10)
+        with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+            assert ms.plan()["tile_frames"] == 64
+            img, lay = device_image(torch, ms, cfg, x, 3, 1, 2)
+        got = mr.values_of(img, lay, cfg, 6, T, "log %s" % log)
+        if log is None:
+            P = got
+            inf, nan = np.isposinf(P), np.isnan(P)
+            low = P <= np.float32(1e-10)
+            rest = ~(inf | nan | low)
+            assert inf.any() and nan.any() and low[:2].all() and rest.any() and not (P[~nan] < 0).any()
+            continue
+        s = 10.0 if log == "db" else 1.0
+        fl = float(np.float32(1e-10))
+        assert np.isposinf(got[inf]).all(), "log %s of +inf" % log
+        assert np.isnan(got[nan]).all() and not np.isnan(got[~nan]).any(), "log %s of a NaN" % log
+        at_floor = np.float32(s * (np.log(fl) if log == "ln" else np.log10(fl)))
+        assert np.array_equal(got[low].view(np.uint32), np.full(low.sum(), at_floor, np.float32).view(np.uint32)), "log %s at the floor" % log
+        u = float(mr.ulps32(got[rest], mr.log64(cfg, P[rest].astype(np.float64))).max())
+        print("%s log %s: %.3f ulps over %d values" % (name, log, u, rest.sum()))
+        assert u <= LOG_ULPS[log], "log %s: %.3f ulps, bound %.3f" % (log, u, LOG_ULPS[log])
+
+
+def test_pass_without_sync(torch, pkg, sim):
+    """mel_device(..., sync=False) and then synchronize(): the image of sync=True, and the pass has a time."""
+    cfg = mr.CASES["tiny"]
+    x = mr.signal(np.random.default_rng(5), 3, mr.length_for(cfg, 64 + 5))
+    with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+        want, lay = device_image(torch, ms, cfg, x, 1, 2, 1, sync=True)
+    with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+        img, _ = device_image(torch, ms, cfg, x, 1, 2, 1, sync=False)
+        assert ms.last_ms() > 0
+    assert_same_image(img, want, "sync=False", lay)
+    y = host_values(sim, cfg, x)
+    assert_same_image(img, mr.expected_image(y, img.size, lay[5], lay[3], lay[4]), "sync=False against the host build", lay)
+
+
+def test_frame_count_at_odd_n_fft(torch, pkg):
+    """An odd n_fft, centred: torch.stft pads n_fft / 2 on each side, so F = 1 + (T - 1) / hop: 28 frames at n_fft 15, hop 4, T 112,
+    not 29; and out_frames of the handle is the restatement's at every T up to 4 n_fft."""
+    x = torch.from_numpy(np.random.default_rng(15).uniform(-1, 1, (2, 112)).astype(np.float32)).to("cuda:0")
+    assert tuple(pkg.mel_spectrogram(x, 8000, n_fft=15, hop_length=4, n_mels=4).shape) == (2, 4, 28)
+    assert tuple(pkg.spectrogram(x, 8000, 15, hop_length=4).shape) == (2, 8, 28)
+    assert tuple(pkg.spectrogram(x, 8000, 16, hop_length=4).shape) == (2, 9, 29)
+    for name in ("n15", "n3", "n2047", "tiny"):
+        cfg = mr.CASES[name] if name in mr.CASES else mr.EDGE_CASES[name][0]
+        with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+            for T in range(0, 4 * cfg.n_fft):
+                assert ms.out_frames(T) == mr.out_frames(cfg, T), "%s T %d" % (name, T)
+            if cfg.n_fft % 2:
+                T = 3 * cfg.hop_length * cfg.n_fft
+                assert ms.out_frames(T) == T // cfg.hop_length
 
 
 @pytest.mark.parametrize("name", ["tiny", "whisper80", "uncentred"])

@@ -1,5 +1,5 @@
-"""The second launch of the four tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
-alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip) and alac_wave_pack (k_wavepack.hip). Each launch gets the slice's
+"""The second launch of the five tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
+alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip), alac_wave_pack (k_wavepack.hip) and alac_mel_rows (k_mel.hip). Each launch gets the slice's
 first tile as first_tile; only a batch of more than 2^22 tiles has a second slice, and a launch that lost its first_tile would
 corrupt such batches alone, silently.
 
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import clip_ref as cr
+from tests import mel_ref as mr
 from tests import resample_ref as rr
 from tests import wave_ref as wr
 from tests import wavepack_ref as pr
@@ -182,3 +183,31 @@ def test_second_launch_of_alac_wave_pack(torch, pkg):
     assert_cycle(torch, buf[LEAD:LEAD + 2 * N], ref, "PCM")
     assert_guards(buf, 2 * N, pr.PCM_SENTINEL)
     assert int(d_clip.item()) == N // 7 + (1 if N % 7 > 2 else 0)
+
+
+def test_second_launch_of_alac_mel_rows(torch, pkg):
+    """N rows of 2 samples, n_fft 2, win_length 2, hop 1, centred, no mel stage: 3 frames of 2 bins, tile_frames 64, so
+    tiles_per_row = 1, tile = row and the second launch has first_tile = 2^22. Row r is class r % 7; the expectation is the host
+    build's output for the 7 rows (34 MB in, 101 MB out).
+
+    A launch that ignored first_tile would compute rows 0 .. 4 098 again and leave the rows from 2^22 on unwritten (the
+    sentinel); one that wrote to the slice's rows but read from the batch's start would give row 2^22 + j the spectrogram of
+    row j, whose class j % 7 is not (2^22 + j) % 7."""
+    sim = mr.build_mel_sim()
+    cfg = mr.Cfg(8000, 2, 1, 2)
+    T, F, K = 2, 3, 2
+    rows7 = np.random.default_rng(14).uniform(-1, 1, (7, T)).astype(np.float32)
+    rows7[3] = [1.0, -1.0]
+    img, lay = mr.sim_image(sim, cfg, rows7)
+    assert mr.out_frames(cfg, T) == F and cfg.K == K
+    want7 = mr.rows_of(img, 7, K, F, lay[5], lay[3], lay[4])
+    assert want7.shape == (7, K, F) and len({w.tobytes() for w in want7}) == 7
+    x = cycled(torch, rows7, N)
+    fill = mr.SENTINEL - (1 << 32)
+    buf = sentinel_buffer(torch, N * K * F, fill, torch.int32)
+    torch.cuda.synchronize()
+    with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
+        assert ms.out_frames(T) == F and N * -(-F // ms.plan()["tile_frames"]) > SLICE
+        ms.mel_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, K * F, F, sync=True)
+    assert_cycle(torch, buf[LEAD:LEAD + N * K * F], np.ascontiguousarray(want7).view(np.int32), "rows")
+    assert_guards(buf, N * K * F, fill)

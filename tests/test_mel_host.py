@@ -1,12 +1,13 @@
 """The spectrogram pass on the CPU: csrc/alac_mel.h built with g++, contraction off (tests/host_sim/mel_sim.cpp), tile for tile
 and work item for work item what the gfx950 kernel of k_mel.hip runs, against the numpy float64 restatement of tests/mel_ref.py.
 
-* the restatement itself against torch.stft in float64;
+* the restatement itself, and the header's frame count, against torch.stft in float64;
 * the plan (dimensions, window starts, the float32 tables) against the restatement;
 * the host build over whole sentinel-filled buffers, every base offset, odd strides, a bin stride above F, NaN between the input
   rows and the input ending at an inaccessible page: the sentinel outside [rows, bins, F], inside it the derived ceiling of the
   float32 chains against the restatement run on the plan's own tables;
-* impulses, which come out as single table entries;
+* mr.EDGE_CASES, the parameter sets at which the header takes another path (dft_blocks<4>, hop > n_fft, the DFT loop's tail, ...);
+* impulses, which come out as single table entries: a batch of rows, one impulse each, at every n of a frame;
 * the arguments the entries reject, whisper_log_mel's post-processing, and the new names in library, header and binding.
 
 The library's own plan needs a handle, so it is held against the host build's in tests/test_gpu_mel.py."""
@@ -30,22 +31,33 @@ def sim():
 
 
 # ---- 1. the restatement ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,h,W", [(400, 160, 400), (16, 4, 12), (1024, 256, 1024)])
-def test_restatement_against_torch_stft(N, h, W):
+STFT_CASES = [(400, 160, 400, True), (16, 4, 12, True), (1024, 256, 1024, True), (15, 4, 9, True), (3, 1, 3, True), (2, 1, 2, True),
+              (6, 2, 6, False), (64, 24, 48, False), (16, 37, 16, True), (16, 37, 16, False), (30, 7, 11, True), (8, 3, 1, True),
+              (2047, 1024, 2047, True)]
+
+
+@pytest.mark.parametrize("N,h,W,center", STFT_CASES)
+def test_restatement_against_torch_stft(sim, N, h, W, center):
+    """Two lengths: 5 max(N, h) + 37, and the multiple of h below it, where an odd N's frame count differs from 1 + T / h. The
+    host build's frame count is torch's too."""
     import torch
-    cfg = mr.Cfg(16000, N, h, W)
+    cfg = mr.Cfg(16000, N, h, W, center=center)
     rng = np.random.default_rng(N)
-    T = 5 * N + 37
-    x = rng.uniform(-1, 1, (2, T))
-    got = mr.power64(cfg, x)
-    win = torch.hann_window(W, periodic=True, dtype=torch.float64)
-    X = torch.stft(torch.from_numpy(x), N, hop_length=h, win_length=W, window=win, center=True, pad_mode="reflect",
-                   return_complex=True)
-    want = (X.abs() ** 2).numpy()
-    assert got.shape == want.shape == (2, N // 2 + 1, 1 + T // h) and mr.out_frames(cfg, T) == 1 + T // h
-    err = np.abs(got - want).max() / want.max()
-    print("N %d: %.3g of the largest bin" % (N, err))
-    assert err <= 1e-6
+    T0 = 5 * max(N, h) + 37
+    for T in (T0, T0 // h * h):
+        x = rng.uniform(-1, 1, (2, T))
+        got = mr.power64(cfg, x)
+        win = torch.hann_window(W, periodic=True, dtype=torch.float64)
+        X = torch.stft(torch.from_numpy(x), N, hop_length=h, win_length=W, window=win, center=center, pad_mode="reflect",
+                       return_complex=True)
+        want = (X.abs() ** 2).numpy()
+        F = 1 + (T - N % 2) // h if center else 1 + (T - N) // h
+        assert got.shape == want.shape == (2, N // 2 + 1, F) and mr.out_frames(cfg, T) == F
+        assert mr.sim_out_frames(sim, cfg, T) == want.shape[2], "the header's frame count is not torch.stft's"
+        assert T % h or N % 2 == 0 or not center or F == T // h, "an odd n_fft has no frame at T itself"
+        err = np.abs(got - want).max() / want.max()
+        print("N %d hop %d W %d T %d: %.3g of the largest bin" % (N, h, W, T, err))
+        assert err <= 1e-6
 
 
 def test_restatement_fbanks_against_closed_forms():
@@ -63,11 +75,14 @@ def test_restatement_fbanks_against_closed_forms():
 
 
 # ---- 2. the plan -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(mr.CASES) + ["power", "short_window"])
+@pytest.mark.parametrize("name", list(mr.CASES) + ["power", "short_window"] + list(mr.EDGE_CASES))
 def test_plan_against_the_restatement(sim, name):
-    cfg = mr.CASES.get(name) or {"power": mr.Cfg(16000, 400, 160), "short_window": mr.Cfg(8000, 30, 7, 11, n_mels=4)}[name]
-    plan = mr.sim_plan(sim, cfg)
+    cfg = mr.CASES.get(name) or {"power": mr.Cfg(16000, 400, 160), "short_window": mr.Cfg(8000, 30, 7, 11, n_mels=4)}.get(name)
+    plan = mr.sim_plan(sim, cfg or mr.EDGE_CASES[name][0])
     assert plan is not None, "no plan"
+    if cfg is None:
+        cfg, tf = mr.EDGE_CASES[name]
+        assert plan["tile_frames"] == tf
     N, W, K = cfg.n_fft, cfg.win_length, cfg.K
     assert (plan["n_fft"], plan["win_length"], plan["hop_length"], plan["n_freqs"], plan["bins"]) == (N, W, cfg.hop_length, K, cfg.bins)
     tf = plan["tile_frames"]
@@ -77,8 +92,8 @@ def test_plan_against_the_restatement(sim, name):
     assert got.shape == want.shape
     # within one float32 ulp of the double value (libm's and numpy's cos may differ in the last double bit)
     assert (np.abs(got.astype(np.float64) - want) <= np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)).all()
-    zero = mr.window(N, W) == 0.0  # outside the window, and the periodic Hann's sample 0
-    assert zero[(N - W) // 2] and zero.sum() == N - W + 1
+    zero = mr.window(N, W) == 0.0  # outside the window, and the periodic Hann's sample 0 (win_length 1 is [1.0]: none inside)
+    assert zero[(N - W) // 2] == (W > 1) and zero.sum() == (N - W + 1 if W > 1 else N - W)
     assert not got[:, :, zero].view(np.uint32).any(), "a window zero is not +0.0 in the table"
     assert not got[1, 0].view(np.uint32).any(), "sin(0) is not +0.0"
     if cfg.n_mels is None:
@@ -95,29 +110,16 @@ def test_plan_against_the_restatement(sim, name):
 
 def test_tile_frames_follow_the_lds_budget(sim):
     for cfg, tf in ((mr.CASES["tiny"], 64), (mr.CASES["whisper80"], 32), (mr.CASES["n1024"], 16), (mr.Cfg(48000, 2048, 2048), 4),
-                    (mr.Cfg(48000, 2048, 5000), 4), (mr.Cfg(48000, 2048, 512, n_mels=64), 8)):
+                    (mr.Cfg(48000, 2048, 5000), 4), (mr.Cfg(48000, 2048, 512, n_mels=64), 8)) + tuple(mr.EDGE_CASES.values()):
         assert mr.sim_plan(sim, cfg)["tile_frames"] == tf
+    assert mr.sim_plan(sim, mr.EDGE_CASES["n2046u"][0])["lds_bytes"] == 60608
 
 
 # ---- 3. the host build against the restatement ------------------------------------------------------------------------
 def check_image(cfg, plan, x, img, lay, what):
     """The whole buffer: the sentinel outside [rows, bins, F], inside it the ceilings of mr.bounds."""
-    rows, T = x.shape
-    F = mr.out_frames(cfg, T)
-    _, _, _, row_stride, bin_stride, out_lead, _ = lay
-    got = mr.rows_of(img, rows, cfg.bins, F, out_lead, row_stride, bin_stride)
-    assert np.array_equal(img, mr.expected_image(got, img.size, out_lead, row_stride, bin_stride)), what + ": outside the output"
-    if cfg.n_mels is None:
-        ref = mr.power64(cfg, x, plan["basis"])
-        lim, _ = mr.bounds(cfg, x, plan["basis"])
-    else:
-        dense = mr.dense_fb(plan, cfg.K)
-        ref = mr.mel64(cfg, x, plan["basis"], dense)
-        _, lim = mr.bounds(cfg, x, plan["basis"], dense, plan["taps"])
-    err = np.abs(got.astype(np.float64) - ref)
-    ok = err <= lim
-    assert ok.all(), "%s: error %g above the ceiling %g" % (what, err[~ok][0], lim[~ok][0])
-    return float((err / np.maximum(lim, 1e-300)).max())
+    got = mr.values_of(img, lay, cfg, x.shape[0], x.shape[1], what)
+    return mr.ceiling_share(cfg, plan, x, got, what)
 
 
 def lengths(cfg, tf):
@@ -159,6 +161,49 @@ def test_hop_above_n_fft_and_odd_sizes(sim):
             for out_off, in_off in mr.OFFSETS[:2]:
                 img, lay = mr.sim_image(sim, cfg, x, in_off, out_off, 1, guard=1)
                 check_image(cfg, plan, x, img, lay, "n_fft %d hop %d T %d" % (cfg.n_fft, cfg.hop_length, T))
+
+
+@pytest.mark.parametrize("name", list(mr.EDGE_CASES))
+def test_edge_cases_against_the_restatement(sim, name):
+    """mr.EDGE_CASES, each at the tile_frames the table gives: rows 1 and 3; F = tile_frames + 1, the shortest row and F =
+    tile_frames; up to n_fft 128 every offset pair of mr.OFFSETS with bin strides F and F + 3, above it one pair and the first
+    two lengths."""
+    cfg, tf = mr.EDGE_CASES[name]
+    plan = mr.sim_plan(sim, cfg)
+    assert plan["tile_frames"] == tf
+    rng = np.random.default_rng(len(name) + cfg.n_fft)
+    small = name in mr.SMALL_EDGES
+    worst = 0.0
+    for rows in (1, 3):
+        for T in mr.edge_lengths(cfg, tf):
+            x = mr.signal(rng, rows, T)
+            assert mr.sim_out_frames(sim, cfg, T) == mr.out_frames(cfg, T) > 0
+            for out_off, in_off in mr.OFFSETS if small else mr.OFFSETS[1:2]:
+                for bin_pad in (0, 3) if small else (3,):
+                    img, lay = mr.sim_image(sim, cfg, x, in_off, out_off, bin_pad, guard=1)
+                    worst = max(worst, check_image(cfg, plan, x, img, lay, "%s rows %d T %d offsets %d/%d pad %d"
+                                                   % (name, rows, T, in_off, out_off, bin_pad)))
+    print("%s: tile_frames %d, at most %.1f %% of the ceiling" % (name, tf, 100 * worst))
+
+
+@pytest.mark.parametrize("name", mr.IMPULSE_CASES)
+def test_impulse_at_every_n(sim, name):
+    """One launch over a batch of rows, row r of +0.0 with 1.0 at js[r]: every frame that reads js[r] holds fmaf(S, S, C * C) of
+    the table's entries under it, every other power is +0.0, the whole buffer compared as uint32. A frame's n that the DFT loop
+    dropped, staged from a neighbouring index or took from another row shows here even where the window is 1e-6 there, which
+    the ceilings let pass."""
+    cfg, tf, T, js = mr.impulse_batch(name)
+    plan = mr.sim_plan(sim, cfg)
+    assert plan["tile_frames"] == tf
+    want, twice, silent = mr.impulse_image(cfg, plan["basis"], T, js)
+    if cfg.n_fft < 2048:  # the positions of the large cases lie inside the row, away from both margins
+        assert (twice > 0) == (cfg.center and cfg.n_fft >= 3), "the reflected margin shows an impulse twice"
+    if name == "hop37":
+        assert silent > 0, "no impulse lies between two frames"
+    x = mr.impulse_rows(T, js)
+    img, lay = mr.sim_image(sim, cfg, x, 1, 2, 1)
+    bad = np.nonzero(img != mr.expected_image(want, img.size, lay[5], lay[3], lay[4]))[0]
+    assert not len(bad), "%s: %d words differ, the first in the row of the impulse at %d" % (name, len(bad), js[(bad[0] - lay[5]) // lay[3]])
 
 
 def test_impulses_come_out_as_single_table_entries(sim):
