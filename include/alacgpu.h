@@ -538,6 +538,102 @@ typedef struct alacgpu_mel_info {
 int alacgpu_mel_plan(const alacgpu_mel* mel, alacgpu_mel_info* info, float* basis_out, size_t basis_cap, float* fb_out,
                      size_t fb_cap, int32_t* first_out, size_t first_cap);
 
+/*
+ * KALDI FEATURES: float32 rows -> Kaldi's filterbank (fbank) or MFCC features, one fused pass on a handle of its own
+ * (k_fbank.hip, alac_fbank.h over alac_mel.h; the spectrogram pass and every other kernel are untouched): what
+ * torchaudio.compliance.kaldi.fbank / .mfcc compute, without the intermediates. W = frame_length, h = frame_shift, N = the
+ * next power of two >= W with round_to_power_of_two, else W, at most 2048; K = N / 2 + 1; M = num_mel_bins:
+ *     frames  snip_edges: F = 1 + (T - W) / h for T >= W, frame f reads x[f h + n], n < W; otherwise F = (T + h / 2) / h for
+ *             T >= W, frame f reads x[f h - (W / 2 - h / 2) + n], index i < 0 being -1 - i and i >= T being 2 T - 1 - i (Kaldi's
+ *             reflection: the edge sample repeats). T < W has no frame in either mode.
+ *     frame   mean removed (remove_dc_offset), y[n] = v[n] - c v[n - 1] with v[-1] = v[0] (c = preemphasis_coefficient),
+ *             times the symmetric window of window_type, zeros up to N; all of it, and `scale`, folded into the basis
+ *             C[k][n], S[k][n], n < W, in double, each entry rounded once (alac_fbank.h spells the folding out)
+ *     p[k]    = fmaf(im, im, re * re),  re = fmaf(C[k][n], x[n], re), im = fmaf(S[k][n], x[n], im) for n = 0 .. W - 1 from +0.0f
+ *     mel[m]  = fmaf chain over q < taps of fbw[m][q] * p[first[m] + q] from +0.0f; the weights are get_mel_banks' in double:
+ *             triangles in mel(f) = 1127 ln(1 + f / 700) over the bins k < N / 2, M + 2 points equally spaced from low_freq to
+ *             high_freq (<= 0: Nyquist + high_freq)
+ *     log     use_log_fbank: ln(max(v, 2^-23))
+ *     energy  use_energy: ln(max(scale^2 sum (x[n] - mean)^2, 2^-23)), raised to ln(energy_floor) where that is > 0, as
+ *             column 0, or the last column with htk_compat; log_energy = 0 keeps the sum itself (for checks)
+ *     MFCC    num_ceps > 0: the log-mel (always logged) times D[c][m] = sqrt(2 / M) cos(pi (m + 0.5) c / M) (row 0: sqrt(1 /
+ *             M)), a chain over m upwards, times 1 + 0.5 L sin(pi c / L) where L = cepstral_lifter != 0; with use_energy
+ *             column 0 is the energy; with htk_compat column 0 moves to the end
+ * cols = M (+ 1 with use_energy) for fbank, num_ceps for MFCC. Up to the logs every build gives the same bits.
+ * alacgpu_fbank_create is ALACGPU_E_ARG, before any HIP call, when no plan can be built: frame_length outside [1, 2048],
+ * frame_shift 0, sample_rate 0, a flag above 1, window_type or layout outside its values, dither != 0, vtln_warp != 1,
+ * use_power 0, use_energy without raw_energy, num_mel_bins outside [1, 4096], num_ceps > num_mel_bins, a number that is not
+ * finite, scale 0, energy_floor < 0, not 0 <= low_freq < Nyquist, 0 < high <= Nyquist, low < high, a filter whose weights
+ * are not one run, or four frames that do not fit 64 KB of LDS. The handle owns a stream, an event pair and the tables on the
+ * device; it is single-caller, like a decoder.
+ */
+enum {
+    ALACGPU_FBANK_WINDOW_HANNING = 0,
+    ALACGPU_FBANK_WINDOW_HAMMING = 1,
+    ALACGPU_FBANK_WINDOW_POVEY = 2,
+    ALACGPU_FBANK_WINDOW_RECTANGULAR = 3,
+    ALACGPU_FBANK_WINDOW_BLACKMAN = 4
+};
+enum { ALACGPU_FBANK_LAYOUT_FRAMES = 0, ALACGPU_FBANK_LAYOUT_BINS = 1 };
+typedef struct alacgpu_fbank_config {
+    uint32_t sample_rate;
+    uint32_t frame_length;          /* W, samples: 1 .. 2048 */
+    uint32_t frame_shift;           /* h, samples: >= 1 */
+    uint32_t round_to_power_of_two; /* 0 or 1 */
+    uint32_t num_mel_bins;          /* 1 .. 4096 */
+    uint32_t num_ceps;              /* 0: fbank; 1 .. num_mel_bins: MFCC */
+    uint32_t snip_edges;
+    uint32_t remove_dc_offset;
+    uint32_t window_type;           /* ALACGPU_FBANK_WINDOW_* */
+    uint32_t use_log_fbank;         /* fbank only; MFCC always logs */
+    uint32_t use_energy;
+    uint32_t raw_energy;            /* 1 wherever use_energy is */
+    uint32_t htk_compat;
+    uint32_t use_power;             /* 1 */
+    uint32_t log_energy;            /* 1; 0 keeps the energy column unlogged and unfloored */
+    uint32_t layout;                /* ALACGPU_FBANK_LAYOUT_* */
+    double preemphasis_coefficient;
+    double blackman_coeff;
+    double low_freq, high_freq;     /* Hz; high_freq <= 0: Nyquist + high_freq */
+    double energy_floor;            /* >= 0; 0: none */
+    double scale;                   /* folded into the basis; 32768 feeds [-1, 1] waveforms to recipes made for 16-bit values */
+    double cepstral_lifter;         /* 0: none */
+    double dither;                  /* 0 */
+    double vtln_warp;               /* 1 */
+} alacgpu_fbank_config;
+typedef struct alacgpu_fbank alacgpu_fbank;
+int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu_fbank** out);
+void alacgpu_fbank_destroy(alacgpu_fbank* fb);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernels (valid after a sync). */
+void* alacgpu_fbank_stream(alacgpu_fbank* fb);
+int alacgpu_fbank_synchronize(alacgpu_fbank* fb);
+int alacgpu_fbank_last_ms(alacgpu_fbank* fb, float* ms);
+/* F for rows of in_frames samples; 0 for a NULL handle, where no frame exists, or above 2^61 samples. */
+uint64_t alacgpu_fbank_out_frames(const alacgpu_fbank* fb, uint64_t in_frames);
+/*
+ * rows rows of in_frames float32 samples, row r at d_in + r * in_row_stride (strides in elements), F =
+ * alacgpu_fbank_out_frames(fb, in_frames). ALACGPU_FBANK_LAYOUT_FRAMES: -> [rows][F][cols], element (r, f, c) at d_out + r *
+ * out_row_stride + f * out_inner_stride + c (out_inner_stride >= cols: the frame stride). ALACGPU_FBANK_LAYOUT_BINS: ->
+ * [rows][cols][F], element (r, c, f) at d_out + r * out_row_stride + c * out_inner_stride + f (out_inner_stride >= F: the bin
+ * stride). Exactly those elements are written, nothing in the gaps the strides leave; nothing outside [0, in_frames) of an
+ * input row is read. rows = 0 or F = 0 succeeds and touches nothing. ALACGPU_E_ARG before any HIP call: a NULL handle; with
+ * work to do a NULL d_in or d_out, a base that is not 4-byte aligned, in_row_stride < in_frames, an inner stride below a
+ * line, a row stride below what a row spans, or sizes whose products overflow. Asynchronous on the handle's stream unless
+ * sync != 0: the input must be complete, or ordered on that stream, before the call.
+ */
+int alacgpu_fbank_device(alacgpu_fbank* fb, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
+                         size_t out_row_stride, size_t out_inner_stride, int sync);
+/* The plan the handle's kernel uses: its numbers, and (where the pointers are not NULL and the capacities, counted in
+ * entries, suffice) the host copies of the folded basis [2][n_freqs][frame_length] (C, then S), of the filterbank windows
+ * fbw[num_mel_bins][taps], of first[num_mel_bins], of the DCT [num_ceps][num_mel_bins] and of the lifter [num_ceps]. */
+typedef struct alacgpu_fbank_info {
+    uint32_t frame_length, frame_shift, n_fft, n_freqs, num_mel_bins, taps, num_ceps, cols, tile_frames, lds_bytes;
+} alacgpu_fbank_info;
+int alacgpu_fbank_plan(const alacgpu_fbank* fb, alacgpu_fbank_info* info, float* basis_out, size_t basis_cap, float* fb_out,
+                       size_t fb_cap, int32_t* first_out, size_t first_cap, float* dct_out, size_t dct_cap, float* lifter_out,
+                       size_t lifter_cap);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

@@ -34,6 +34,7 @@ __all__ = [
     "ErrConfig", "ErrDecode", "AlacError", "build", "lib", "lib_path", "trim", "load", "save",
     "load_clips", "Resampler", "NewResampler", "resample",
     "MelSpectrogram", "NewMelSpectrogram", "mel_spectrogram", "spectrogram", "whisper_log_mel",
+    "KaldiFeatures", "NewKaldiFeatures", "kaldi_fbank", "kaldi_mfcc",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -282,6 +283,17 @@ _EXPORTS = {
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]),
     "alacgpu_mel_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
+    "alacgpu_fbank_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_fbank_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_fbank_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_fbank_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_fbank_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_fbank_out_frames": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "alacgpu_fbank_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]),
+    "alacgpu_fbank_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p, ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -1176,6 +1188,227 @@ def whisper_log_mel(waveform, n_mels=80, device=None):
     slaney scale and norm and log10 at floor 1e-10, then whisper_post."""
     return whisper_post(mel_spectrogram(waveform, 16000, 400, 400, 160, 0.0, 8000.0, n_mels, True, "slaney", "slaney", "log10",
                                         1e-10, device))
+
+
+# ---- Kaldi features (new: torchaudio.compliance.kaldi.fbank / .mfcc, one fused pass on the device) ---------------------
+class FbankConfig(ctypes.Structure):
+    """alacgpu_fbank_config (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("sample_rate", "frame_length", "frame_shift", "round_to_power_of_two", "num_mel_bins",
+                                               "num_ceps", "snip_edges", "remove_dc_offset", "window_type", "use_log_fbank",
+                                               "use_energy", "raw_energy", "htk_compat", "use_power", "log_energy", "layout")] + [
+        (k, ctypes.c_double) for k in ("preemphasis_coefficient", "blackman_coeff", "low_freq", "high_freq", "energy_floor", "scale",
+                                       "cepstral_lifter", "dither", "vtln_warp")]
+
+
+class FbankInfo(ctypes.Structure):
+    """alacgpu_fbank_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("frame_length", "frame_shift", "n_fft", "n_freqs", "num_mel_bins", "taps", "num_ceps",
+                                               "cols", "tile_frames", "lds_bytes")]
+
+
+_FBANK_WINDOWS = {"hanning": 0, "hamming": 1, "povey": 2, "rectangular": 3, "blackman": 4}
+_FBANK_LAYOUTS = {"frames": 0, "bins": 1}
+
+
+def _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps, round_to_power_of_two, snip_edges, remove_dc_offset,
+                  window_type, use_log_fbank, use_energy, raw_energy, htk_compat, use_power, log_energy, layout,
+                  preemphasis_coefficient, blackman_coeff, low_freq, high_freq, energy_floor, scale, cepstral_lifter, dither,
+                  vtln_warp):
+    """The arguments of the handle (lengths in samples) -> FbankConfig; ValueError for what is no number of its kind or no name
+    of an enum (what the numbers may be is the plan's to say)."""
+    for v in (sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("sample_rate, frame_length, frame_shift, num_mel_bins and num_ceps are integers in [0, 2^32)")
+    if window_type not in _FBANK_WINDOWS:
+        raise ValueError("window_type is one of %s, not %r" % (", ".join(sorted(_FBANK_WINDOWS)), window_type))
+    if layout not in _FBANK_LAYOUTS:
+        raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
+    c = FbankConfig()
+    c.sample_rate, c.frame_length, c.frame_shift = int(sample_rate), int(frame_length), int(frame_shift)
+    c.num_mel_bins, c.num_ceps = int(num_mel_bins), int(num_ceps)
+    c.round_to_power_of_two, c.snip_edges, c.remove_dc_offset = int(bool(round_to_power_of_two)), int(bool(snip_edges)), int(bool(remove_dc_offset))
+    c.window_type, c.layout = _FBANK_WINDOWS[window_type], _FBANK_LAYOUTS[layout]
+    c.use_log_fbank, c.use_energy, c.raw_energy = int(bool(use_log_fbank)), int(bool(use_energy)), int(bool(raw_energy))
+    c.htk_compat, c.use_power, c.log_energy = int(bool(htk_compat)), int(bool(use_power)), int(bool(log_energy))
+    c.preemphasis_coefficient, c.blackman_coeff = float(preemphasis_coefficient), float(blackman_coeff)
+    c.low_freq, c.high_freq, c.energy_floor = float(low_freq), float(high_freq), float(energy_floor)
+    c.scale, c.cepstral_lifter, c.dither, c.vtln_warp = float(scale), float(cepstral_lifter), float(dither), float(vtln_warp)
+    return c
+
+
+class KaldiFeatures:
+    """float32 rows -> Kaldi's fbank (num_ceps 0) or MFCC features on one MI355X (include/alacgpu.h: alacgpu_fbank_*). Lengths
+    are in samples here; kaldi_fbank / kaldi_mfcc take torchaudio's milliseconds. layout "frames" gives [..., F, cols], "bins"
+    [..., cols, F]. log_energy=False keeps the energy column unlogged (for checks). ValueError when no plan can be built:
+    dither != 0, vtln_warp != 1, use_power False and use_energy without raw_energy among them, before any HIP call.
+    Single-caller, bound to one device and one stream."""
+
+    def __init__(self, sample_rate, frame_length, frame_shift, num_mel_bins=23, num_ceps=0, round_to_power_of_two=True,
+                 snip_edges=True, remove_dc_offset=True, window_type="povey", use_log_fbank=True, use_energy=False, raw_energy=True,
+                 htk_compat=False, use_power=True, log_energy=True, layout="frames", preemphasis_coefficient=0.97,
+                 blackman_coeff=0.42, low_freq=20.0, high_freq=0.0, energy_floor=1.0, scale=1.0, cepstral_lifter=22.0, dither=0.0,
+                 vtln_warp=1.0, device=0):
+        self._h = ctypes.c_void_p()
+        self._lib = lib()
+        self.config = _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps, round_to_power_of_two, snip_edges,
+                                    remove_dc_offset, window_type, use_log_fbank, use_energy, raw_energy, htk_compat, use_power,
+                                    log_energy, layout, preemphasis_coefficient, blackman_coeff, low_freq, high_freq, energy_floor,
+                                    scale, cepstral_lifter, dither, vtln_warp)
+        _check(self._lib.alacgpu_fbank_create(device, ctypes.byref(self.config), ctypes.byref(self._h)))
+        self.device = device
+        self.layout = layout
+        self.cols = int(num_ceps) if int(num_ceps) else int(num_mel_bins) + int(bool(use_energy))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.alacgpu_fbank_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def out_frames(self, in_frames):
+        """alacgpu_fbank_out_frames: 1 + (T - W) / h with snip_edges, (T + h / 2) / h without; 0 for T < W."""
+        return int(self._lib.alacgpu_fbank_out_frames(self._h, int(in_frames)))
+
+    def features_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, sync=True):
+        """alacgpu_fbank_device: raw device pointers (ints), strides in elements. rows rows of in_frames float32 samples ->
+        element (r, f, c) at d_out + r * out_row_stride + f * out_inner_stride + c (layout frames) or (r, c, f) at d_out + r *
+        out_row_stride + c * out_inner_stride + f (layout bins); exactly those elements are written. Runs on the handle's
+        stream, which does not order against torch's: synchronize the input first."""
+        _check(self._lib.alacgpu_fbank_device(self._h, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride,
+                                              1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_fbank_plan -> dict: the numbers of alacgpu_fbank_info and the host copies of the tables the kernel uses: basis
+        [2, n_freqs, frame_length] float32 (C, then S, folded), fb [num_mel_bins, taps], first [num_mel_bins] int32, dct
+        [num_ceps, num_mel_bins] and lifter [num_ceps]."""
+        info = FbankInfo()
+        _check(self._lib.alacgpu_fbank_plan(self._h, ctypes.byref(info), None, 0, None, 0, None, 0, None, 0, None, 0))
+        basis = np.zeros((2, info.n_freqs, info.frame_length), np.float32)
+        fb = np.zeros((info.num_mel_bins, info.taps), np.float32)
+        first = np.zeros(info.num_mel_bins, np.int32)
+        dct = np.zeros((info.num_ceps, info.num_mel_bins), np.float32)
+        lifter = np.zeros(info.num_ceps, np.float32)
+        _check(self._lib.alacgpu_fbank_plan(self._h, ctypes.byref(info), basis.ctypes.data, basis.size, fb.ctypes.data, fb.size,
+                                            first.ctypes.data, first.size, dct.ctypes.data, dct.size, lifter.ctypes.data, lifter.size))
+        out = {k: int(getattr(info, k)) for k, _ in FbankInfo._fields_}
+        out.update(basis=basis, fb=fb, first=first, dct=dct, lifter=lifter)
+        return out
+
+    def last_ms(self):
+        """alacgpu_fbank_last_ms: HIP events around the kernels of the last pass."""
+        ms = ctypes.c_float()
+        _check(self._lib.alacgpu_fbank_last_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def synchronize(self):
+        _check(self._lib.alacgpu_fbank_synchronize(self._h))
+
+    def __call__(self, waveform):
+        """A float32 tensor [..., T] -> [..., F, cols] (layout frames) or [..., cols, F] (bins) on the handle's device (made
+        contiguous, flattened to rows). ValueError where T has no frame (T < frame_length)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        T = int(waveform.shape[-1])
+        frames = self.out_frames(T)
+        if not frames:
+            raise ValueError("%d samples have no frame of %d" % (T, self.config.frame_length))
+        rows = 1
+        for d in waveform.shape[:-1]:
+            rows *= int(d)
+        x = waveform.to(dev).contiguous().reshape(rows, T)
+        shape = (frames, self.cols) if self.layout == "frames" else (self.cols, frames)
+        out = torch.empty((rows,) + shape, dtype=torch.float32, device=dev)
+        if rows:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            self.features_device(x.data_ptr(), T, rows, T, out.data_ptr(), self.cols * frames, shape[1], sync=True)
+        return out.reshape(tuple(waveform.shape[:-1]) + shape)
+
+
+def NewKaldiFeatures(*args, **kw):
+    """A KaldiFeatures (context manager); ValueError where no plan can be built."""
+    return KaldiFeatures(*args, **kw)
+
+
+_KALDIS = {}  # (device, every field of the configuration) -> KaldiFeatures: a plan is built once per process
+
+
+def _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, **kw):
+    import torch
+    if isinstance(waveform, np.ndarray):
+        if waveform.dtype != np.float32:
+            raise ValueError("waveform must be float32")
+    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
+        raise ValueError("waveform must be a float32 torch tensor or numpy array")
+    if waveform.ndim < 1:
+        raise ValueError("waveform must be [..., T]")
+    # torchaudio's _get_waveform_and_window_properties: milliseconds -> samples
+    W, h = int(sample_frequency * frame_length * 0.001), int(sample_frequency * frame_shift * 0.001)
+    c = _fbank_config(sample_frequency, W, h, kw["num_mel_bins"], kw["num_ceps"], kw["round_to_power_of_two"], kw["snip_edges"],
+                      kw["remove_dc_offset"], kw["window_type"], kw["use_log_fbank"], kw["use_energy"], kw["raw_energy"],
+                      kw["htk_compat"], kw["use_power"], True, kw["layout"], kw["preemphasis_coefficient"], kw["blackman_coeff"],
+                      kw["low_freq"], kw["high_freq"], kw["energy_floor"], kw["scale"], kw["cepstral_lifter"], kw["dither"],
+                      kw["vtln_warp"])
+    if isinstance(waveform, np.ndarray):
+        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
+    if device is None:
+        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    key = (device,) + tuple(getattr(c, k) for k, _ in FbankConfig._fields_)
+    if key not in _KALDIS:
+        _KALDIS[key] = KaldiFeatures(sample_frequency, W, h, device=device, **kw)
+    out = _KALDIS[key](waveform)
+    if subtract_mean:  # over the frames, as torchaudio's _subtract_column_mean: a torch op, as Whisper's post-processing is
+        out = out - out.mean(dim=-2 if kw["layout"] == "frames" else -1, keepdim=True)
+    return out
+
+
+def kaldi_fbank(waveform, sample_frequency=16000, blackman_coeff=0.42, dither=0.0, energy_floor=1.0, frame_length=25.0,
+                frame_shift=10.0, high_freq=0.0, htk_compat=False, low_freq=20.0, num_mel_bins=23, preemphasis_coefficient=0.97,
+                raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True, snip_edges=True, subtract_mean=False,
+                use_energy=False, use_log_fbank=True, use_power=True, vtln_warp=1.0, window_type="povey", scale=1.0,
+                layout="frames", device=None):
+    """torchaudio.compliance.kaldi.fbank(waveform, ...) in one pass on the device, with torchaudio's keyword names and defaults
+    (frame_length / frame_shift in milliseconds; sample_frequency an integer): a float32 tensor [..., T] (CUDA, CPU or numpy;
+    the last two are uploaded) -> [..., F, num_mel_bins (+ 1 with use_energy)] on cuda:`device`, or [..., cols, F] with
+    layout="bins". scale multiplies the waveform (32768 for recipes made for 16-bit sample values) at no cost. ValueError for
+    dither != 0, vtln_warp != 1, use_power=False, use_energy without raw_energy, parameters without a plan, another dtype, or
+    T below one frame (torchaudio returns frames there without snip_edges; this does not). The tables of a (device, parameter
+    set) are built once and kept."""
+    return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, num_mel_bins=num_mel_bins, num_ceps=0,
+                  round_to_power_of_two=round_to_power_of_two, snip_edges=snip_edges, remove_dc_offset=remove_dc_offset,
+                  window_type=window_type, use_log_fbank=use_log_fbank, use_energy=use_energy, raw_energy=raw_energy,
+                  htk_compat=htk_compat, use_power=use_power, layout=layout, preemphasis_coefficient=preemphasis_coefficient,
+                  blackman_coeff=blackman_coeff, low_freq=low_freq, high_freq=high_freq, energy_floor=energy_floor, scale=scale,
+                  cepstral_lifter=0.0, dither=dither, vtln_warp=vtln_warp)
+
+
+def kaldi_mfcc(waveform, sample_frequency=16000, blackman_coeff=0.42, cepstral_lifter=22.0, dither=0.0, energy_floor=1.0,
+               frame_length=25.0, frame_shift=10.0, high_freq=0.0, htk_compat=False, low_freq=20.0, num_ceps=13, num_mel_bins=23,
+               preemphasis_coefficient=0.97, raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True, snip_edges=True,
+               subtract_mean=False, use_energy=False, vtln_warp=1.0, window_type="povey", scale=1.0, layout="frames", device=None):
+    """torchaudio.compliance.kaldi.mfcc(waveform, ...) in one pass on the device: as kaldi_fbank, -> [..., F, num_ceps] (1 <=
+    num_ceps <= num_mel_bins)."""
+    if isinstance(num_ceps, bool) or int(num_ceps) != num_ceps or int(num_ceps) < 1:
+        raise ValueError("num_ceps is an integer in [1, num_mel_bins]")
+    return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, num_mel_bins=num_mel_bins,
+                  num_ceps=num_ceps, round_to_power_of_two=round_to_power_of_two, snip_edges=snip_edges,
+                  remove_dc_offset=remove_dc_offset, window_type=window_type, use_log_fbank=True, use_energy=use_energy,
+                  raw_energy=raw_energy, htk_compat=htk_compat, use_power=True, layout=layout,
+                  preemphasis_coefficient=preemphasis_coefficient, blackman_coeff=blackman_coeff, low_freq=low_freq,
+                  high_freq=high_freq, energy_floor=energy_floor, scale=scale, cepstral_lifter=cepstral_lifter, dither=dither,
+                  vtln_warp=vtln_warp)
 
 
 def NewDecoder(source, device=0, window=1024):

@@ -1,0 +1,271 @@
+/*
+ * k_fbank.hip — float32 rows -> Kaldi's fbank or MFCC features: the gfx950 kernel over csrc/alac_fbank.h (which stands on
+ * csrc/alac_mel.h) and the fbank handle's entries (one translation unit of libalacgpu.so; nothing here touches the other
+ * kernels).
+ *
+ * One pass = launches of one kernel on the handle's stream:
+ *   alac_fbank_rows  one workgroup per tile (tile_frames consecutive frames of one row): the tile's inputs with 16-byte loads
+ *                    into LDS, Kaldi's reflection resolved there; the frames' energies out of that image; every lane the fmaf
+ *                    chains of blocks of 8 frames x 2 bins against the folded basis (mean removal, pre-emphasis, window and
+ *                    scale live in the table); the powers into an LDS tile, the mel chains and the log out of it; for MFCC the
+ *                    DCT and lifter out of the log-mel tile; the results through LDS into 16-byte stores
+ * No matrix instruction, no atomic; everything is written with vector stores.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "alac_fbank.h"
+#include "alac_host.h"
+
+using namespace alacfb;
+using alack::set_err;
+
+namespace {
+
+/* alac_fbank_rows goes in slices, each far below a dispatch's 2^32 work-items: 2^22 workgroups of 256 */
+constexpr uint64_t kTilesPerLaunch = (uint64_t)1 << 22;
+
+__global__ void __launch_bounds__(kThreads) alac_fbank_rows(Params p, uint64_t first_tile) {
+    extern __shared__ __attribute__((aligned(16))) float lds[]; /* the plan's lds_floats */
+    const uint64_t b = first_tile + blockIdx.x;
+    const uint64_t row = b / p.m.tiles_per_row;
+    if (row >= p.m.rows) return;
+    const Tile t = make_tile(p, row, b - row * p.m.tiles_per_row);
+    if (t.count == 0) return;
+    tile_phase(p, t, lds, 0u, threadIdx.x); /* stage */
+    __syncthreads();
+    tile_phase(p, t, lds, 1u, threadIdx.x); /* energies, DFT */
+    __syncthreads();
+    tile_phase(p, t, lds, 2u, threadIdx.x); /* mel, log */
+    __syncthreads();
+    if (p.num_ceps) {
+        tile_phase(p, t, lds, 3u, threadIdx.x); /* DCT, lifter */
+        __syncthreads();
+    }
+    tile_phase(p, t, lds, 4u, threadIdx.x); /* store */
+}
+
+} /* namespace */
+
+namespace alack {
+
+hipError_t fbank_launch(hipStream_t stream, const Params& p, uint32_t lds_bytes) {
+    if (p.m.rows == 0 || p.m.out_frames == 0) return hipSuccess;
+    const uint64_t tiles = p.m.rows * p.m.tiles_per_row;
+    for (uint64_t t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
+        const uint64_t m = tiles - t0 < kTilesPerLaunch ? tiles - t0 : kTilesPerLaunch;
+        hipLaunchKernelGGL(alac_fbank_rows, dim3((unsigned)m), dim3(kThreads), lds_bytes, stream, p, t0);
+    }
+    return hipGetLastError();
+}
+
+} /* namespace alack */
+
+/* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
+struct alacgpu_fbank {
+    int device = 0;
+    Plan plan;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; /* around the kernels of the last pass */
+    bool timed = false;
+    float* d_bt = nullptr;
+    float* d_fbw = nullptr;
+    int32_t* d_first = nullptr;
+    float* d_dct = nullptr;
+    float* d_lifter = nullptr;
+};
+
+namespace {
+void release(alacgpu_fbank* r) {
+    (void)hipSetDevice(r->device);
+    if (r->stream) (void)hipStreamSynchronize(r->stream);
+    if (r->d_bt) (void)hipFree(r->d_bt);
+    if (r->d_fbw) (void)hipFree(r->d_fbw);
+    if (r->d_first) (void)hipFree(r->d_first);
+    if (r->d_dct) (void)hipFree(r->d_dct);
+    if (r->d_lifter) (void)hipFree(r->d_lifter);
+    if (r->ev0) (void)hipEventDestroy(r->ev0);
+    if (r->ev1) (void)hipEventDestroy(r->ev1);
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    delete r;
+}
+
+Config config_of(const alacgpu_fbank_config* c) {
+    Config k;
+    k.sample_rate = c->sample_rate;
+    k.frame_length = c->frame_length;
+    k.frame_shift = c->frame_shift;
+    k.round_to_power_of_two = c->round_to_power_of_two;
+    k.num_mel_bins = c->num_mel_bins;
+    k.num_ceps = c->num_ceps;
+    k.snip_edges = c->snip_edges;
+    k.remove_dc_offset = c->remove_dc_offset;
+    k.window_type = c->window_type;
+    k.use_log_fbank = c->use_log_fbank;
+    k.use_energy = c->use_energy;
+    k.raw_energy = c->raw_energy;
+    k.htk_compat = c->htk_compat;
+    k.use_power = c->use_power;
+    k.log_energy = c->log_energy;
+    k.layout = c->layout;
+    k.preemphasis = c->preemphasis_coefficient;
+    k.blackman_coeff = c->blackman_coeff;
+    k.low_freq = c->low_freq;
+    k.high_freq = c->high_freq;
+    k.energy_floor = c->energy_floor;
+    k.scale = c->scale;
+    k.cepstral_lifter = c->cepstral_lifter;
+    k.dither = c->dither;
+    k.vtln_warp = c->vtln_warp;
+    return k;
+}
+
+/* a table on the device; an empty one still gets a block, so that the kernel's arguments are never NULL */
+template <typename T>
+hipError_t upload(T** d, const std::vector<T>& v) {
+    hipError_t h = hipMalloc((void**)d, (v.empty() ? 1 : v.size()) * sizeof(T));
+    if (h == hipSuccess && !v.empty()) h = hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    return h;
+}
+} /* namespace */
+
+extern "C" {
+
+int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu_fbank** out) {
+    if (!out || !config) {
+        if (out) *out = nullptr;
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    *out = nullptr;
+    alacgpu_fbank* r = new (std::nothrow) alacgpu_fbank();
+    if (!r) {
+        set_err("out of memory");
+        return ALACGPU_E_ARG;
+    }
+    if (!make_plan(config_of(config), &r->plan)) {
+        set_err("no Kaldi feature plan for frame_length %u, frame_shift %u at %u Hz, %u mel bins in [%g, %g] Hz, %u ceps: "
+                "frame_length in [1, %u], frame_shift >= 1, flags 0 or 1, window_type 0..4, layout 0..1, dither 0 (was %g), "
+                "vtln_warp 1 (was %g), use_power 1 (was %u), use_energy only with raw_energy, 1 <= num_mel_bins <= %u, num_ceps <= "
+                "num_mel_bins, finite numbers, scale not 0, energy_floor >= 0, 0 <= low_freq < Nyquist, 0 < high <= Nyquist, low < "
+                "high, every filter one run of weights, and four frames within %u bytes of LDS",
+                config->frame_length, config->frame_shift, config->sample_rate, config->num_mel_bins, config->low_freq,
+                config->high_freq, config->num_ceps, kMaxFft, config->dither, config->vtln_warp, config->use_power, kMaxMels,
+                kLdsFloats * 4u);
+        delete r;
+        return ALACGPU_E_ARG;
+    }
+    r->device = device;
+    const Plan& pl = r->plan;
+    hipError_t h = hipSetDevice(device);
+    if (h == hipSuccess) h = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
+    if (h == hipSuccess) h = hipEventCreate(&r->ev0);
+    if (h == hipSuccess) h = hipEventCreate(&r->ev1);
+    if (h == hipSuccess) h = upload(&r->d_bt, pl.bt);
+    if (h == hipSuccess) h = upload(&r->d_fbw, pl.fbw);
+    if (h == hipSuccess) h = upload(&r->d_first, pl.first);
+    if (h == hipSuccess) h = upload(&r->d_dct, pl.dct);
+    if (h == hipSuccess) h = upload(&r->d_lifter, pl.lifter);
+    if (h != hipSuccess) {
+        set_err("Kaldi feature handle creation failed: %s", hipGetErrorString(h));
+        release(r);
+        return ALACGPU_E_HIP;
+    }
+    *out = r;
+    return ALACGPU_E_OK;
+}
+
+void alacgpu_fbank_destroy(alacgpu_fbank* r) {
+    if (r) release(r);
+}
+
+void* alacgpu_fbank_stream(alacgpu_fbank* r) { return r ? (void*)r->stream : nullptr; }
+
+int alacgpu_fbank_synchronize(alacgpu_fbank* r) {
+    if (!r) return ALACGPU_E_ARG;
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_fbank_last_ms(alacgpu_fbank* r, float* ms) {
+    if (!r || !ms || !r->timed) {
+        set_err(!r || !ms ? "null argument" : "no feature pass on this handle yet");
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipEventSynchronize(r->ev1));
+    HIP_TRY(hipEventElapsedTime(ms, r->ev0, r->ev1));
+    return ALACGPU_E_OK;
+}
+
+uint64_t alacgpu_fbank_out_frames(const alacgpu_fbank* r, uint64_t in_frames) {
+    if (!r || in_frames > ((uint64_t)1 << 61)) return 0;
+    return out_frames_of(r->plan.W, r->plan.hop, r->plan.cfg.snip_edges, in_frames);
+}
+
+int alacgpu_fbank_plan(const alacgpu_fbank* r, alacgpu_fbank_info* info, float* basis_out, size_t basis_cap, float* fb_out,
+                       size_t fb_cap, int32_t* first_out, size_t first_cap, float* dct_out, size_t dct_cap, float* lifter_out,
+                       size_t lifter_cap) {
+    if (!r || !info) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    const Plan& pl = r->plan;
+    if ((basis_out && basis_cap < pl.basis.size()) || (fb_out && fb_cap < pl.fbw.size()) || (first_out && first_cap < pl.first.size()) ||
+        (dct_out && dct_cap < pl.dct.size()) || (lifter_out && lifter_cap < pl.lifter.size())) {
+        set_err("capacity below the plan's %zu basis / %zu filterbank / %zu first / %zu DCT / %zu lifter entries", pl.basis.size(),
+                pl.fbw.size(), pl.first.size(), pl.dct.size(), pl.lifter.size());
+        return ALACGPU_E_ARG;
+    }
+    info->frame_length = pl.W;
+    info->frame_shift = pl.hop;
+    info->n_fft = pl.N;
+    info->n_freqs = pl.K;
+    info->num_mel_bins = pl.n_mels;
+    info->taps = pl.taps;
+    info->num_ceps = pl.num_ceps;
+    info->cols = pl.cols;
+    info->tile_frames = pl.tile_frames;
+    info->lds_bytes = pl.lds_floats * 4u;
+    if (basis_out) memcpy(basis_out, pl.basis.data(), pl.basis.size() * sizeof(float));
+    if (fb_out) memcpy(fb_out, pl.fbw.data(), pl.fbw.size() * sizeof(float));
+    if (first_out) memcpy(first_out, pl.first.data(), pl.first.size() * sizeof(int32_t));
+    if (dct_out && !pl.dct.empty()) memcpy(dct_out, pl.dct.data(), pl.dct.size() * sizeof(float));
+    if (lifter_out && !pl.lifter.empty()) memcpy(lifter_out, pl.lifter.data(), pl.lifter.size() * sizeof(float));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_fbank_device(alacgpu_fbank* r, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
+                         size_t out_row_stride, size_t out_inner_stride, int sync) {
+    if (!r) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    if (rows == 0 || alacgpu_fbank_out_frames(r, in_frames) == 0) {
+        if (rows && in_frames > ((uint64_t)1 << 61)) {
+            set_err("Kaldi features: %zu samples are more than one pass takes", in_frames);
+            return ALACGPU_E_ARG;
+        }
+        return ALACGPU_E_OK;
+    }
+    Params p;
+    if (!make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, r->d_bt, r->d_fbw,
+                     r->d_first, r->d_dct, r->d_lifter, &p)) {
+        set_err("Kaldi features: a NULL or misaligned buffer, a stride (%zu in, %zu out rows, %zu out %s) below what it spans (%zu "
+                "samples, %llu frames of %u columns), or sizes that overflow", in_row_stride, out_row_stride, out_inner_stride,
+                r->plan.cfg.layout == kLayoutBins ? "bins" : "frames", in_frames,
+                (unsigned long long)alacgpu_fbank_out_frames(r, in_frames), r->plan.cols);
+        return ALACGPU_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipEventRecord(r->ev0, r->stream));
+    HIP_TRY(alack::fbank_launch(r->stream, p, r->plan.lds_floats * 4u));
+    HIP_TRY(hipEventRecord(r->ev1, r->stream));
+    r->timed = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(r->stream));
+    return ALACGPU_E_OK;
+}
+
+} /* extern "C" */

@@ -1,0 +1,37 @@
+/*
+ * fbank_shim.cpp — TEST-ONLY C entry point over saprobe-alac_amd/host/kaldi_features.hpp, so the Python test-suite can drive
+ * it with ctypes (GPU, links libalacgpu).
+ */
+#include <cstdint>
+#include <cstring>
+
+#include "../../saprobe-alac_amd/host/kaldi_features.hpp"
+
+extern "C" {
+
+static thread_local char g_msg[1024];
+const char* fbank_shim_last_error() { return g_msg; }
+
+static int fail(int kind, const char* what) {
+    strncpy(g_msg, what, sizeof(g_msg) - 1);
+    return -kind;
+}
+
+/* A KaldiFeatures for *config, one pass over device pointers (sync), and what it reports: OutFrames, the ten numbers of Plan()'s
+ * info and LastMs. -> 0, -6 for std::invalid_argument (no plan, or arguments the pass refuses), -5 for anything else */
+long fbank_shim_run(const alacgpu_fbank_config* config, const float* d_in, size_t in_stride, size_t rows, size_t in_frames,
+                    float* d_out, size_t out_row_stride, size_t out_inner_stride, uint64_t* out_frames, uint32_t* info, float* ms) {
+    try {
+        auto kf = alac::NewKaldiFeatures(*config);
+        *out_frames = kf->OutFrames(in_frames);
+        const alac::KaldiPlan pl = kf->Plan();
+        memcpy(info, &pl.info, 10 * sizeof(uint32_t));
+        if (pl.basis.size() != (size_t)2 * pl.info.n_freqs * pl.info.frame_length) return fail(5, "basis size");
+        kf->FeaturesDevice(d_in, in_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, true);
+        *ms = kf->LastMs();
+    } catch (const std::invalid_argument& e) { return fail(6, e.what());
+    } catch (const std::exception& e) { return fail(5, e.what()); }
+    return 0;
+}
+
+}  // extern "C"
