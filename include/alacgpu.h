@@ -558,7 +558,8 @@ int alacgpu_mel_plan(const alacgpu_mel* mel, alacgpu_mel_info* info, float* basi
  *             column 0, or the last column with htk_compat; log_energy = 0 keeps the sum itself (for checks)
  *     MFCC    num_ceps > 0: the log-mel (always logged) times D[c][m] = sqrt(2 / M) cos(pi (m + 0.5) c / M) (row 0: sqrt(1 /
  *             M)), a chain over m upwards, times 1 + 0.5 L sin(pi c / L) where L = cepstral_lifter != 0; with use_energy
- *             column 0 is the energy; with htk_compat column 0 moves to the end
+ *             column 0 is the energy; with htk_compat column 0 moves to the end, and without use_energy it is then sqrt(2)
+ *             C0, as in Kaldi's MfccComputer and torchaudio (row 0 of D is sqrt(2 / M) there)
  * cols = M (+ 1 with use_energy) for fbank, num_ceps for MFCC. Up to the logs every build gives the same bits.
  * alacgpu_fbank_create is ALACGPU_E_ARG, before any HIP call, when no plan can be built: frame_length outside [1, 2048],
  * frame_shift 0, sample_rate 0, a flag above 1, window_type or layout outside its values, dither != 0, vtln_warp != 1,

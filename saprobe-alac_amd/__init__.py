@@ -1241,7 +1241,8 @@ def _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps
 class KaldiFeatures:
     """float32 rows -> Kaldi's fbank (num_ceps 0) or MFCC features on one MI355X (include/alacgpu.h: alacgpu_fbank_*). Lengths
     are in samples here; kaldi_fbank / kaldi_mfcc take torchaudio's milliseconds. layout "frames" gives [..., F, cols], "bins"
-    [..., cols, F]. log_energy=False keeps the energy column unlogged (for checks). ValueError when no plan can be built:
+    [..., cols, F]. log_energy=False keeps the energy column unlogged (for checks). MFCC with htk_compat and without use_energy
+    ends in sqrt(2) C0 (plan()["dct"][0] is sqrt(2 / num_mel_bins) there). ValueError when no plan can be built:
     dither != 0, vtln_warp != 1, use_power False and use_energy without raw_energy among them, before any HIP call.
     Single-caller, bound to one device and one stream."""
 
@@ -1399,7 +1400,8 @@ def kaldi_mfcc(waveform, sample_frequency=16000, blackman_coeff=0.42, cepstral_l
                preemphasis_coefficient=0.97, raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True, snip_edges=True,
                subtract_mean=False, use_energy=False, vtln_warp=1.0, window_type="povey", scale=1.0, layout="frames", device=None):
     """torchaudio.compliance.kaldi.mfcc(waveform, ...) in one pass on the device: as kaldi_fbank, -> [..., F, num_ceps] (1 <=
-    num_ceps <= num_mel_bins)."""
+    num_ceps <= num_mel_bins). Column 0 is C0, or the log energy with use_energy; htk_compat moves it to the end, and where
+    it is C0 (no use_energy) it leaves there as sqrt(2) C0, as in Kaldi and torchaudio."""
     if isinstance(num_ceps, bool) or int(num_ceps) != num_ceps or int(num_ceps) < 1:
         raise ValueError("num_ceps is an integer in [1, num_mel_bins]")
     return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, num_mel_bins=num_mel_bins,

@@ -32,7 +32,9 @@
  *   MFCC     over the log-mel (always log): D[c][m] = sqrt(2 / M) cos(pi (m + 0.5) c / M), row 0 sqrt(1 / M), c < num_ceps <=
  *            M, in double, rounded once; acc = +0.0f; for m upwards acc = fmaf(D[c][m], logmel[m], acc); times lifter[c] =
  *            float(1 + 0.5 L sin(pi c / L)) (1 where L = 0). With use_energy column 0 is the energy instead; with htk_compat
- *            column 0 moves to the end.
+ *            column 0 moves to the end, and where that column is C0 itself (htk_compat without use_energy) it leaves as
+ *            sqrt(2) C0, as Kaldi's MfccComputer and torchaudio ("removing a scale we previously added") do: the plan's row 0
+ *            is then sqrt(2 / M), in double, rounded once (lifter[0] is 1), and the kernel only permutes.
  *   output   float32. Layout frames: [rows][F][cols], element (r, f, c) at out + r * row_stride + f * frame_stride + c.
  *            Layout bins: [rows][cols][F], element (r, c, f) at out + r * row_stride + c * bin_stride + f, as the mel pass
  *            writes. Exactly those elements are written.
@@ -408,10 +410,12 @@ inline bool make_plan(const Config& c, Plan* out) {
     if (c.num_ceps) {
         pl.dct.assign((size_t)c.num_ceps * M, 0.0f);
         pl.lifter.assign(c.num_ceps, 1.0f);
+        /* row 0: sqrt(1 / M); times sqrt(2) where C0 itself leaves in the last column (htk_compat without use_energy) */
+        const float row0 = round_once(std::sqrt(((c.htk_compat && !c.use_energy) ? 2.0 : 1.0) / (double)M));
         for (uint32_t q = 0; q < c.num_ceps; q++) {
             for (uint32_t m = 0; m < M; m++)
                 pl.dct[(size_t)q * M + m] = q ? round_once(std::sqrt(2.0 / (double)M) * std::cos(pi * ((double)m + 0.5) * (double)q / (double)M))
-                                              : (float)std::sqrt(1.0 / (double)M);
+                                              : row0;
             if (c.cepstral_lifter != 0.0)
                 pl.lifter[q] = (float)(1.0 + 0.5 * c.cepstral_lifter * std::sin(pi * (double)q / c.cepstral_lifter));
         }

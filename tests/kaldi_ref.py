@@ -7,7 +7,8 @@ table of both suites; and the host build of that header (tests/host_sim/fbank_si
     (index i < 0 is -1 - i, i >= T is 2 T - 1 - i) at f h - (W / 2 - h / 2) + n; no frame for T < W
     per frame: v = scale x; v -= mean(v); energy = sum v^2; y[n] = v[n] - c v[n - 1], v[-1] = v[0]; y *= window; zeros up to N
     p = |rfft(y)|^2;  mel = fb p, fb = Kaldi's get_mel_banks in double, rounded to float32;  ln(max(., 2^-23))
-    MFCC = lifter[c] * sum_m D[c][m] logmel[m]"""
+    MFCC = lifter[c] * sum_m D[c][m] logmel[m]; htk_compat moves column 0 to the end, and where that is C0 (no use_energy)
+    it leaves as sqrt(2) C0: D's row 0 is sqrt(2 / M) there"""
 import ctypes
 import math
 import os
@@ -178,9 +179,11 @@ def folded(cfg):
 
 
 def dct_matrix(cfg):
+    """[ceps, M]; row 0 is sqrt(1 / M), or sqrt(2 / M) where C0 itself leaves in the last column (htk_compat without use_energy:
+    Kaldi and torchaudio multiply it by sqrt(2) there), so that arrange only permutes"""
     M = cfg.mels
     D = math.sqrt(2.0 / M) * np.cos(np.pi * (np.arange(M)[None, :] + 0.5) * np.arange(cfg.ceps)[:, None] / M)
-    D[0] = math.sqrt(1.0 / M)
+    D[0] = math.sqrt((2.0 if cfg.htk and not cfg.energy else 1.0) / M)
     return D
 
 
@@ -499,6 +502,8 @@ def impulse_cfg(cfg):
 # ---- the parameter cases, shared by the CPU and the GPU suite ------------------------------------------------------------
 # name -> (Cfg, tile_frames by the LDS rule). The path each case runs is the issue's table's.
 W10 = Cfg(8000, 10, 4)
+MF13 = Cfg(8000, 50, 20, ceps=13)
+E_SCALE_FLOOR = 2.0 ** 30  # at scale 32768 the energy of a frame whose unscaled sum of squares is 1: mr.signal has both kinds
 CASES = {
     "w8": (Cfg(8000, 8, 4, mels=4), 64),                                  # W = N
     "w10": (W10, 64),                                                     # W < N, one block and a tail of 2
@@ -527,7 +532,28 @@ CASES = {
     "mfcc13_l0": (Cfg(8000, 50, 20, ceps=13, lifter=0.0), 64),            # no lifter
     "mfcc23": (Cfg(8000, 50, 20, ceps=23), 64),                           # num_ceps = M
     "mfcc_e_htk": (Cfg(8000, 50, 20, ceps=13, energy=True, htk=True), 64),
+    "mfcc_htk": (MF13.with_(htk=True), 64),                               # C0 last, times sqrt(2)
+    "mfcc_e": (MF13.with_(energy=True), 64),                              # energy in column 0, no permutation
+    "mfcc_ns": (MF13.with_(snip=False), 64),                              # MFCC over reflected frames
+    "mfcc_c1": (Cfg(8000, 50, 20, ceps=1), 64),                           # cols 1
+    "mfcc_asr": (Cfg(16000, 400, 160, mels=23, ceps=13), 32),             # torchaudio's default MFCC
+    "mfcc_hires": (Cfg(16000, 400, 160, mels=40, ceps=40, energy=True, htk=True, snip=False), 32),  # ceps = M, everything on
+    "mfcc_full": (Cfg(48000, 2048, 2048, pow2=False, ceps=13, energy=True), 4),  # c_off behind a full tile
+    "mfcc_many": (Cfg(16000, 64, 16, mels=2048, ceps=1024), 4),           # DCT chains of 2048, 4096 items per tile
+    "m1": (W10.with_(mels=1), 64),                                        # cols 1 in store_frames
+    "m2e": (W10.with_(mels=2, energy=True), 64),                          # cols 3
+    "e_nodc": (W10.with_(energy=True, dc=False), 64),                     # mean = 0
+    "e_ns9": (Cfg(8000, 9, 5, snip=False, energy=True), 64),              # energy of reflected frames
+    "e_h37": (Cfg(8000, 16, 37, energy=True, htk=True), 64),              # h > W: fs = W, sh = 0
+    "e_h37ns": (Cfg(8000, 16, 37, energy=True, snip=False), 64),
+    "e_scale": (W10.with_(energy=True, scale=32768.0, efloor=E_SCALE_FLOOR), 64),  # scale2; energies on both sides of the floor
+    "e_full": (Cfg(48000, 2048, 2048, pow2=False, energy=True), 4),       # sums of 2048 per work item
+    "e_many_first": (Cfg(16000, 64, 16, mels=2048, energy=True), 4),      # mel_off = tile_frames, output tile above the staging
+    "e_many_last": (Cfg(16000, 64, 16, mels=2048, energy=True, htk=True), 4),
+    "e_asr": (Cfg(16000, 400, 160, mels=80, energy=True), 32),
 }
+# the LDS rule leaves this one nothing: 16 516 floats at tile_frames 4
+NO_LDS = Cfg(16000, 64, 16, mels=2048, ceps=2048)
 SMALL = [k for k, (c, _) in CASES.items() if c.W <= 64 and c.mels <= 128]
 IMPULSE_CASES = ["w8", "w10", "w3", "w7", "ns10", "ns9", "h37", "h37ns"]
 
@@ -545,3 +571,140 @@ def impulse_batch(name):
     T = length_for(cfg, tf + 3)
     js = sorted(set(range(0, min(T, 3 * cfg.W))) | set(range(max(0, T - 2 * cfg.W), T)))
     return cfg, T, js
+
+
+# ---- checks that both suites run: `run(cfg, x)` is a build's pass, x [R, T] float32 -> [R, F, cols] float32 ----------------
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+ARRANGE_MFCC = Cfg(8000, 50, 20, ceps=13, scale=32768.0)
+
+
+def check_arrangement(run):
+    """Where use_energy and htk_compat put the columns, from a build's own outputs alone (no restatement): one signal through the
+    four handles (use_energy, htk_compat) of MFCC (W 50, h 20, F 65, 13 ceps, scale 32768) and of fbank (w10). With A the plain
+    MFCC: htk_compat alone gives A's columns 1..12 bit for bit and then sqrt(2) A[..., 0] within both passes' bounds (a missing
+    factor is 0.41 |C0|, which the input keeps above 100 bounds in every frame); use_energy alone A's columns 1..12 behind the
+    energy column of the fbank pass; both, A's 1..12 and then that energy. fbank: the mel columns and the energy column are the
+    same bits wherever they stand. -> the largest error / bound of the sqrt(2) C0 column"""
+    base = ARRANGE_MFCC
+    x = signal(np.random.default_rng(33), 3, length_for(base, 65))
+    A = run(base, x)
+    H = run(base.with_(htk=True), x)
+    E = run(base.with_(energy=True), x)
+    EH = run(base.with_(energy=True, htk=True), x)
+    assert A.shape == H.shape == E.shape == EH.shape == (3, 65, 13)
+    pre = run(base.prelog(), x)
+    lim_a = log_of_prelog(base, pre)[1]
+    lim_h = log_of_prelog(base.with_(htk=True), pre)[1]
+    lim = lim_a[..., 0] * math.sqrt(2.0) + lim_h[..., 12]
+    c0 = A[..., 0].astype(np.float64)
+    assert (0.4 * np.abs(c0) > 100.0 * lim).all(), "the input does not separate C0 from sqrt(2) C0"
+    assert same_bits(H[..., :12], A[..., 1:])
+    err = np.abs(H[..., 12].astype(np.float64) - math.sqrt(2.0) * c0)
+    worst = np.unravel_index((err / lim).argmax(), err.shape)
+    assert (err <= lim).all(), "htk_compat: the last column is not sqrt(2) C0: off by %g, bound %g" % (err[worst], lim[worst])
+    fb_e = Cfg(8000, 50, 20, energy=True, scale=32768.0)
+    energy = run(fb_e, x)[..., 0]
+    assert same_bits(E[..., 1:], A[..., 1:]) and same_bits(E[..., 0], energy)
+    assert same_bits(EH[..., :12], A[..., 1:]) and same_bits(EH[..., 12], energy)
+    assert len(np.unique(energy)) > 100 and not same_bits(energy, A[..., 0])
+    # fbank over w10
+    y = signal(np.random.default_rng(34), 3, length_for(W10, 65))
+    P = run(W10, y)
+    assert same_bits(run(W10.with_(htk=True), y), P)
+    first, last = run(W10.with_(energy=True), y), run(W10.with_(energy=True, htk=True), y)
+    assert first.shape == last.shape == (3, 65, 24)
+    assert same_bits(first[..., 1:], P) and same_bits(last[..., :23], P) and same_bits(first[..., 0], last[..., 23])
+    assert len(np.unique(first[..., 0])) > 50
+    return float((err / lim).max())
+
+
+SPECIAL_CASES = ["w10", "e_first_1", "e_first_0", "ns9", "asr"]
+LOG_EPS32 = np.float32(math.log(EPS))
+
+
+def special_input(name):
+    """-> (cfg, T, mr.special_rows at T = length_for(tile_frames + 2))"""
+    cfg, tf = CASES[name]
+    T = length_for(cfg, tf + 2)
+    return cfg, T, mr.special_rows(np.random.default_rng(tf + cfg.W), T)
+
+
+def check_special_unlogged(cfg, T, x, P):
+    """P [6, F, cols] = the unlogged pass over mr.special_rows: rows 0, 1 and 3 finite, zeros give +0.0 in every column, and in
+    the rows with one infinity / one NaN exactly the frames that read that sample are non-finite, in every column"""
+    assert np.isfinite(P[[0, 1, 3]]).all()
+    assert not P[0].view(np.uint32).any(), "zeros do not give +0.0"
+    assert not (P[np.isfinite(P)] < 0).any() and not np.isneginf(P).any()
+    idx = frame_index(cfg, T)
+    for r, at in ((4, T // 3), (5, 2 * T // 3)):
+        reads = (idx == at).any(axis=1)
+        assert reads.any() and (~reads).any()
+        assert np.isfinite(P[r][~reads]).all() and not np.isfinite(P[r][reads]).any(), "row %d" % r
+    assert np.isposinf(P).any() and np.isnan(P).any()
+
+
+def check_special_logged(cfg, got, P, what):
+    """got = the logging fbank pass of cfg over the input whose unlogged pass gave P (same build, same columns): +inf where P is,
+    a NaN exactly where P is one, and the finite values as kr.check_logged holds them (float32(ln 2^-23) bit for bit where P <=
+    2^-23) -> the largest error / bound"""
+    assert not cfg.ceps and got.shape == P.shape
+    inf, nan = np.isposinf(P), np.isnan(P)
+    assert np.isposinf(got[inf]).all(), what + ": the log of +inf"
+    assert np.array_equal(np.isnan(got), nan), what + ": the log of a NaN"
+    fin = ~(inf | nan)
+    want, lim, exact = log_of_prelog(cfg, np.where(fin, P, np.float32(1.0)))
+    pinned = want.astype(np.float32)
+    assert (got.view(np.uint32) == pinned.view(np.uint32))[exact & fin].all(), what + ": a floored value is not exact"
+    mels = np.ones(P.shape, bool)
+    if cfg.energy:
+        mels[..., cfg.mels if cfg.htk else 0] = False
+    low = fin & mels & (P <= np.float32(EPS))
+    if cfg.log:
+        assert low.any() and (got[low].view(np.uint32) == LOG_EPS32.view(np.uint32)).all(), what + ": at or below 2^-23"
+    err = np.abs(got.astype(np.float64) - want)
+    free = fin & ~exact
+    assert (err[free] <= lim[free]).all(), what + ": a log above its bound"
+    return float((err[free] / lim[free]).max())
+
+
+def check_silence_mfcc(run, name):
+    """A row of zeros through an MFCC case: every log-mel is ln(2^-23), so the coefficients are the DCT of a constant (C0 =
+    sqrt(M) ln(2^-23), the others 0 but for the table's rounding) within kr.log_of_prelog's bound, and the energy column is the
+    floor, bit for bit"""
+    cfg, tf = CASES[name]
+    x = np.zeros((2, length_for(cfg, tf + 2)), np.float32)
+    pre = run(cfg.prelog(), x)
+    assert not pre.view(np.uint32).any()
+    got = run(cfg, x)
+    share = check_logged(cfg, got, pre, name + " silence")
+    want = np.einsum("cm,m->c", dct_matrix(cfg), np.full(cfg.mels, math.log(EPS))) * lifter(cfg)
+    want = arrange(cfg, np.broadcast_to(want, got.shape), np.zeros(got.shape[:2]))
+    lim = log_of_prelog(cfg, pre)[1] + U * np.abs(want) * 2  # the table's own rounding of D and of the lifter
+    body = np.ones(got.shape[-1], bool)
+    if cfg.energy:
+        e_col = cfg.ceps - 1 if cfg.htk else 0
+        body[e_col] = False
+        floor = np.float32(math.log(cfg.efloor)) if cfg.efloor > 0.0 else LOG_EPS32
+        assert (got[..., e_col].view(np.uint32) == floor.view(np.uint32)).all()
+    assert (np.abs(got.astype(np.float64) - want)[..., body] <= lim[..., body]).all()
+    return share
+
+
+def check_constant(run, sim_plan_of):
+    """A row of constant 0.5 with DC removal, where Kaldi has exact zeros behind the mean's removal and the folded tables leave
+    their rounding: unlogged within kr.prelog_bounds at scale 1 and 32768 -> {scale: the largest mel value}"""
+    out = {}
+    for scale in (1.0, 32768.0):
+        cfg = CASES["e_first_1"][0].with_(scale=scale).prelog()
+        x = np.full((1, length_for(cfg, 66)), 0.5, np.float32)
+        got = run(cfg, x)
+        ref, lim = prelog_bounds(cfg, sim_plan_of(cfg), x)
+        assert not ref.any(), "the restatement has exact zeros"
+        assert_within(got, ref, lim, "constant 0.5 at scale %g" % scale)
+        assert not got[..., 0].view(np.uint32).any(), "the energy of a constant is +0.0"
+        out[scale] = float(got[..., 1:].max())
+    return out

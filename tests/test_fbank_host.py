@@ -7,7 +7,9 @@ tests/kaldi_ref.py, which does not fold anything and so tests the folding.
     * whole sentinel-filled buffers at every base offset, odd strides, a frame stride above cols; rows 1 and 3
     * unlogged values within the derived ceilings (kr.prelog_bounds); logged values and MFCC against the float64 ln (and DCT) of
       the build's own unlogged values
-    * impulses bit for bit from the tables alone; the refusals"""
+    * impulses bit for bit from the tables alone; the refusals
+    * where use_energy and htk_compat put the columns, and sqrt(2) C0, from the build's own outputs alone (kr.check_arrangement)
+    * zeros, denormals, huge values, -0.0, an infinity and a NaN; silence through MFCC; a constant row"""
 import numpy as np
 import pytest
 
@@ -99,6 +101,8 @@ def test_refusals(sim):
         assert kr.sim_plan(sim, bad) is None
     assert kr.sim_plan(sim, ok.with_(W=2048, h=2048, pow2=False)) is not None
     assert kr.sim_plan(sim, ok.with_(W=1025, h=2048))["n_fft"] == 2048
+    assert kr.lds_rule(kr.NO_LDS) == (4, 16516) and kr.sim_plan(sim, kr.NO_LDS) is None  # four frames do not fit LDS
+    assert kr.sim_plan(sim, kr.NO_LDS.with_(ceps=2015))["lds_bytes"] == 65536  # and the largest that does
     # what the entry refuses: strides below what they span, misaligned or NULL buffers
     x = mr.aligned(64, 0)
     out = mr.aligned(4096, 0)
@@ -140,6 +144,8 @@ def test_host_build_against_the_restatement(sim, name):
             img, lay = kr.sim_image(sim, cfg, x)
             got = kr.values_of(img, lay, cfg, rows, T, what)
             worst_log = max(worst_log, kr.check_logged(cfg, got, pre, what))
+            if name == "e_scale" and rows == 3:  # its floor lies between the energies of the signal's rows
+                assert (pre[..., 0] > cfg.efloor).any() and (pre[..., 0] < cfg.efloor).any() and (pre[..., 0] > kr.EPS).all()
             for j, (out_off, in_off) in enumerate(kr.OFFSETS[1:] if small else kr.OFFSETS[1:2]):
                 img, lay = kr.sim_image(sim, cfg, x, in_off, out_off, 3)
                 assert np.array_equal(img, kr.image_of(cfg, got, img.size, lay)), "%s offsets %d/%d" % (what, in_off, out_off)
@@ -147,7 +153,8 @@ def test_host_build_against_the_restatement(sim, name):
     assert 0 < worst <= 1
 
 
-@pytest.mark.parametrize("name", ["w10", "ns9", "h37ns", "e_last_1", "mfcc_e_htk", "asr"])
+@pytest.mark.parametrize("name", ["w10", "ns9", "h37ns", "e_last_1", "mfcc_e_htk", "asr", "mfcc_htk", "mfcc_c1", "mfcc_many", "m2e",
+                                  "e_many_first"])
 def test_layout_bins_is_the_transpose(sim, name):
     cfg, tf = kr.CASES[name]
     rng = np.random.default_rng(11)
@@ -174,19 +181,59 @@ def test_impulses_are_table_entries(sim, name):
     assert want.any() and (cfg.snip or sum(twice) > 0), "no frame saw its impulse twice through the reflection"
 
 
+def test_column_arrangement(sim):
+    """kr.check_arrangement on the host build: the place of every column and the factor of C0 under htk_compat, without the
+    restatement"""
+    share = kr.check_arrangement(lambda cfg, x: kr.host_values(sim, cfg, x))
+    print("sqrt(2) C0: largest error / bound %.3f" % share)
+
+
+@pytest.mark.parametrize("name", kr.SPECIAL_CASES)
+def test_other_float_values(sim, name):
+    """mr.special_rows through the host build. Unlogged: rows 0 and 3 (zeros; a signal with -0.0) within the ceilings of the
+    restatement, the denormal row below the normal range (its powers underflow, which the ceilings do not model), and
+    kr.check_special_unlogged; the case's own logging pass over the same rows: kr.check_special_logged"""
+    cfg, T, x = kr.special_input(name)
+    pre_cfg = cfg.prelog()
+    P = kr.host_values(sim, pre_cfg, x)
+    kr.check_special_unlogged(pre_cfg, T, x, P)
+    ref, lim = kr.prelog_bounds(pre_cfg, kr.sim_plan(sim, pre_cfg), x[[0, 3]])
+    kr.assert_within(P[[0, 3]], ref, lim, name + " rows 0 and 3")
+    assert (P[1] < 2.0 ** -126).all()
+    got = kr.host_values(sim, cfg, x)
+    share = kr.check_special_logged(cfg, got, P, name)
+    if cfg.energy:
+        floor = np.float32(0.0) if cfg.efloor > 0.0 else kr.LOG_EPS32
+        assert cfg.efloor in (0.0, 1.0) and (got[0, :, 0].view(np.uint32) == floor.view(np.uint32)).all()
+    print("%s: largest error / bound of the logs %.3f" % (name, share))
+
+
+@pytest.mark.parametrize("name", ["mfcc13", "mfcc_e_htk", "mfcc_htk"])
+def test_silence_through_mfcc(sim, name):
+    print("%s: %.3f of the bound" % (name, kr.check_silence_mfcc(lambda cfg, x: kr.host_values(sim, cfg, x), name)))
+
+
+def test_constant_row(sim):
+    """What the folded mean removal leaves of a constant 0.5: within the ceilings; the figures are DESIGN.md §15's"""
+    left = kr.check_constant(lambda cfg, x: kr.host_values(sim, cfg, x), lambda cfg: kr.sim_plan(sim, cfg))
+    print("constant 0.5: largest mel value %s" % ", ".join("%.3g at scale %g" % (v, s) for s, v in left.items()))
+
+
 def test_restatement_is_torchaudio():
-    """Where torchaudio is installed: the restatement against kaldi.fbank / kaldi.mfcc within 1e-5 relative of the largest value"""
+    """Where torchaudio is installed: the restatement against kaldi.fbank / kaldi.mfcc within 1e-5 relative of the largest value,
+    over snip_edges x use_energy x htk_compat, the five windows, remove_dc_offset off and round_to_power_of_two off"""
     kaldi = pytest.importorskip("torchaudio.compliance.kaldi")
     import torch
     rng = np.random.default_rng(3)
     x = kr.signal(rng, 1, 4000)
-    for snip in (True, False):
-        for energy in (False, True):
-            cfg = kr.Cfg(16000, 400, 160, mels=40, snip=snip, energy=energy)
-            want = kaldi.fbank(torch.from_numpy(x), num_mel_bins=40, snip_edges=snip, use_energy=energy, dither=0.0).double().numpy()
+    base = kr.Cfg(16000, 400, 160, mels=40)
+    sets = [base.with_(snip=snip, energy=energy, htk=htk) for snip in (True, False) for energy in (False, True) for htk in (False, True)]
+    sets += [base.with_(window=w) for w in kr.WINDOWS] + [base.with_(window=w, htk=True, snip=False) for w in kr.WINDOWS]
+    sets += [base.with_(dc=False), base.with_(dc=False, energy=True), base.with_(pow2=False), base.with_(pow2=False, htk=True)]
+    for c in sets:
+        kw = dict(num_mel_bins=40, snip_edges=c.snip, use_energy=c.energy, htk_compat=c.htk, window_type=c.window,
+                  remove_dc_offset=c.dc, round_to_power_of_two=c.pow2, dither=0.0)
+        for cfg, fn in ((c, kaldi.fbank), (c.with_(ceps=13), kaldi.mfcc)):
+            want = fn(torch.from_numpy(x), **kw).double().numpy()
             got = kr.features64(cfg, x, kr.mel_banks(cfg))[0]
-            assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max()
-            cfg = kr.Cfg(16000, 400, 160, mels=40, ceps=13, snip=snip, energy=energy)
-            want = kaldi.mfcc(torch.from_numpy(x), num_mel_bins=40, snip_edges=snip, use_energy=energy, dither=0.0).double().numpy()
-            got = kr.features64(cfg, x, kr.mel_banks(cfg))[0]
-            assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max()
+            assert got.shape == want.shape and np.abs(got - want).max() <= 1e-5 * np.abs(want).max(), kw

@@ -4,7 +4,9 @@ every case of kr.CASES, and within the derived ceilings against the step-by-step
 fbank, log energy, MFCC) are held to the float64 ln (and DCT, lifter) of the device's own bit-checked unlogged values from that
 second pass, within twice the 2.23 float32 ulps DESIGN.md §14 measured for this device's logf; values at or below 2^-23 give
 ln(2^-23) exactly. Impulses come out as table entries; sync=False, both layouts, the Python entries (kaldi_fbank, kaldi_mfcc)
-and host/kaldi_features.hpp through tests/host_sim/fbank_shim.cpp are covered.
+and host/kaldi_features.hpp through tests/host_sim/fbank_shim.cpp are covered; so are the place of every column and sqrt(2)
+C0 under htk_compat from the device's own outputs (kr.check_arrangement), the layout bins of every case with a DCT or an energy
+column, samples outside the audio range, silence, a constant row, calls without work and kaldi_fbank behind load_clips.
 
 The values of the host build do not depend on where the buffers lie (tests/test_fbank_host.py runs it at every offset), so it
 runs once per (parameters, rows, length) here and the device is held to its values at every offset.
@@ -15,7 +17,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests import clip_ref as cr
 from tests import kaldi_ref as kr
+from tests import m4a
 from tests import mel_ref as mr
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +54,13 @@ def device_image(torch, kf, cfg, x, in_off=0, out_off=0, pad=0, sync=True):
     if not sync:
         kf.synchronize()
     return buf.cpu().numpy().view(np.uint32), lay
+
+
+def device_values(torch, pkg, cfg, x, in_off=1, out_off=2, pad=1):
+    """[rows, F, cols] float32 of a fresh handle's pass, everything outside the output checked to be the sentinel"""
+    with pkg.NewKaldiFeatures(**cfg.kwargs()) as kf:
+        img, lay = device_image(torch, kf, cfg, x, in_off, out_off, pad)
+    return kr.values_of(img, lay, cfg, x.shape[0], x.shape[1], "device pass")
 
 
 def assert_same_image(img, want, what, lay):
@@ -185,3 +196,133 @@ def test_cpp_entry(torch, pkg, sim):
     c.dither = 0.0
     assert shim.fbank_shim_run(ctypes.addressof(c), d_in.data_ptr(), T, 3, T, d_out.data_ptr(), F * cfg.cols, cfg.cols - 1,
                                ctypes.addressof(frames), ctypes.addressof(info), ctypes.addressof(ms)) == -6
+
+
+def test_column_arrangement(torch, pkg):
+    """kr.check_arrangement on the device: the place of every column and the factor of C0 under htk_compat, without the
+    restatement and without the host build"""
+    share = kr.check_arrangement(lambda cfg, x: device_values(torch, pkg, cfg, x))
+    print("sqrt(2) C0 on the device: largest error / bound %.3f" % share)
+
+
+@pytest.mark.parametrize("name", [k for k, (c, _) in kr.CASES.items() if c.ceps or c.energy])
+def test_layout_bins_of_the_dct_and_energy_passes(torch, pkg, name):
+    """Every case with a DCT or an energy column, its own configuration (logs, DCT and all) at F = tile_frames + 1, rows 3: the
+    whole image of layout="bins" (offsets 1 / 3, a bin stride of F + 3) is the transpose of the layout frames' output of the same
+    parameters, bit for bit, and the sentinel everywhere else. For MFCC this is alacmel::store_tile out of the cepstral tile."""
+    cfg, tf = kr.CASES[name]
+    x = kr.signal(np.random.default_rng(12), 3, kr.length_for(cfg, tf + 1))
+    want = device_values(torch, pkg, cfg, x)
+    bins = cfg.with_(layout="bins")
+    with pkg.NewKaldiFeatures(**bins.kwargs()) as kf:
+        img, lay = device_image(torch, kf, bins, x, 3, 1, 3)
+    assert want.shape == (3, tf + 1, cfg.cols) and len(np.unique(want)) > tf + 1  # (with 2048 bins most are at the floor)
+    assert_same_image(img, kr.image_of(bins, want, img.size, lay), name + " layout bins", lay)
+
+
+@pytest.mark.parametrize("name", kr.SPECIAL_CASES)
+def test_other_float_values(torch, pkg, sim, name):
+    """Zeros, denormals, values whose powers overflow, -0.0, an infinity and a NaN (mr.special_rows). Unlogged: where the host
+    build has a NaN the device has one too, whatever its payload, and every other word is equal; kr.check_special_unlogged. Then
+    the case's own logging pass against the device's unlogged values (kr.check_special_logged), and the floors of the energy of
+    silence."""
+    cfg, T, x = kr.special_input(name)
+    pre_cfg = cfg.prelog()
+    y = kr.host_values(sim, pre_cfg, x)
+    with pkg.NewKaldiFeatures(**pre_cfg.kwargs()) as kf:
+        for out_off, in_off in ((0, 0), (1, 3)):
+            img, lay = device_image(torch, kf, pre_cfg, x, in_off, out_off, 2)
+            want = kr.image_of(pre_cfg, y, img.size, lay)
+            nan = np.isnan(want.view(np.float32))
+            assert nan.any() and np.isnan(img.view(np.float32)[nan]).all(), "a NaN of the host build is none on the device"
+            assert_same_image(np.where(nan, 0, img), np.where(nan, 0, want), "%s offsets %d/%d" % (name, in_off, out_off), lay)
+    P = kr.values_of(img, lay, pre_cfg, 6, T, name)
+    kr.check_special_unlogged(pre_cfg, T, x, P)
+    got = device_values(torch, pkg, cfg, x, 2, 1, 3)
+    share = kr.check_special_logged(cfg, got, P, name)
+    if cfg.energy:
+        floor = np.float32(0.0) if cfg.efloor > 0.0 else kr.LOG_EPS32
+        assert cfg.efloor in (0.0, 1.0) and (got[0, :, 0].view(np.uint32) == floor.view(np.uint32)).all()
+    print("%s: largest error / bound of the logs on the device %.3f" % (name, share))
+
+
+@pytest.mark.parametrize("name", ["mfcc13", "mfcc_e_htk", "mfcc_htk"])
+def test_silence_through_mfcc(torch, pkg, name):
+    print("%s: %.3f of the bound on the device" % (name, kr.check_silence_mfcc(lambda cfg, x: device_values(torch, pkg, cfg, x), name)))
+
+
+def test_constant_row(torch, pkg, sim):
+    """What the folded mean removal leaves of a constant 0.5 on the device: within the ceilings, and the host build's bits"""
+    def run(cfg, x):
+        got = device_values(torch, pkg, cfg, x)
+        assert kr.same_bits(got, kr.host_values(sim, cfg, x))
+        return got
+    left = kr.check_constant(run, lambda cfg: kr.sim_plan(sim, cfg))
+    print("constant 0.5 on the device: largest mel value %s" % ", ".join("%.3g at scale %g" % (v, s) for s, v in left.items()))
+
+
+def test_small_inputs_and_no_work(torch, pkg):
+    """Calls without work, which touch nothing, and what the entry refuses before a launch; a plan that does not fit LDS"""
+    with pytest.raises(ValueError):
+        pkg.NewKaldiFeatures(**kr.NO_LDS.kwargs())
+    for cfg in (kr.W10, kr.W10.with_(layout="bins")):
+        T = 30
+        F, cols = kr.out_frames(cfg, T), cfg.cols  # 6 frames of 23
+        lines, length = kr.out_shape(cfg, F)
+        span = (lines - 1) * length + length
+        with pkg.NewKaldiFeatures(**cfg.kwargs()) as kf:
+            buf = torch.full((1024,), 7.0, dtype=torch.float32, device="cuda:0")
+            torch.cuda.synchronize()
+            B = buf.data_ptr()
+            O = B + 2048
+            kf.features_device(B, T, 0, T, O, span, length)            # no rows
+            kf.features_device(B, T, 2, cfg.W - 1, O, span, length)    # rows shorter than a frame
+            kf.features_device(None, 0, 0, 0, None, 0, 0)
+            kf.synchronize()
+            assert bool((buf == 7.0).all().item())
+            for bad in [(None, T, 2, T, O, span, length), (B, T, 2, T, None, span, length), (B + 2, T, 2, T, O, span, length),
+                        (B + 1, T, 2, T, O, span, length), (B, T, 2, T, O + 1, span, length), (B, T, 2, T, O + 2, span, length),
+                        (B, T - 1, 2, T, O, span, length), (B, T, 2, T, O, span, length - 1), (B, T, 2, T, O, span - 1, length),
+                        (B, 1 << 62, 2, T, O, span, length), (B, T, 2, T, O, 1 << 62, length), (B, T, 2, T, O, 1 << 62, 1 << 62)]:
+                with pytest.raises(ValueError):
+                    kf.features_device(*bad)
+            kf.synchronize()
+            assert bool((buf == 7.0).all().item())
+            with pytest.raises(ValueError):
+                kf.last_ms()  # nothing was launched
+            kf.features_device(B, T, 2, T, O, span, length)  # and the same arguments, in order, are a pass
+            assert kf.last_ms() > 0 and not bool((buf[512:512 + 2 * span] == 7.0).any().item()) and bool((buf[:512] == 7.0).all().item())
+
+
+FL = 256
+
+
+@pytest.fixture(scope="module")
+def files(oracle, synth, tmp_path_factory):
+    """Two small 16-bit stereo files, at 44 100 and at 16 000 Hz -> paths"""
+    d = tmp_path_factory.mktemp("fbank")
+    made = []
+    for name, rate, seed in (("a44", 44100, 1), ("b16", 16000, 2)):
+        cfg = oracle.make_config(FL, 16, 2, sample_rate=rate)
+        path = d / (name + ".m4a")
+        path.write_bytes(m4a.write_m4a(cfg, cr.file_packets(oracle, synth, cfg, 12, seed)))
+        made.append(str(path))
+    return made
+
+
+def test_fbank_of_loaded_clips(torch, pkg, files):
+    """kaldi_fbank(load_clips(..., sample_rate=16000)[0], 16000, ...) is the pass over the same tensor through the raw-pointer
+    entry, there into a buffer with a frame stride of cols + 2 whose padding stays untouched."""
+    L = 1200
+    clips, lengths, rate = pkg.load_clips(files, [100, 7], L, sample_rate=16000)
+    assert rate == 16000 and tuple(clips.shape) == (2, 2, L) and bool(clips.any().item())
+    got = pkg.kaldi_fbank(clips, 16000, num_mel_bins=40, use_energy=True)
+    F, cols = 1 + (L - 400) // 160, 41
+    assert tuple(got.shape) == (2, 2, F, cols)
+    out = torch.full((4, F, cols + 2), -7.0, dtype=torch.float32, device="cuda:0")
+    flat = clips.contiguous().reshape(4, L)
+    torch.cuda.synchronize()
+    with pkg.NewKaldiFeatures(16000, 400, 160, num_mel_bins=40, use_energy=True) as kf:
+        kf.features_device(flat.data_ptr(), L, 4, L, out.data_ptr(), F * (cols + 2), cols + 2, sync=True)
+    assert torch.equal(out[:, :, :cols].view(torch.int32), got.reshape(4, F, cols).view(torch.int32))
+    assert bool((out[:, :, cols:] == -7.0).all()) and len(torch.unique(got)) > got.numel() // 2

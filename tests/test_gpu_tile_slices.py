@@ -1,5 +1,6 @@
-"""The second launch of the five tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
-alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip), alac_wave_pack (k_wavepack.hip) and alac_mel_rows (k_mel.hip). Each launch gets the slice's
+"""The second launch of the six tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
+alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip), alac_wave_pack (k_wavepack.hip), alac_mel_rows (k_mel.hip) and
+alac_fbank_rows (k_fbank.hip). Each launch gets the slice's
 first tile as first_tile; only a batch of more than 2^22 tiles has a second slice, and a launch that lost its first_tile would
 corrupt such batches alone, silently.
 
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import clip_ref as cr
+from tests import kaldi_ref as kr
 from tests import mel_ref as mr
 from tests import resample_ref as rr
 from tests import wave_ref as wr
@@ -211,3 +213,30 @@ def test_second_launch_of_alac_mel_rows(torch, pkg):
         ms.mel_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, K * F, F, sync=True)
     assert_cycle(torch, buf[LEAD:LEAD + N * K * F], np.ascontiguousarray(want7).view(np.int32), "rows")
     assert_guards(buf, N * K * F, fill)
+
+
+def test_second_launch_of_alac_fbank_rows(torch, pkg):
+    """N rows of 4 samples, frame length 4, shift 4, one mel bin and the energy column, nothing logged: one frame of 2 columns,
+    tile_frames 64, so tiles_per_row = 1, tile = row and the second launch has first_tile = 2^22. Row r is class r % 7; the
+    expectation is the host build's output for the 7 rows (67 MB in, 34 MB out).
+
+    A launch that ignored first_tile would compute rows 0 .. 4 098 again and leave the rows from 2^22 on unwritten (the
+    sentinel); one that wrote to the slice's rows but read from the batch's start would give row 2^22 + j the features of row
+    j, whose class j % 7 is not (2^22 + j) % 7."""
+    sim = kr.build_fbank_sim()
+    cfg = kr.Cfg(8000, 4, 4, mels=1, energy=True, log=False, log_energy=False)
+    T, F, cols = 4, 1, 2
+    rows7 = np.random.default_rng(15).uniform(-1, 1, (7, T)).astype(np.float32)
+    rows7[3] = [1.0, -1.0, 1.0, -1.0]
+    want7 = kr.host_values(sim, cfg, rows7)
+    assert kr.out_frames(cfg, T) == F and want7.shape == (7, F, cols)
+    assert all(len(set(want7[:, 0, c].tolist())) == 7 for c in range(cols)), "the 7 rows are not distinct in both columns"
+    x = cycled(torch, rows7, N)
+    fill = mr.SENTINEL - (1 << 32)
+    buf = sentinel_buffer(torch, N * cols, fill, torch.int32)
+    torch.cuda.synchronize()
+    with pkg.NewKaldiFeatures(**cfg.kwargs()) as kf:
+        assert kf.out_frames(T) == F and N * -(-F // kf.plan()["tile_frames"]) > SLICE
+        kf.features_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, cols, cols, sync=True)
+    assert_cycle(torch, buf[LEAD:LEAD + N * cols], np.ascontiguousarray(want7).view(np.int32), "rows")
+    assert_guards(buf, N * cols, fill)
