@@ -32,6 +32,13 @@
 
 namespace alac {
 
+/* ALAC_WRAP_COUNTDOWN, set per translation unit (as ALAC_LDS_ROWS is): 1 = the int16-wrap test of the wrapping orders runs
+ * by countdown (predict_chunk) instead of once per chunk. On in k_dec16q.hip, where it pays (profiles/chunk_sync/); every
+ * other unit keeps the per-chunk test and with it the code it had: any edit of these loops moves a whole kernel's schedule,
+ * and the 24- and 32-bit kernels lost 0.6-1.0 % to that with nothing to gain back. */
+#ifndef ALAC_WRAP_COUNTDOWN
+#define ALAC_WRAP_COUNTDOWN 0
+#endif
 constexpr uint32_t DUO_CHUNK = 16;     /* steps per queue buffer (a multiple of 8) */
 constexpr int DUO_UN8_MAX = 12;        /* longest predictor whose steady-state groups are 8 steps (else 4) */
 enum { ROLE_A = 0, ROLE_B = 1, ROLE_BOTH = 2, ROLE_C = 3 };
@@ -81,6 +88,9 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     constexpr bool U16_OUT = F16 && EC && OUT == OUT_UTILE;
     constexpr bool C16 = F16 && EC && CPE && EMIT_A;
     const uint32_t na = GEN ? na_rt : (uint32_t)NA;
+#ifdef ALAC_SYNC_DIAG /* (alac_gpu.h: the diagnostic build keeps its sums per phase) */
+    wv.dg_phase = LAST ? 1u : 0u;
+#endif
     uint32_t kb = cfg.kb;
     ALAC_OWN_REG(kb); /* its own register: cfg is an 8-dword kernel-argument tuple that would otherwise be pulled out
                          of its spill slot, whole, in every step of the entropy loop (8 v_readlane per step) */
@@ -475,6 +485,10 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     };
     /* B: samples of chunk c (UnpcBlock, predictor.go:45-684): out[0] = residual, warm-up up to na (:53-79),
      * copy (0) / delta (31) modes, then the adaptive taps */
+#if ALAC_WRAP_COUNTDOWN
+    /* int16-wrapping orders: whole chunks from here on in which no coefficient can reach the int16 limits (predict_chunk) */
+    uint32_t wrap_safe = 0;
+#endif
     auto predict_chunk = [&](uint32_t c) {
         const uint32_t buf = c & 1u;
         const bool simple = GEN && (na == 0 || na == 31);
@@ -575,6 +589,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
                 }
                 groups(wrap, fp_no{});
             };
+#if !ALAC_WRAP_COUNTDOWN
             if (WRAP) {
                 /* A coefficient moves by at most 1 per step, so one that is further than a chunk away from the
                  * int16 limits cannot wrap inside this chunk: test once per chunk and run the chunk without the
@@ -588,9 +603,35 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
                     return;
                 }
             }
+#else
+            if (WRAP) {
+                /* A coefficient moves by at most 1 per step: a step adds sign(e) * sign(del) or nothing to it
+                 * (predictor.go:664,675). One that is D steps away from the int16 limits therefore cannot wrap within
+                 * the next D steps, and a chunk that starts with every coefficient of the wave at least CH steps away
+                 * runs without the per-tap, per-step sign extension (one instruction of ten). The distance is not looked
+                 * at in every chunk: a test that finds the nearest coefficient D steps away answers for the next
+                 * D / CH chunks, this one included (before step t of them the distance is at least D - t >= 1), and
+                 * wrap_safe counts them down. Real coefficients are thousands of steps away. D = 32767 - (c ^ (c >> 31))
+                 * is exact on both sides (32767 and -32768 are 0 steps away); lanes without a packet hold zeros. */
+                if (wrap_safe == 0u) {
+                    uint32_t mag = 0;
+#pragma unroll
+                    for (int j = 0; j < NR; ++j) mag = umax(mag, (uint32_t)(coef[j] ^ (coef[j] >> 31)));
+                    wrap_safe = (32767u - wv.max_u32(mag)) / CH;
+                }
+                if (wrap_safe != 0u) {
+                    --wrap_safe;
+                    run_groups(wrap_no{});
+                    return;
+                }
+            }
+#endif
             run_groups(wrap_yes{});
             return;
         }
+#if ALAC_WRAP_COUNTDOWN
+        wrap_safe = 0; /* (the steps below keep the coefficients in int16: the next whole chunk looks again) */
+#endif
 #pragma nounroll
         for (uint32_t j = 0; j < CH; ++j) {
             const uint32_t i = c * CH + j;
@@ -776,6 +817,9 @@ ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, u
         } else if (!LAST) *wv.u_row(i) = o; /* every lane of the group stores the same value to the packet's cell */
         else wv.rq_write(buf, CH + k, o);
     };
+#if ALAC_WRAP_COUNTDOWN
+    uint32_t wrap_safe = 0; /* whole chunks from here on in which no coefficient can reach the int16 limits (duo_phase) */
+#endif
     auto predict_chunk = [&](uint32_t cc) {
         const uint32_t i0 = cc * CH, buf = cc & 1u;
         const uint32_t nst = umin(CH, n_it - i0);
@@ -798,6 +842,7 @@ ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, u
 #pragma unroll
                 for (uint32_t k = 0; k < CH; ++k) put(buf, k, i0 + k, step(i0 + k, dv[k], yes{}, wrap_c));
             };
+#if !ALAC_WRAP_COUNTDOWN
             if (wraps) {
                 /* a coefficient moves by at most 1 per step: one that is further than a chunk away from the int16 limits
                  * cannot wrap inside this chunk (predict_chunk of duo_phase) */
@@ -810,9 +855,30 @@ ALAC_DEV void duo_phase_lanes(W& wv, const B& bits, uint32_t q, uint32_t n_it, u
                     return;
                 }
             }
+#else
+            if (wraps) {
+                /* a coefficient moves by at most 1 per step (predictor.go:664,675): the nearest one D steps away from the
+                 * int16 limits answers for the next D / CH chunks, counted down in wrap_safe (predict_chunk of duo_phase;
+                 * the lanes' unused taps hold zeros) */
+                if (wrap_safe == 0u) {
+                    uint32_t mag = 0;
+#pragma unroll
+                    for (int t = 0; t < T; ++t) mag = umax(mag, (uint32_t)(coef[t] ^ (coef[t] >> 31)));
+                    wrap_safe = (32767u - wv.max_u32(mag)) / CH;
+                }
+                if (wrap_safe == 0u) {
+                    run(yes{});
+                    return;
+                }
+                --wrap_safe;
+            }
+#endif
             run(no{});
             return;
         }
+#if ALAC_WRAP_COUNTDOWN
+        wrap_safe = 0;
+#endif
 #pragma nounroll
         for (uint32_t k = 0; k < nst; ++k) {
             const uint32_t nd = (uint32_t)wv.rq_read(buf, k);

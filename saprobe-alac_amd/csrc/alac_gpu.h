@@ -219,6 +219,21 @@ static __shared__ __attribute__((aligned(16))) uint32_t s_ring[kRingSlots * kWav
 constexpr uint32_t kQ = alac::DUO_CHUNK;
 static __shared__ int32_t s_rq[2 * kQ * kWave];
 
+/* dwords per wave slot behind the plan (PairArgs::claims). ALAC_SYNC_DIAG: a build for tools/chunk_sync.py only, never the
+ * shipped one: the waves of the ungated four-wave kernels time their stay at the chunk barrier (GpuWave::duo_sync) and leave
+ * the sums in a wider record: [4 role + 2 phase] cycles inside duo_sync, [.. + 1] chunks in which the wave arrived last
+ * (role 0 entropy, 1 predictor, 2 writer; phase 0 U, 1 the last channel); [14] the entropy wave's cycles in the slot; [15] key.
+ * "Last" is read off one counter per workgroup, zeroed once when the workgroup starts: wave number (old + 1) of a round of
+ * dg_waves arrivals is the last. That holds because every wave that takes part goes through GpuWave::duo_sync the same
+ * number of times (each call is one barrier all of them share) and nothing else touches the counter: duo_sync_mem and the
+ * kernel's own __syncthreads are other barriers and are not counted. */
+#ifdef ALAC_SYNC_DIAG
+constexpr uint32_t kClaimDw = 16;
+static __shared__ uint32_t s_dg_arrive; /* waves that have reached a chunk barrier so far */
+#else
+constexpr uint32_t kClaimDw = 4;
+#endif
+
 /* U hand-off tile of one wave: frame_length rows of 64 cells and one spare row (the single-wave decoders read one
  * row ahead) */
 __host__ __device__ inline size_t u_tile_cells(uint32_t frame_length) { return ((size_t)frame_length + 1u) * kWave; }
@@ -232,6 +247,10 @@ struct GpuWave {
     uint8_t* my_out;
     uint32_t lane, wcnt, flushed;
     uint32_t ppw;              /* packets (= live lanes) per wave; also the row stride of the HBM tiles */
+#ifdef ALAC_SYNC_DIAG
+    uint32_t dg_wait[2] = {0, 0}, dg_last[2] = {0, 0}; /* per phase (kClaimDw) */
+    uint32_t dg_phase = 0, dg_waves = 3; /* dg_waves: waves of the workgroup that meet at the barrier */
+#endif
 
     ALAC_DEV bool any(bool p) const { return __ballot(p) != 0ull; }
     ALAC_DEV uint32_t max_u32(uint32_t v) const {
@@ -404,7 +423,19 @@ struct GpuWave {
     }
     /* chunk hand-over between the two waves of the workgroup: LDS traffic only, so outstanding global loads
      * (ring refills, U prefetch) and stores (U tile) are NOT waited for — __syncthreads() would drain them */
+#ifndef ALAC_SYNC_DIAG
     ALAC_DEV void duo_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+#else
+    ALAC_DEV void duo_sync() {
+        const uint64_t t0 = __builtin_amdgcn_s_memtime();
+        uint32_t old = 0;
+        if ((threadIdx.x & (kWave - 1u)) == 0u) old = atomicAdd(&s_dg_arrive, 1u);
+        old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        dg_wait[dg_phase] += (uint32_t)(__builtin_amdgcn_s_memtime() - t0);
+        dg_last[dg_phase] += (old + 1u) % dg_waves == 0u ? 1u : 0u;
+    }
+#endif
     /* end of the U phase: wave B's tile stores must have landed before wave A loads them */
     ALAC_DEV void duo_sync_mem() {
         __threadfence_block();
@@ -533,7 +564,7 @@ struct PairArgs {
     int32_t* status;
     int32_t* scratch_u;
     const uint32_t* cu_number; /* 1 + the number of each CU (indexed like Plan::gate), 0 for CUs the census did not see */
-    uint32_t* claims; /* four words per wave slot of the plan, zeroed before every decode: whoever sets the first decodes the slot */
+    uint32_t* claims; /* kClaimDw (four) words per wave slot of the plan, zeroed before every decode: whoever sets the first decodes the slot */
     uint32_t ppw;
     uint32_t n_cu; /* compute units of the device */
     uint32_t cap;  /* pairs one of them holds */

@@ -219,7 +219,7 @@ struct alacgpu_decoder {
 namespace {
 
 size_t plan_claims_offset() { return (sizeof(Plan) + 255u) & ~(size_t)255u; }
-size_t plan_bytes(size_t waves) { return plan_claims_offset() + waves * 4 * sizeof(uint32_t); }
+size_t plan_bytes(size_t waves) { return plan_claims_offset() + waves * kClaimDw * sizeof(uint32_t); }
 
 /* What launch() asks the runtime about a kernel, asked once per kernel: the cache is keyed by the kernel's address (every
  * pair kernel has the same function type, so a function-local static of a template on that type would be ONE cache for
@@ -1145,9 +1145,9 @@ int alacgpu_pair_placement(alacgpu_decoder* d, uint32_t* tags, size_t max_n, siz
     if (!d->plan.p) return ALACGPU_E_OK;
     Plan head;
     HIP_TRY(hipMemcpy(&head, d->plan.p, sizeof(Plan), hipMemcpyDeviceToHost));
-    const size_t n = std::min<size_t>(head.total_waves, max_n / 4);
+    const size_t n = std::min<size_t>(head.total_waves, max_n / kClaimDw);
     if (plan_bytes(n) > d->plan.cap) return ALACGPU_E_ARG;
-    if (n) HIP_TRY(hipMemcpy(tags, (const uint8_t*)d->plan.p + plan_claims_offset(), n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(tags, (const uint8_t*)d->plan.p + plan_claims_offset(), n * kClaimDw * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *n_out = n;
     return ALACGPU_E_OK;
 }

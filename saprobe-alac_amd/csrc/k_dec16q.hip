@@ -23,6 +23,8 @@
 /* 26 KB of static LDS: five of these workgroups fit a CU ("fit 5"); launched with a dynamic-LDS pad for four (alac_gpu.h: decode_mode) */
 #define ALAC_LDS_ROWS 32
 #define ALAC_LDS_FLUSH 32
+/* the int16-wrap test by countdown (alac_duo.h): 65 536 packets 2.047 -> 2.020 ms; the other widths' kernels lose by it */
+#define ALAC_WRAP_COUNTDOWN 1
 #include "alac_gpu.h"
 
 #define ALAC_DECODE_KERNEL alac_decode_16q

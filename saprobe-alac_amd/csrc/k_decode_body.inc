@@ -89,6 +89,25 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
     wv.my_out = nullptr;
     wv.lane = lane;
     wv.wcnt = wv.flushed = wv.wpos = wv.fpos = 0;
+#if defined(ALAC_SYNC_DIAG) && ALAC_DECODE_ROLES == 4
+    /* (alac_gpu.h: kClaimDw) the first lane of a wave leaves its sums in the slot's record; of two predictor waves the first */
+    wv.dg_waves = (lanes_on && ppw > per_wave) ? 4u : 3u;
+    const uint64_t dg_t0 = __builtin_amdgcn_s_memtime();
+#define ALAC_DG_RECORD(R)                                                       \
+    if ((threadIdx.x & (kWave - 1u)) == 0u) {                                   \
+        uint32_t* rec = pair_args()->claims + kClaimDw * b;                     \
+        rec[4u * (R)] = wv.dg_wait[0];                                          \
+        rec[4u * (R) + 1u] = wv.dg_last[0];                                     \
+        rec[4u * (R) + 2u] = wv.dg_wait[1];                                     \
+        rec[4u * (R) + 3u] = wv.dg_last[1];                                     \
+        if ((R) == 0u) {                                                        \
+            rec[14] = (uint32_t)(__builtin_amdgcn_s_memtime() - dg_t0);         \
+            rec[15] = key;                                                      \
+        }                                                                       \
+    }
+#else
+#define ALAC_DG_RECORD(R)
+#endif
 
     /* lanes without a packet read nothing (size 0) */
     const uint64_t off = live ? ka->offsets[pkt] : 0ull;
@@ -107,6 +126,7 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
          * writer against 430 in the other two) */
         __builtin_amdgcn_s_setprio(ALAC_PRIO_C);
         (void)alac::decode_regular_duo<GpuWave, alac::ROLE_C, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC>(wv, cfg, ukey, live, p, size, avail, o, &frames);
+        ALAC_DG_RECORD(2u)
         return;
     }
 #else
@@ -134,6 +154,7 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
         else
             (void)alac::decode_regular_duo<GpuWave, alac::ROLE_B, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC, 2>(wv, cfg, ukey, live, p, size, avail, o, &frames,
                                                                                                            lane_q, ns_other);
+        if (role == 1u) { ALAC_DG_RECORD(1u) }
         return;
     }
 #endif
@@ -147,6 +168,7 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
         else if (na_max >= 6u && na_max != 31u) __builtin_amdgcn_s_setprio(ALAC_PRIO_B_MID);
         else __builtin_amdgcn_s_setprio(ALAC_PRIO_B_SHORT);
         (void)alac::decode_regular_duo<GpuWave, alac::ROLE_B, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC>(wv, cfg, ukey, live, p, size, avail, o, &frames);
+        ALAC_DG_RECORD(1u)
         return;
     }
     /* the entropy chain is serial: it issues whenever it can, shorter predictor waves (many independent
@@ -158,12 +180,14 @@ static __device__ __forceinline__ void pair_item(PairArgsPtr ka, uint32_t b, uin
         else __builtin_amdgcn_s_setprio(ALAC_PRIO_A);
     }
     const int32_t st = alac::decode_regular_duo<GpuWave, alac::ROLE_A, ALAC_DECODE_WIDE, ALAC_DECODE_DEPTH, EC>(wv, cfg, ukey, live, p, size, avail, o, &frames);
+    ALAC_DG_RECORD(0u)
     if (live) {
         PairArgsPtr kb = pair_args();
         kb->frames_out[pkt] = frames;
         kb->status[pkt] = st;
     }
 }
+#undef ALAC_DG_RECORD
 
 #if !ALAC_DECODE_GATED
 
@@ -217,6 +241,9 @@ __global__ void __launch_bounds__(ALAC_DECODE_ROLES * kWave, ALAC_DECODE_WAVES) 
             for (uint32_t w = 0; w < 4u; ++w)
                 if (s_simd[w] == k) spare = w;
             s_spare = spare;
+#ifdef ALAC_SYNC_DIAG
+            s_dg_arrive = 0u;
+#endif
         }
         __syncthreads();
         const uint32_t rel = (role + 4u - s_spare) & 3u; /* 0: the spare wave */
@@ -254,7 +281,7 @@ static __device__ __forceinline__ uint32_t pair_sweep(Plan* plan, uint32_t* clai
     for (;;) {
         const uint32_t t = atomicAdd(&plan->queue[ALAC_DECODE_WIDE], 1u);
         if (t >= items) return 0xffffffffu;
-        if (atomicCAS(&claims[4u * t], 0u, tag | 1u) == 0u) return t;
+        if (atomicCAS(&claims[kClaimDw * t], 0u, tag | 1u) == 0u) return t;
     }
 }
 
@@ -283,7 +310,7 @@ __global__ void __launch_bounds__(2 * kWave, ALAC_DECODE_WAVES) ALAC_DECODE_KERN
                 const uint32_t cu = ((xcc & 7u) << 6) | (((id >> 13) & 3u) << 4) | ((id >> 8) & 15u);
                 const uint32_t simd0 = (id >> 4) & 3u, simd1 = s_simd1;
                 const uint32_t quota = pair_quota(items, n_cu, ka->cap);
-                uint32_t* claims = ka->claims + 4u * first;
+                uint32_t* claims = ka->claims + kClaimDw * first;
                 const uint32_t j = atomicAdd(&plan->gate[ALAC_DECODE_WIDE][cu], 1u);
                 if (j < quota) {
                     /* Which of the two waves takes the entropy role: whichever leaves the CU's SIMDs most level. The
@@ -309,7 +336,7 @@ __global__ void __launch_bounds__(2 * kWave, ALAC_DECODE_WAVES) ALAC_DECODE_KERN
                      * there all have a pair of their own on the way (taking one now would be taking a slow one
                      * from a CU that is still filling up) */
                     if (r >= n_cu) item = pair_sweep(plan, claims, items, tag);
-                    else if (mine < items) item = atomicCAS(&claims[4u * mine], 0u, tag) == 0u ? mine : pair_sweep(plan, claims, items, tag);
+                    else if (mine < items) item = atomicCAS(&claims[kClaimDw * mine], 0u, tag) == 0u ? mine : pair_sweep(plan, claims, items, tag);
                 }
             }
             s_item = item;
@@ -330,10 +357,10 @@ __global__ void __launch_bounds__(2 * kWave, ALAC_DECODE_WAVES) ALAC_DECODE_KERN
         if (threadIdx.x == 0) {
             PairArgsPtr ka = pair_args();
             /* diagnostics (alacgpu_pair_placement): when the pair had the item */
-            uint32_t* rec = ka->claims + 4u * (first + item);
+            uint32_t* rec = ka->claims + kClaimDw * (first + item);
             rec[1] = (uint32_t)t0;
             rec[2] = (uint32_t)__builtin_amdgcn_s_memtime();
-            s_item = pair_sweep(ka->plan, ka->claims + 4u * first, items, s_tag);
+            s_item = pair_sweep(ka->plan, ka->claims + kClaimDw * first, items, s_tag);
         }
         __syncthreads();
     }
