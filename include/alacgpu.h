@@ -490,9 +490,21 @@ int alacgpu_resampler_plan(const alacgpu_resampler* rs, alacgpu_resample_info* i
  * positive float32; with a mel scale n_mels outside [1, 4096] or not 0 <= f_min < f_max; with ALACGPU_MEL_SCALE_NONE (the
  * power spectrogram itself is the output) n_mels or norm not 0; or four frames that do not fit 64 KB of LDS. The handle owns
  * a stream, an event pair and the tables on the device; it is single-caller, like a decoder.
+ *
+ * transform = ALACGPU_MEL_TRANSFORM_FFT (opt-in; k_melfft.hip, alac_melfft.h) computes p[k] by a mixed-radix FFT
+ * out of LDS in place of the chains over the basis; frames, mel, log and output are the same. n_fft must be even with M = n_fft /
+ * 2 = 2^a 3^b 5^c: any other n_fft is ALACGPU_E_ARG before any HIP call (there is no fall-back to the direct transform), and so is
+ * a transform above 1.
+ *     v[n]    = w32[n] * x[n], w32 the window above rounded to float32 once;  z[m] = v[2 m] + i v[2 m + 1]
+ *     Z       = FFT_M(z): in-place passes of radix 5, 3, 4, 2 in the plan's order, twiddles from float32 tables
+ *     X[k]    = (Z[k] + conj Z[M - k]) / 2 + exp(-2 pi i k / N) (Z[k] - conj Z[M - k]) / (2 i), k = 0 .. M, indices mod M
+ *     p[k]    = fmaf(im, im, re * re)
+ * with every float operation in a fixed order and none contracted (alac_melfft.h writes them out), so up to the log every build
+ * gives the same bits here too; they are not the direct transform's bits.
  */
 enum { ALACGPU_MEL_SCALE_NONE = 0, ALACGPU_MEL_SCALE_HTK = 1, ALACGPU_MEL_SCALE_SLANEY = 2 };
 enum { ALACGPU_MEL_LOG_NONE = 0, ALACGPU_MEL_LOG_LN = 1, ALACGPU_MEL_LOG_LOG10 = 2, ALACGPU_MEL_LOG_DB = 3 };
+enum { ALACGPU_MEL_TRANSFORM_DIRECT = 0, ALACGPU_MEL_TRANSFORM_FFT = 1 };
 typedef struct alacgpu_mel_config {
     uint32_t sample_rate;
     uint32_t n_fft;
@@ -504,7 +516,7 @@ typedef struct alacgpu_mel_config {
     uint32_t norm;       /* 0 none, 1 slaney */
     uint32_t mel_scale;  /* ALACGPU_MEL_SCALE_* */
     uint32_t log;        /* ALACGPU_MEL_LOG_* */
-    uint32_t reserved0;  /* 0 */
+    uint32_t transform;  /* ALACGPU_MEL_TRANSFORM_*; 0, the direct transform, is what a zeroed field asked for before */
     double floor;        /* > 0; read with a log only, but checked always */
 } alacgpu_mel_config;
 typedef struct alacgpu_mel alacgpu_mel;
@@ -537,6 +549,21 @@ typedef struct alacgpu_mel_info {
 } alacgpu_mel_info;
 int alacgpu_mel_plan(const alacgpu_mel* mel, alacgpu_mel_info* info, float* basis_out, size_t basis_cap, float* fb_out,
                      size_t fb_cap, int32_t* first_out, size_t first_cap);
+/* The plan of the handle's transform. On a handle with ALACGPU_MEL_TRANSFORM_FFT (whose alacgpu_mel_plan reports a basis of 0
+ * entries: none is built; basis_out is left alone): tile_frames and lds_bytes (the FFT's own choice, which alacgpu_mel_plan
+ * reports as well), batch_frames (the frames of a tile transformed at a time), pitch (complex elements between two frames in
+ * the transform buffer), the passes' radices in order, and (where the pointers are not NULL and the capacities suffice) the
+ * window w32[n_fft] and the twiddle table: 8 roots {-0.5, sin(2 pi / 3), cos, sin(2 pi / 5), cos, sin(4 pi / 5), 0, 0}, then per
+ * pass s (radix r, L = the product of the radices before it) L (r - 1) pairs {cos, -sin}(2 pi ((q k) mod (L r)) / (L r)) at [k][q
+ * - 1], then n_fft / 2 + 1 pairs {cos, -sin}(2 pi k / n_fft). On a direct handle transform is 0, tile_frames and lds_bytes are
+ * alacgpu_mel_plan's, and everything else is 0. */
+typedef struct alacgpu_mel_fft_info {
+    uint32_t transform, tile_frames, lds_bytes, batch_frames, pitch, n_passes;
+    uint32_t radix[8];
+    uint32_t window_entries, twiddle_entries;
+} alacgpu_mel_fft_info;
+int alacgpu_mel_fft_plan(const alacgpu_mel* mel, alacgpu_mel_fft_info* info, float* window_out, size_t window_cap,
+                         float* twiddle_out, size_t twiddle_cap);
 
 /*
  * KALDI FEATURES: float32 rows -> Kaldi's filterbank (fbank) or MFCC features, one fused pass on a handle of its own

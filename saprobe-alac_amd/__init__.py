@@ -283,6 +283,8 @@ _EXPORTS = {
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]),
     "alacgpu_mel_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
+    "alacgpu_mel_fft_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_size_t]),
     "alacgpu_fbank_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "alacgpu_fbank_destroy": (None, [ctypes.c_void_p]),
     "alacgpu_fbank_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
@@ -999,7 +1001,7 @@ class MelConfig(ctypes.Structure):
     _fields_ = [("sample_rate", ctypes.c_uint32), ("n_fft", ctypes.c_uint32), ("win_length", ctypes.c_uint32),
                 ("hop_length", ctypes.c_uint32), ("f_min", ctypes.c_double), ("f_max", ctypes.c_double), ("n_mels", ctypes.c_uint32),
                 ("center", ctypes.c_uint32), ("norm", ctypes.c_uint32), ("mel_scale", ctypes.c_uint32), ("log", ctypes.c_uint32),
-                ("reserved0", ctypes.c_uint32), ("floor", ctypes.c_double)]
+                ("transform", ctypes.c_uint32), ("floor", ctypes.c_double)]
 
 
 class MelInfo(ctypes.Structure):
@@ -1009,13 +1011,24 @@ class MelInfo(ctypes.Structure):
                                                "tile_frames", "lds_bytes")]
 
 
+class MelFftInfo(ctypes.Structure):
+    """alacgpu_mel_fft_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("transform", "tile_frames", "lds_bytes", "batch_frames", "pitch", "n_passes")] + [
+        ("radix", ctypes.c_uint32 * 8), ("window_entries", ctypes.c_uint32), ("twiddle_entries", ctypes.c_uint32)]
+
+
+_MEL_TRANSFORMS = {"direct": 0, "fft": 1}
 _MEL_SCALES = {"htk": 1, "slaney": 2}
 _MEL_LOGS = {None: 0, "ln": 1, "log10": 2, "db": 3}
 
 
-def _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor):
+def _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor,
+                transform="direct"):
     """The arguments of the Python entries -> MelConfig, defaults resolved; ValueError for what is no number of its kind or no
     name of an enum (what the numbers may be is the plan's to say)."""
+    if not isinstance(transform, str) or transform not in _MEL_TRANSFORMS:
+        raise ValueError("transform is 'direct' or 'fft', not %r" % (transform,))
     for v in (sample_rate, n_fft) + tuple(u for u in (win_length, hop_length, n_mels) if u is not None):
         if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError("sample_rate, n_fft, win_length, hop_length and n_mels are integers in [0, 2^32)")
@@ -1035,6 +1048,7 @@ def _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels
     c.f_max = float(int(sample_rate) / 2 if f_max is None else f_max)
     c.center = 1 if center else 0
     c.log, c.floor = _MEL_LOGS[log], float(floor)
+    c.transform = _MEL_TRANSFORMS[transform]
     if n_mels is not None:
         c.n_mels, c.norm, c.mel_scale = int(n_mels), 1 if norm == "slaney" else 0, _MEL_SCALES[mel_scale]
     return c
@@ -1044,13 +1058,17 @@ class MelSpectrogram:
     """float32 rows -> their power spectrograms (n_mels None) or (log-)mel spectrograms on one MI355X (include/alacgpu.h:
     alacgpu_mel_*): periodic Hann window, reflect padding when centred, |X|^2, torchaudio's melscale_fbanks, s log(max(v,
     floor)); the tables are built once per handle. ValueError when no plan can be built. Single-caller, bound to one device
-    and one stream."""
+    and one stream. transform="fft" (keyword only; the default "direct" is the fmaf chains over the basis) computes the powers by
+    a mixed-radix FFT: n_fft must be even with n_fft / 2 = 2^a 3^b 5^c, any other is a ValueError, never a fall-back; the result
+    is fixed bit for bit as well, but it is not the direct transform's."""
 
     def __init__(self, sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128, center=True,
-                 norm=None, mel_scale="htk", log=None, floor=1e-10, device=0):
+                 norm=None, mel_scale="htk", log=None, floor=1e-10, device=0, *, transform="direct"):
         self._h = ctypes.c_void_p()
         self._lib = lib()
-        self.config = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor)
+        self.config = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor,
+                                  transform)
+        self.transform = transform
         _check(self._lib.alacgpu_mel_create(device, ctypes.byref(self.config), ctypes.byref(self._h)))
         self.device = device
         self.bins = int(n_mels) if n_mels is not None else int(n_fft) // 2 + 1
@@ -1091,13 +1109,27 @@ class MelSpectrogram:
         filter's window) and first [n_mels] int32 (the bin of each window's first weight)."""
         info = MelInfo()
         _check(self._lib.alacgpu_mel_plan(self._h, ctypes.byref(info), None, 0, None, 0, None, 0))
-        basis = np.zeros((2, info.n_freqs, info.n_fft), np.float32)
+        basis = np.zeros((2, info.n_freqs, info.n_fft) if self.config.transform == 0 else (2, 0, info.n_fft), np.float32)
         fb = np.zeros((info.n_mels, info.taps), np.float32)
         first = np.zeros(info.n_mels, np.int32)
         _check(self._lib.alacgpu_mel_plan(self._h, ctypes.byref(info), basis.ctypes.data, basis.size, fb.ctypes.data, fb.size,
                                           first.ctypes.data, first.size))
         out = {k: int(getattr(info, k)) for k, _ in MelInfo._fields_}
         out.update(basis=basis, fb=fb, first=first)
+        return out
+
+    def fft_plan(self):
+        """alacgpu_mel_fft_plan -> dict: transform (0 direct, 1 fft), tile_frames, lds_bytes, batch_frames, pitch, n_passes, radix
+        (the passes' radices in order), and the tables window [n_fft] float32 and twiddle float32 (8 roots, each pass's twiddles,
+        the split step's n_fft / 2 + 1 pairs). On a direct handle: transform 0, no passes, empty tables."""
+        info = MelFftInfo()
+        _check(self._lib.alacgpu_mel_fft_plan(self._h, ctypes.byref(info), None, 0, None, 0))
+        window = np.zeros(info.window_entries, np.float32)
+        twiddle = np.zeros(info.twiddle_entries, np.float32)
+        _check(self._lib.alacgpu_mel_fft_plan(self._h, ctypes.byref(info), window.ctypes.data, window.size, twiddle.ctypes.data,
+                                              twiddle.size))
+        out = {k: int(getattr(info, k)) for k in ("transform", "tile_frames", "lds_bytes", "batch_frames", "pitch", "n_passes")}
+        out.update(radix=[int(r) for r in info.radix[:info.n_passes]], window=window, twiddle=twiddle)
         return out
 
     def last_ms(self):
@@ -1130,22 +1162,24 @@ class MelSpectrogram:
 
 
 def NewMelSpectrogram(sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128, center=True,
-                      norm=None, mel_scale="htk", log=None, floor=1e-10, device=0):
+                      norm=None, mel_scale="htk", log=None, floor=1e-10, device=0, *, transform="direct"):
     """A MelSpectrogram (context manager); ValueError where no plan can be built."""
-    return MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor, device)
+    return MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor, device,
+                          transform=transform)
 
 
 _MELS = {}  # (device, every field of the configuration) -> MelSpectrogram: a plan is built once per process
 
 
 def mel_spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128,
-                    center=True, norm=None, mel_scale="htk", log=None, floor=1e-10, device=None):
+                    center=True, norm=None, mel_scale="htk", log=None, floor=1e-10, device=None, *, transform="direct"):
     """torchaudio.transforms.MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels=n_mels, center=center,
     norm=norm, mel_scale=mel_scale)(waveform) with power 2, the periodic Hann window and reflect padding, and optionally s
     log(max(., floor)) (log: None, "ln", "log10", "db"), in one pass on the device: a float32 tensor [..., T] (CUDA, CPU or
     numpy; the last two are uploaded) -> [..., n_mels, F] on cuda:`device` (default: the tensor's own device, cuda:0 for a CPU
     tensor or a numpy array). n_mels None gives the power spectrogram [..., n_fft / 2 + 1, F]. Another dtype, parameters without
-    a plan or a T without a frame raise ValueError. The tables of a (device, parameter set) are built once and kept."""
+    a plan or a T without a frame raise ValueError. The tables of a (device, parameter set) are built once and kept.
+    transform="fft" takes the FFT in place of the direct transform (MelSpectrogram); the two have handles of their own."""
     import torch
     if isinstance(waveform, np.ndarray):
         if waveform.dtype != np.float32:
@@ -1154,7 +1188,7 @@ def mel_spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_lengt
         raise ValueError("waveform must be a float32 torch tensor or numpy array")
     if waveform.ndim < 1:
         raise ValueError("waveform must be [..., T]")
-    c = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor)
+    c = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor, transform)
     if isinstance(waveform, np.ndarray):
         waveform = torch.from_numpy(np.ascontiguousarray(waveform))
     if device is None:
@@ -1162,15 +1196,16 @@ def mel_spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_lengt
     key = (device,) + tuple(getattr(c, k) for k, _ in MelConfig._fields_)
     if key not in _MELS:
         _MELS[key] = MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log,
-                                    floor, device)
+                                    floor, device, transform=transform)
     return _MELS[key](waveform)
 
 
-def spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_length=None, center=True, log=None, floor=1e-10, device=None):
+def spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_length=None, center=True, log=None, floor=1e-10, device=None,
+                *, transform="direct"):
     """mel_spectrogram without the mel stage: the power spectrogram [..., n_fft / 2 + 1, F] (torchaudio.transforms.Spectrogram
     with power 2), sample_rate only naming the handle."""
     return mel_spectrogram(waveform, sample_rate, n_fft, win_length, hop_length, n_mels=None, center=center, log=log, floor=floor,
-                           device=device)
+                           device=device, transform=transform)
 
 
 def whisper_post(logmel):
@@ -1183,11 +1218,11 @@ def whisper_post(logmel):
     return (x + 4.0) / 4.0
 
 
-def whisper_log_mel(waveform, n_mels=80, device=None):
+def whisper_log_mel(waveform, n_mels=80, device=None, *, transform="direct"):
     """Whisper's log_mel_spectrogram of 16 kHz audio [..., T] -> [..., n_mels, T / 160]: the pass at n_fft 400, hop 160 with the
     slaney scale and norm and log10 at floor 1e-10, then whisper_post."""
     return whisper_post(mel_spectrogram(waveform, 16000, 400, 400, 160, 0.0, 8000.0, n_mels, True, "slaney", "slaney", "log10",
-                                        1e-10, device))
+                                        1e-10, device, transform=transform))
 
 
 # ---- Kaldi features (new: torchaudio.compliance.kaldi.fbank / .mfcc, one fused pass on the device) ---------------------

@@ -335,8 +335,9 @@ inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t* a_floats) {
 
 /* false: no plan for these arguments (N outside [2, 2048], W outside [1, N], hop 0, a sample rate of 0, an enum outside its
  * values, floor not a positive float32, with a mel stage n_mels outside [1, 4096] or not 0 <= f_min < f_max, without one n_mels
- * or norm not 0, or four frames that do not fit the LDS budget) */
-inline bool make_plan(const Config& c, Plan* out) {
+ * or norm not 0, or four frames that do not fit the LDS budget). with_basis false leaves basis and bt empty: the plan of a pass
+ * that brings its own transform (alac_melfft.h). */
+inline bool make_plan(const Config& c, Plan* out, bool with_basis = true) {
     if (c.n_fft < 2u || c.n_fft > kMaxFft || c.win_length < 1u || c.win_length > c.n_fft || c.hop_length < 1u || !c.sample_rate)
         return false;
     if (c.center > 1u || c.norm > 1u || c.mel_scale > kScaleSlaney || c.log > kLogDb) return false;
@@ -365,20 +366,22 @@ inline bool make_plan(const Config& c, Plan* out) {
     std::vector<double> w(N, 0.0);
     const uint32_t off = (N - W) / 2u;
     for (uint32_t j = 0; j < W; j++) w[off + j] = W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W);
-    pl.basis.assign((size_t)2 * K * N, 0.0f);
-    pl.bt.assign((size_t)N * pl.BP * 4u, 0.0f);
-    for (uint32_t k = 0; k < K; k++)
-        for (uint32_t n = 0; n < N; n++) {
-            const uint32_t r = (uint32_t)(((uint64_t)k * n) % N);
-            const double ang = 2.0 * pi * (double)r / (double)N;
-            const bool in = w[n] != 0.0; /* +0.0f, not the -0.0f a negative cosine would make of it, outside the window */
-            const float cv = in ? (float)(w[n] * std::cos(ang)) : 0.0f, sv = in ? (float)(w[n] * std::sin(ang)) : 0.0f;
-            pl.basis[((size_t)k) * N + n] = cv;
-            pl.basis[((size_t)K + k) * N + n] = sv;
-            float* e = &pl.bt[((size_t)n * pl.BP + k / 2u) * 4u + 2u * (k & 1u)];
-            e[0] = cv;
-            e[1] = sv;
-        }
+    if (with_basis) {
+        pl.basis.assign((size_t)2 * K * N, 0.0f);
+        pl.bt.assign((size_t)N * pl.BP * 4u, 0.0f);
+        for (uint32_t k = 0; k < K; k++)
+            for (uint32_t n = 0; n < N; n++) {
+                const uint32_t r = (uint32_t)(((uint64_t)k * n) % N);
+                const double ang = 2.0 * pi * (double)r / (double)N;
+                const bool in = w[n] != 0.0; /* +0.0f, not the -0.0f a negative cosine would make of it, outside the window */
+                const float cv = in ? (float)(w[n] * std::cos(ang)) : 0.0f, sv = in ? (float)(w[n] * std::sin(ang)) : 0.0f;
+                pl.basis[((size_t)k) * N + n] = cv;
+                pl.basis[((size_t)K + k) * N + n] = sv;
+                float* e = &pl.bt[((size_t)n * pl.BP + k / 2u) * 4u + 2u * (k & 1u)];
+                e[0] = cv;
+                e[1] = sv;
+            }
+    }
 
     if (pl.n_mels) {
         const uint32_t M = pl.n_mels;

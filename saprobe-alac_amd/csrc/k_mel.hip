@@ -9,6 +9,8 @@
  *                  the powers into an LDS tile, the mel chains and the log out of it; the results through LDS into 16-byte
  *                  stores along time
  * No matrix instruction, no atomic; everything is written with vector stores.
+ * A handle made with transform = ALACGPU_MEL_TRANSFORM_FFT runs alac_melfft_rows (k_melfft.hip over alac_melfft.h) in its place:
+ * it owns the window, twiddle and position tables and no basis.
  */
 #include <hip/hip_runtime.h>
 
@@ -16,6 +18,7 @@
 
 #include "alac_host.h"
 #include "alac_mel.h"
+#include "alac_melfft.h"
 
 using namespace alacmel;
 using alack::set_err;
@@ -67,6 +70,11 @@ struct alacgpu_mel {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr; /* around the kernels of the last pass */
     bool timed = false;
+    uint32_t transform = ALACGPU_MEL_TRANSFORM_DIRECT;
+    alacmelfft::Plan fft; /* transform = fft: the plan in use; `plan` then is its base */
+    float* d_w32 = nullptr;
+    float* d_tw = nullptr;
+    uint32_t* d_pos = nullptr;
     float* d_bt = nullptr;
     float* d_fbw = nullptr;
     int32_t* d_first = nullptr;
@@ -77,6 +85,9 @@ void release(alacgpu_mel* r) {
     (void)hipSetDevice(r->device);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
     if (r->d_bt) (void)hipFree(r->d_bt);
+    if (r->d_w32) (void)hipFree(r->d_w32);
+    if (r->d_tw) (void)hipFree(r->d_tw);
+    if (r->d_pos) (void)hipFree(r->d_pos);
     if (r->d_fbw) (void)hipFree(r->d_fbw);
     if (r->d_first) (void)hipFree(r->d_first);
     if (r->ev0) (void)hipEventDestroy(r->ev0);
@@ -117,7 +128,26 @@ int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel
         set_err("out of memory");
         return ALACGPU_E_ARG;
     }
-    if (!make_plan(config_of(config), &r->plan)) {
+    if (config->transform > ALACGPU_MEL_TRANSFORM_FFT) {
+        set_err("transform %u is neither ALACGPU_MEL_TRANSFORM_DIRECT (0) nor ALACGPU_MEL_TRANSFORM_FFT (1)", config->transform);
+        delete r;
+        return ALACGPU_E_ARG;
+    }
+    r->transform = config->transform;
+    if (r->transform == ALACGPU_MEL_TRANSFORM_FFT && !alacmelfft::size_ok(config->n_fft)) {
+        set_err("no FFT plan for n_fft %u: with transform = fft n_fft is even, in [2, %u], and n_fft / 2 = 2^a 3^b 5^c (the direct "
+                "transform takes every n_fft in that range)", config->n_fft, kMaxFft);
+        delete r;
+        return ALACGPU_E_ARG;
+    }
+    bool planned;
+    if (r->transform == ALACGPU_MEL_TRANSFORM_FFT) {
+        planned = alacmelfft::make_plan(config_of(config), &r->fft);
+        if (planned) r->plan = r->fft.base;
+    } else {
+        planned = make_plan(config_of(config), &r->plan);
+    }
+    if (!planned) {
         set_err("no spectrogram plan for n_fft %u, win_length %u, hop_length %u at %u Hz, %u mels in [%g, %g) Hz, floor %g: n_fft "
                 "in [2, %u], 1 <= win_length <= n_fft, hop_length >= 1, center and norm 0 or 1, mel_scale 0..2, log 0..3, floor a "
                 "positive float32; with a mel scale 1 <= n_mels <= %u and 0 <= f_min < f_max, without one n_mels and norm 0; and "
@@ -129,7 +159,8 @@ int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel
     }
     r->device = device;
     const Plan& pl = r->plan;
-    const size_t table = pl.bt.size() * sizeof(float);
+    const bool fft = r->transform == ALACGPU_MEL_TRANSFORM_FFT;
+    const size_t table = (pl.bt.empty() ? 1 : pl.bt.size()) * sizeof(float);
     const size_t fbw = (pl.fbw.empty() ? 1 : pl.fbw.size()) * sizeof(float);
     const size_t firsts = (pl.first.empty() ? 1 : pl.first.size()) * sizeof(int32_t);
     hipError_t h = hipSetDevice(device);
@@ -139,7 +170,16 @@ int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel
     if (h == hipSuccess) h = hipMalloc((void**)&r->d_bt, table);
     if (h == hipSuccess) h = hipMalloc((void**)&r->d_fbw, fbw);
     if (h == hipSuccess) h = hipMalloc((void**)&r->d_first, firsts);
-    if (h == hipSuccess) h = hipMemcpy(r->d_bt, pl.bt.data(), table, hipMemcpyHostToDevice);
+    if (h == hipSuccess && !fft) h = hipMemcpy(r->d_bt, pl.bt.data(), table, hipMemcpyHostToDevice);
+    if (fft) {
+        const alacmelfft::Plan& fp = r->fft;
+        if (h == hipSuccess) h = hipMalloc((void**)&r->d_w32, fp.w32.size() * sizeof(float));
+        if (h == hipSuccess) h = hipMalloc((void**)&r->d_tw, fp.tw.size() * sizeof(float));
+        if (h == hipSuccess) h = hipMalloc((void**)&r->d_pos, fp.pos.size() * sizeof(uint32_t));
+        if (h == hipSuccess) h = hipMemcpy(r->d_w32, fp.w32.data(), fp.w32.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (h == hipSuccess) h = hipMemcpy(r->d_tw, fp.tw.data(), fp.tw.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (h == hipSuccess) h = hipMemcpy(r->d_pos, fp.pos.data(), fp.pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    }
     if (h == hipSuccess && !pl.fbw.empty()) h = hipMemcpy(r->d_fbw, pl.fbw.data(), pl.fbw.size() * sizeof(float), hipMemcpyHostToDevice);
     if (h == hipSuccess && !pl.first.empty())
         h = hipMemcpy(r->d_first, pl.first.data(), pl.first.size() * sizeof(int32_t), hipMemcpyHostToDevice);
@@ -208,6 +248,34 @@ int alacgpu_mel_plan(const alacgpu_mel* r, alacgpu_mel_info* info, float* basis_
     return ALACGPU_E_OK;
 }
 
+int alacgpu_mel_fft_plan(const alacgpu_mel* r, alacgpu_mel_fft_info* info, float* window_out, size_t window_cap, float* twiddle_out,
+                         size_t twiddle_cap) {
+    if (!r || !info) {
+        set_err("null argument");
+        return ALACGPU_E_ARG;
+    }
+    const alacmelfft::Plan& fp = r->fft;
+    if ((window_out && window_cap < fp.w32.size()) || (twiddle_out && twiddle_cap < fp.tw.size())) {
+        set_err("capacity below the plan's %zu window entries / %zu twiddle entries", fp.w32.size(), fp.tw.size());
+        return ALACGPU_E_ARG;
+    }
+    memset(info, 0, sizeof(*info));
+    info->transform = r->transform;
+    info->tile_frames = r->plan.tile_frames;
+    info->lds_bytes = r->plan.lds_floats * 4u;
+    if (r->transform == ALACGPU_MEL_TRANSFORM_FFT) {
+        info->batch_frames = fp.batch;
+        info->pitch = fp.pitch;
+        info->n_passes = fp.n_pass;
+        for (uint32_t s = 0; s < fp.n_pass; s++) info->radix[s] = fp.radix[s];
+        info->window_entries = (uint32_t)fp.w32.size();
+        info->twiddle_entries = (uint32_t)fp.tw.size();
+        if (window_out) memcpy(window_out, fp.w32.data(), fp.w32.size() * sizeof(float));
+        if (twiddle_out) memcpy(twiddle_out, fp.tw.data(), fp.tw.size() * sizeof(float));
+    }
+    return ALACGPU_E_OK;
+}
+
 int alacgpu_mel_device(alacgpu_mel* r, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
                        size_t out_row_stride, size_t out_bin_stride, int sync) {
     if (!r) {
@@ -221,9 +289,13 @@ int alacgpu_mel_device(alacgpu_mel* r, const float* d_in, size_t in_row_stride, 
         }
         return ALACGPU_E_OK;
     }
+    const bool fft = r->transform == ALACGPU_MEL_TRANSFORM_FFT;
     Params p;
-    if (!make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, r->d_bt, r->d_fbw,
-                     r->d_first, &p)) {
+    alacmelfft::Params q;
+    if (fft ? !alacmelfft::make_params(r->fft, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, r->d_w32,
+                                       r->d_tw, r->d_pos, r->d_fbw, r->d_first, &q)
+            : !make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, r->d_bt, r->d_fbw,
+                           r->d_first, &p)) {
         set_err("spectrogram: a NULL or misaligned buffer, a stride (%zu in, %zu out rows, %zu out bins) below what it spans (%zu "
                 "samples, %u bins of %llu frames), or sizes that overflow", in_row_stride, out_row_stride, out_bin_stride, in_frames,
                 r->plan.bins, (unsigned long long)alacgpu_mel_out_frames(r, in_frames));
@@ -231,7 +303,8 @@ int alacgpu_mel_device(alacgpu_mel* r, const float* d_in, size_t in_row_stride, 
     }
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(hipEventRecord(r->ev0, r->stream));
-    HIP_TRY(alack::mel_launch(r->stream, p, r->plan.lds_floats * 4u));
+    if (fft) HIP_TRY(alack::melfft_launch(r->stream, q, r->plan.lds_floats * 4u));
+    else HIP_TRY(alack::mel_launch(r->stream, p, r->plan.lds_floats * 4u));
     HIP_TRY(hipEventRecord(r->ev1, r->stream));
     r->timed = true;
     if (sync) HIP_TRY(hipStreamSynchronize(r->stream));

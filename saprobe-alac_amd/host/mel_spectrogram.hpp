@@ -6,6 +6,8 @@
 //   MelSpectrogram::OutFrames(T)          1 + (T - n_fft % 2) / hop centred, 1 + (T - n_fft) / hop otherwise; 0 where no frame exists
 //   MelSpectrogram::MelDevice(...)        float32 rows on the device -> [rows][bins][frames], asynchronous on Stream() unless sync
 //   MelSpectrogram::Plan()                the numbers and the host copies of the tables the kernel uses
+//   MelConfig(...).transform              ALACGPU_MEL_TRANSFORM_DIRECT (the default) or _FFT: n_fft even, n_fft / 2 = 2^a 3^b 5^c
+//   MelSpectrogram::FftPlan()             the FFT's numbers, window and twiddle table (transform 0 and no tables on a direct handle)
 // Header-only; link with -lalacgpu. Every pass runs the HIP kernel: there is no CPU path.
 #pragma once
 
@@ -35,15 +37,22 @@ inline alacgpu_mel_config MelConfig(uint32_t sample_rate, uint32_t n_fft = 400, 
     c.norm = n_mels && slaney_norm ? 1u : 0u;
     c.mel_scale = n_mels ? (uint32_t)mel_scale : (uint32_t)ALACGPU_MEL_SCALE_NONE;
     c.log = (uint32_t)log;
+    c.transform = ALACGPU_MEL_TRANSFORM_DIRECT;
     c.floor = floor;
     return c;
 }
 
 struct MelPlan {
     alacgpu_mel_info info{};
-    std::vector<float> basis;   // [2][n_freqs][n_fft]: C, then S
+    std::vector<float> basis;   // [2][n_freqs][n_fft]: C, then S; empty on a handle with transform = fft
     std::vector<float> fb;      // [n_mels][taps]
     std::vector<int32_t> first; // [n_mels]: the bin of each filter window's first weight
+};
+
+struct MelFftPlan {
+    alacgpu_mel_fft_info info{};
+    std::vector<float> window;  // [n_fft]
+    std::vector<float> twiddle; // roots, the passes' twiddles, the split step's (include/alacgpu.h)
 };
 
 class MelSpectrogram {
@@ -72,11 +81,25 @@ public:
         MelPlan p;
         if (alacgpu_mel_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0, nullptr, 0) != ALACGPU_E_OK)
             throw std::runtime_error(alacgpu_last_error());
-        p.basis.resize((size_t)2 * p.info.n_freqs * p.info.n_fft);
+        alacgpu_mel_fft_info fft{};
+        if (alacgpu_mel_fft_plan(h_.get(), &fft, nullptr, 0, nullptr, 0) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        // a handle with transform = fft builds no basis: 0 entries
+        p.basis.resize(fft.transform == ALACGPU_MEL_TRANSFORM_DIRECT ? (size_t)2 * p.info.n_freqs * p.info.n_fft : 0);
         p.fb.resize((size_t)p.info.n_mels * p.info.taps);
         p.first.resize(p.info.n_mels);
         if (alacgpu_mel_plan(h_.get(), &p.info, p.basis.data(), p.basis.size(), p.fb.data(), p.fb.size(), p.first.data(),
                              p.first.size()) != ALACGPU_E_OK)
+            throw std::runtime_error(alacgpu_last_error());
+        return p;
+    }
+
+    MelFftPlan FftPlan() const {
+        MelFftPlan p;
+        if (alacgpu_mel_fft_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        p.window.resize(p.info.window_entries);
+        p.twiddle.resize(p.info.twiddle_entries);
+        if (alacgpu_mel_fft_plan(h_.get(), &p.info, p.window.data(), p.window.size(), p.twiddle.data(), p.twiddle.size()) !=
+            ALACGPU_E_OK)
             throw std::runtime_error(alacgpu_last_error());
         return p;
     }
