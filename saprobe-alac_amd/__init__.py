@@ -866,34 +866,26 @@ def NewPacketEncoder(config, device=0):
     return PacketEncoder(config, device)
 
 
-# ---- Resampler (new: torchaudio.functional.resample's sinc_interp_hann on the device) ----------------------------------
-class ResampleInfo(ctypes.Structure):
-    """alacgpu_resample_info (include/alacgpu.h)."""
+# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures): what they share -----------------
+class _RowPass:
+    """The handle of a row pass: _h (NULL once closed), _lib and device, and the entries every such handle has. A subclass names
+    its C functions one by one (they are irregular: alacgpu_resampler_last_ms, but alacgpu_resample_out_frames), creates the
+    handle with _create, and keeps its own device entry, plan() and __call__. A closed handle answers out_frames() with 0 and
+    everything else with ValueError, on the host."""
 
-    _fields_ = [("o", ctypes.c_uint32), ("n", ctypes.c_uint32), ("width", ctypes.c_uint32), ("taps", ctypes.c_uint32),
-                ("tile_out", ctypes.c_uint32)]
+    _CREATE = _DESTROY = _OUT_FRAMES = _LAST_MS = _SYNCHRONIZE = None
 
-
-class Resampler:
-    """float32 rows at orig_freq -> the same rows at new_freq on one MI355X (include/alacgpu.h: alacgpu_resampler_*):
-    torchaudio's sinc_interp_hann, its table built once per handle. ValueError when no plan can be built (equal or zero
-    rates, a width of 0, rolloff outside (0, 1], a ratio too steep for the kernel's staging buffer). Single-caller, bound to
-    one device and one stream."""
-
-    def __init__(self, orig_freq, new_freq, device=0, lowpass_filter_width=6, rolloff=0.99):
+    def __init__(self):
         self._h = ctypes.c_void_p()
         self._lib = lib()
-        for v in (orig_freq, new_freq, lowpass_filter_width):
-            if int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
-                raise ValueError("the rates and the filter width are integers below 2^32")
-        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
-        _check(self._lib.alacgpu_resampler_create(device, self.orig_freq, self.new_freq, int(lowpass_filter_width), float(rolloff),
-                                                  ctypes.byref(self._h)))
+
+    def _create(self, device, *args):
+        _check(getattr(self._lib, self._CREATE)(device, *args, ctypes.byref(self._h)))
         self.device = device
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self._lib.alacgpu_resampler_destroy(self._h)
+            getattr(self._lib, self._DESTROY)(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -909,8 +901,100 @@ class Resampler:
         self.close()
 
     def out_frames(self, in_frames):
-        """alacgpu_resample_out_frames: ceil(new_freq * in_frames / orig_freq)."""
-        return int(self._lib.alacgpu_resample_out_frames(self._h, int(in_frames)))
+        """The C entry's count of the frames (columns) a row of in_frames gives, by the formula in the class's docstring; 0
+        where there is none."""
+        return int(getattr(self._lib, self._OUT_FRAMES)(self._h, int(in_frames)))
+
+    def last_ms(self):
+        """HIP events around the kernels of the last pass; ValueError before the first pass that launched one."""
+        ms = ctypes.c_float()
+        _check(getattr(self._lib, self._LAST_MS)(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def synchronize(self):
+        _check(getattr(self._lib, self._SYNCHRONIZE)(self._h))
+
+    def _over_rows(self, waveform, shape, device_call):
+        """The body of a __call__: waveform [..., T] made contiguous on the handle's device and flattened to rows, the output
+        [rows] + shape allocated, torch synchronised and device_call(in pointer, rows, out pointer) run where there is an
+        element to write -> the output as [...] + shape."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        T = int(waveform.shape[-1])
+        rows = 1
+        for d in waveform.shape[:-1]:
+            rows *= int(d)
+        x = waveform.to(dev).contiguous().reshape(rows, T)
+        out = torch.empty((rows,) + shape, dtype=torch.float32, device=dev)
+        if out.numel():
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            device_call(x.data_ptr(), rows, out.data_ptr())
+        return out.reshape(tuple(waveform.shape[:-1]) + shape)
+
+
+def _fetch_plan(fn, handle, info, *tables_of):
+    """The two calls of a plan export: the numbers into info, then the tables. Each of tables_of makes one zeroed numpy array
+    from the filled info -> those arrays, filled."""
+    _check(fn(handle, ctypes.byref(info), *(None, 0) * len(tables_of)))
+    tables = [make(info) for make in tables_of]
+    _check(fn(handle, ctypes.byref(info), *(a for t in tables for a in (t.ctypes.data, t.size))))
+    return tables
+
+
+def _float32_input(waveform):
+    """ValueError unless waveform is a float32 torch tensor or numpy array [..., T]"""
+    import torch
+    if isinstance(waveform, np.ndarray):
+        if waveform.dtype != np.float32:
+            raise ValueError("waveform must be float32")
+    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
+        raise ValueError("waveform must be a float32 torch tensor or numpy array")
+    if waveform.ndim < 1:
+        raise ValueError("waveform must be [..., T]")
+
+
+def _on_device(waveform, device):
+    """A checked input -> (a tensor, the device index): a numpy array wrapped, device None resolved to the tensor's own, cuda:0
+    for what is on the host (the handle's __call__ uploads)"""
+    import torch
+    if isinstance(waveform, np.ndarray):
+        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
+    if device is None:
+        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    return waveform, device
+
+
+def _cached(cache, key, make):
+    """cache[key], made by make() at its first use: one handle per (device, parameter set) and process"""
+    if key not in cache:
+        cache[key] = make()
+    return cache[key]
+
+
+# ---- Resampler (new: torchaudio.functional.resample's sinc_interp_hann on the device) ----------------------------------
+class ResampleInfo(ctypes.Structure):
+    """alacgpu_resample_info (include/alacgpu.h)."""
+
+    _fields_ = [("o", ctypes.c_uint32), ("n", ctypes.c_uint32), ("width", ctypes.c_uint32), ("taps", ctypes.c_uint32),
+                ("tile_out", ctypes.c_uint32)]
+
+
+class Resampler(_RowPass):
+    """float32 rows at orig_freq -> the same rows at new_freq on one MI355X (include/alacgpu.h: alacgpu_resampler_*):
+    torchaudio's sinc_interp_hann, its table built once per handle. ValueError when no plan can be built (equal or zero
+    rates, a width of 0, rolloff outside (0, 1], a ratio too steep for the kernel's staging buffer). Single-caller, bound to
+    one device and one stream. out_frames(T) is alacgpu_resample_out_frames: ceil(new_freq * T / orig_freq)."""
+
+    _CREATE, _DESTROY, _OUT_FRAMES = "alacgpu_resampler_create", "alacgpu_resampler_destroy", "alacgpu_resample_out_frames"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_resampler_last_ms", "alacgpu_resampler_synchronize"
+
+    def __init__(self, orig_freq, new_freq, device=0, lowpass_filter_width=6, rolloff=0.99):
+        super().__init__()
+        for v in (orig_freq, new_freq, lowpass_filter_width):
+            if int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError("the rates and the filter width are integers below 2^32")
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self._create(device, self.orig_freq, self.new_freq, int(lowpass_filter_width), float(rolloff))
 
     def resample_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, sync=True):
         """alacgpu_resample_device: raw device pointers (ints), strides in elements. rows rows of in_frames float32 frames ->
@@ -923,40 +1007,20 @@ class Resampler:
         """alacgpu_resampler_plan -> dict: o, n, width, taps, tile_out, and the host copies of the table the kernel uses, h
         [n, taps] float32 and first [n] int32 (the tap index of each phase's first kept tap)."""
         info = ResampleInfo()
-        _check(self._lib.alacgpu_resampler_plan(self._h, ctypes.byref(info), None, 0, None, 0))
-        h = np.zeros((info.n, info.taps), np.float32)
-        first = np.zeros(info.n, np.int32)
-        _check(self._lib.alacgpu_resampler_plan(self._h, ctypes.byref(info), h.ctypes.data, h.size, first.ctypes.data, first.size))
+        h, first = _fetch_plan(self._lib.alacgpu_resampler_plan, self._h, info, lambda i: np.zeros((i.n, i.taps), np.float32),
+                               lambda i: np.zeros(i.n, np.int32))
         out = {k: int(getattr(info, k)) for k, _ in ResampleInfo._fields_}
         out.update(h=h, first=first)
         return out
 
-    def last_ms(self):
-        """alacgpu_resampler_last_ms: HIP events around the kernels of the last pass."""
-        ms = ctypes.c_float()
-        _check(self._lib.alacgpu_resampler_last_ms(self._h, ctypes.byref(ms)))
-        return ms.value
-
-    def synchronize(self):
-        _check(self._lib.alacgpu_resampler_synchronize(self._h))
-
     def __call__(self, waveform):
         """A float32 CUDA tensor [..., T] on the handle's device -> [..., out_frames(T)] (made contiguous, flattened to rows)."""
-        import torch
-        dev = torch.device("cuda", self.device)
         T = int(waveform.shape[-1])
-        rows = 1
-        for d in waveform.shape[:-1]:
-            rows *= int(d)
-        x = waveform.to(dev).contiguous().reshape(rows, T)
         frames = self.out_frames(T)
         if T and not frames:
             raise ValueError("%d frames are more than one pass takes" % T)
-        out = torch.empty((rows, frames), dtype=torch.float32, device=dev)
-        if rows and frames:
-            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
-            self.resample_device(x.data_ptr(), T, rows, T, out.data_ptr(), frames, sync=True)
-        return out.reshape(tuple(waveform.shape[:-1]) + (frames,))
+        return self._over_rows(waveform, (frames,),
+                               lambda x, rows, out: self.resample_device(x, T, rows, T, out, frames, sync=True))
 
 
 def NewResampler(orig_freq, new_freq, device=0, lowpass_filter_width=6, rolloff=0.99):
@@ -972,26 +1036,14 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
     float32 tensor [..., T] -> [..., ceil(new_freq * T / orig_freq)] on cuda:`device` (default: the tensor's own device, cuda:0
     for a CPU tensor or a numpy array, which are uploaded). Equal rates return the input as it is; another dtype raises
     ValueError. The filter table of a (device, rates, width, rolloff) is built once and kept."""
-    import torch
-    if isinstance(waveform, np.ndarray):
-        if waveform.dtype != np.float32:
-            raise ValueError("waveform must be float32")
-    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
-        raise ValueError("waveform must be a float32 torch tensor or numpy array")
-    if waveform.ndim < 1:
-        raise ValueError("waveform must be [..., T]")
+    _float32_input(waveform)
     if int(orig_freq) != orig_freq or int(new_freq) != new_freq or orig_freq <= 0 or new_freq <= 0:
         raise ValueError("orig_freq and new_freq must be positive integers")
     if int(orig_freq) == int(new_freq):
         return waveform
-    if isinstance(waveform, np.ndarray):
-        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
-    if device is None:
-        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    waveform, device = _on_device(waveform, device)
     key = (device, int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff))
-    if key not in _RESAMPLERS:
-        _RESAMPLERS[key] = Resampler(orig_freq, new_freq, device, lowpass_filter_width, rolloff)
-    return _RESAMPLERS[key](waveform)
+    return _cached(_RESAMPLERS, key, lambda: Resampler(orig_freq, new_freq, device, lowpass_filter_width, rolloff))(waveform)
 
 
 # ---- MelSpectrogram (new: torch.stft + |.|^2 + torchaudio's melscale_fbanks + log, one fused pass on the device) --------
@@ -1054,46 +1106,27 @@ def _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels
     return c
 
 
-class MelSpectrogram:
+class MelSpectrogram(_RowPass):
     """float32 rows -> their power spectrograms (n_mels None) or (log-)mel spectrograms on one MI355X (include/alacgpu.h:
     alacgpu_mel_*): periodic Hann window, reflect padding when centred, |X|^2, torchaudio's melscale_fbanks, s log(max(v,
     floor)); the tables are built once per handle. ValueError when no plan can be built. Single-caller, bound to one device
     and one stream. transform="fft" (keyword only; the default "direct" is the fmaf chains over the basis) computes the powers by
     a mixed-radix FFT: n_fft must be even with n_fft / 2 = 2^a 3^b 5^c, any other is a ValueError, never a fall-back; the result
-    is fixed bit for bit as well, but it is not the direct transform's."""
+    is fixed bit for bit as well, but it is not the direct transform's. out_frames(T) is alacgpu_mel_out_frames: 1 + (T - n_fft %
+    2) / hop centred (T > n_fft / 2; torch.stft's count: it pads n_fft / 2 on each side), 1 + (T - n_fft) / hop otherwise; 0 where
+    no frame exists."""
+
+    _CREATE, _DESTROY, _OUT_FRAMES = "alacgpu_mel_create", "alacgpu_mel_destroy", "alacgpu_mel_out_frames"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_mel_last_ms", "alacgpu_mel_synchronize"
 
     def __init__(self, sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128, center=True,
                  norm=None, mel_scale="htk", log=None, floor=1e-10, device=0, *, transform="direct"):
-        self._h = ctypes.c_void_p()
-        self._lib = lib()
+        super().__init__()
         self.config = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor,
                                   transform)
         self.transform = transform
-        _check(self._lib.alacgpu_mel_create(device, ctypes.byref(self.config), ctypes.byref(self._h)))
-        self.device = device
+        self._create(device, ctypes.byref(self.config))
         self.bins = int(n_mels) if n_mels is not None else int(n_fft) // 2 + 1
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.alacgpu_mel_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def out_frames(self, in_frames):
-        """alacgpu_mel_out_frames: 1 + (T - n_fft % 2) / hop centred (T > n_fft / 2; torch.stft's count: it pads n_fft / 2 on each
-        side), 1 + (T - n_fft) / hop otherwise; 0 where no frame exists."""
-        return int(self._lib.alacgpu_mel_out_frames(self._h, int(in_frames)))
 
     def mel_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride, sync=True):
         """alacgpu_mel_device: raw device pointers (ints), strides in elements. rows rows of in_frames float32 samples ->
@@ -1108,12 +1141,10 @@ class MelSpectrogram:
         host copies of the tables the kernel uses: basis [2, n_freqs, n_fft] float32 (C, then S), fb [n_mels, taps] float32 (each
         filter's window) and first [n_mels] int32 (the bin of each window's first weight)."""
         info = MelInfo()
-        _check(self._lib.alacgpu_mel_plan(self._h, ctypes.byref(info), None, 0, None, 0, None, 0))
-        basis = np.zeros((2, info.n_freqs, info.n_fft) if self.config.transform == 0 else (2, 0, info.n_fft), np.float32)
-        fb = np.zeros((info.n_mels, info.taps), np.float32)
-        first = np.zeros(info.n_mels, np.int32)
-        _check(self._lib.alacgpu_mel_plan(self._h, ctypes.byref(info), basis.ctypes.data, basis.size, fb.ctypes.data, fb.size,
-                                          first.ctypes.data, first.size))
+        basis, fb, first = _fetch_plan(
+            self._lib.alacgpu_mel_plan, self._h, info,
+            lambda i: np.zeros((2, i.n_freqs if self.config.transform == 0 else 0, i.n_fft), np.float32),
+            lambda i: np.zeros((i.n_mels, i.taps), np.float32), lambda i: np.zeros(i.n_mels, np.int32))
         out = {k: int(getattr(info, k)) for k, _ in MelInfo._fields_}
         out.update(basis=basis, fb=fb, first=first)
         return out
@@ -1123,42 +1154,21 @@ class MelSpectrogram:
         (the passes' radices in order), and the tables window [n_fft] float32 and twiddle float32 (8 roots, each pass's twiddles,
         the split step's n_fft / 2 + 1 pairs). On a direct handle: transform 0, no passes, empty tables."""
         info = MelFftInfo()
-        _check(self._lib.alacgpu_mel_fft_plan(self._h, ctypes.byref(info), None, 0, None, 0))
-        window = np.zeros(info.window_entries, np.float32)
-        twiddle = np.zeros(info.twiddle_entries, np.float32)
-        _check(self._lib.alacgpu_mel_fft_plan(self._h, ctypes.byref(info), window.ctypes.data, window.size, twiddle.ctypes.data,
-                                              twiddle.size))
+        window, twiddle = _fetch_plan(self._lib.alacgpu_mel_fft_plan, self._h, info, lambda i: np.zeros(i.window_entries, np.float32),
+                                      lambda i: np.zeros(i.twiddle_entries, np.float32))
         out = {k: int(getattr(info, k)) for k in ("transform", "tile_frames", "lds_bytes", "batch_frames", "pitch", "n_passes")}
         out.update(radix=[int(r) for r in info.radix[:info.n_passes]], window=window, twiddle=twiddle)
         return out
 
-    def last_ms(self):
-        """alacgpu_mel_last_ms: HIP events around the kernels of the last pass."""
-        ms = ctypes.c_float()
-        _check(self._lib.alacgpu_mel_last_ms(self._h, ctypes.byref(ms)))
-        return ms.value
-
-    def synchronize(self):
-        _check(self._lib.alacgpu_mel_synchronize(self._h))
-
     def __call__(self, waveform):
         """A float32 tensor [..., T] -> [..., bins, out_frames(T)] on the handle's device (made contiguous, flattened to rows):
         1 + (T - n_fft % 2) / hop frames centred, as torch.stft has them. ValueError where T has no frame."""
-        import torch
-        dev = torch.device("cuda", self.device)
         T = int(waveform.shape[-1])
         frames = self.out_frames(T)
         if not frames:
             raise ValueError("%d samples have no frame of n_fft %d" % (T, self.config.n_fft))
-        rows = 1
-        for d in waveform.shape[:-1]:
-            rows *= int(d)
-        x = waveform.to(dev).contiguous().reshape(rows, T)
-        out = torch.empty((rows, self.bins, frames), dtype=torch.float32, device=dev)
-        if rows:
-            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
-            self.mel_device(x.data_ptr(), T, rows, T, out.data_ptr(), self.bins * frames, frames, sync=True)
-        return out.reshape(tuple(waveform.shape[:-1]) + (self.bins, frames))
+        return self._over_rows(waveform, (self.bins, frames),
+                               lambda x, rows, out: self.mel_device(x, T, rows, T, out, self.bins * frames, frames, sync=True))
 
 
 def NewMelSpectrogram(sample_rate, n_fft=400, win_length=None, hop_length=None, f_min=0.0, f_max=None, n_mels=128, center=True,
@@ -1180,24 +1190,12 @@ def mel_spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_lengt
     tensor or a numpy array). n_mels None gives the power spectrogram [..., n_fft / 2 + 1, F]. Another dtype, parameters without
     a plan or a T without a frame raise ValueError. The tables of a (device, parameter set) are built once and kept.
     transform="fft" takes the FFT in place of the direct transform (MelSpectrogram); the two have handles of their own."""
-    import torch
-    if isinstance(waveform, np.ndarray):
-        if waveform.dtype != np.float32:
-            raise ValueError("waveform must be float32")
-    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
-        raise ValueError("waveform must be a float32 torch tensor or numpy array")
-    if waveform.ndim < 1:
-        raise ValueError("waveform must be [..., T]")
+    _float32_input(waveform)
     c = _mel_config(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log, floor, transform)
-    if isinstance(waveform, np.ndarray):
-        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
-    if device is None:
-        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    waveform, device = _on_device(waveform, device)
     key = (device,) + tuple(getattr(c, k) for k, _ in MelConfig._fields_)
-    if key not in _MELS:
-        _MELS[key] = MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm, mel_scale, log,
-                                    floor, device, transform=transform)
-    return _MELS[key](waveform)
+    return _cached(_MELS, key, lambda: MelSpectrogram(sample_rate, n_fft, win_length, hop_length, f_min, f_max, n_mels, center, norm,
+                                                      mel_scale, log, floor, device, transform=transform))(waveform)
 
 
 def spectrogram(waveform, sample_rate, n_fft=400, win_length=None, hop_length=None, center=True, log=None, floor=1e-10, device=None,
@@ -1273,50 +1271,31 @@ def _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps
     return c
 
 
-class KaldiFeatures:
+class KaldiFeatures(_RowPass):
     """float32 rows -> Kaldi's fbank (num_ceps 0) or MFCC features on one MI355X (include/alacgpu.h: alacgpu_fbank_*). Lengths
     are in samples here; kaldi_fbank / kaldi_mfcc take torchaudio's milliseconds. layout "frames" gives [..., F, cols], "bins"
     [..., cols, F]. log_energy=False keeps the energy column unlogged (for checks). MFCC with htk_compat and without use_energy
     ends in sqrt(2) C0 (plan()["dct"][0] is sqrt(2 / num_mel_bins) there). ValueError when no plan can be built:
     dither != 0, vtln_warp != 1, use_power False and use_energy without raw_energy among them, before any HIP call.
-    Single-caller, bound to one device and one stream."""
+    Single-caller, bound to one device and one stream. out_frames(T) is alacgpu_fbank_out_frames: 1 + (T - W) / h with snip_edges,
+    (T + h / 2) / h without; 0 for T < W."""
+
+    _CREATE, _DESTROY, _OUT_FRAMES = "alacgpu_fbank_create", "alacgpu_fbank_destroy", "alacgpu_fbank_out_frames"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_fbank_last_ms", "alacgpu_fbank_synchronize"
 
     def __init__(self, sample_rate, frame_length, frame_shift, num_mel_bins=23, num_ceps=0, round_to_power_of_two=True,
                  snip_edges=True, remove_dc_offset=True, window_type="povey", use_log_fbank=True, use_energy=False, raw_energy=True,
                  htk_compat=False, use_power=True, log_energy=True, layout="frames", preemphasis_coefficient=0.97,
                  blackman_coeff=0.42, low_freq=20.0, high_freq=0.0, energy_floor=1.0, scale=1.0, cepstral_lifter=22.0, dither=0.0,
                  vtln_warp=1.0, device=0):
-        self._h = ctypes.c_void_p()
-        self._lib = lib()
+        super().__init__()
         self.config = _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps, round_to_power_of_two, snip_edges,
                                     remove_dc_offset, window_type, use_log_fbank, use_energy, raw_energy, htk_compat, use_power,
                                     log_energy, layout, preemphasis_coefficient, blackman_coeff, low_freq, high_freq, energy_floor,
                                     scale, cepstral_lifter, dither, vtln_warp)
-        _check(self._lib.alacgpu_fbank_create(device, ctypes.byref(self.config), ctypes.byref(self._h)))
-        self.device = device
+        self._create(device, ctypes.byref(self.config))
         self.layout = layout
         self.cols = int(num_ceps) if int(num_ceps) else int(num_mel_bins) + int(bool(use_energy))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.alacgpu_fbank_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def out_frames(self, in_frames):
-        """alacgpu_fbank_out_frames: 1 + (T - W) / h with snip_edges, (T + h / 2) / h without; 0 for T < W."""
-        return int(self._lib.alacgpu_fbank_out_frames(self._h, int(in_frames)))
 
     def features_device(self, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, sync=True):
         """alacgpu_fbank_device: raw device pointers (ints), strides in elements. rows rows of in_frames float32 samples ->
@@ -1331,46 +1310,24 @@ class KaldiFeatures:
         [2, n_freqs, frame_length] float32 (C, then S, folded), fb [num_mel_bins, taps], first [num_mel_bins] int32, dct
         [num_ceps, num_mel_bins] and lifter [num_ceps]."""
         info = FbankInfo()
-        _check(self._lib.alacgpu_fbank_plan(self._h, ctypes.byref(info), None, 0, None, 0, None, 0, None, 0, None, 0))
-        basis = np.zeros((2, info.n_freqs, info.frame_length), np.float32)
-        fb = np.zeros((info.num_mel_bins, info.taps), np.float32)
-        first = np.zeros(info.num_mel_bins, np.int32)
-        dct = np.zeros((info.num_ceps, info.num_mel_bins), np.float32)
-        lifter = np.zeros(info.num_ceps, np.float32)
-        _check(self._lib.alacgpu_fbank_plan(self._h, ctypes.byref(info), basis.ctypes.data, basis.size, fb.ctypes.data, fb.size,
-                                            first.ctypes.data, first.size, dct.ctypes.data, dct.size, lifter.ctypes.data, lifter.size))
+        basis, fb, first, dct, lifter = _fetch_plan(
+            self._lib.alacgpu_fbank_plan, self._h, info, lambda i: np.zeros((2, i.n_freqs, i.frame_length), np.float32),
+            lambda i: np.zeros((i.num_mel_bins, i.taps), np.float32), lambda i: np.zeros(i.num_mel_bins, np.int32),
+            lambda i: np.zeros((i.num_ceps, i.num_mel_bins), np.float32), lambda i: np.zeros(i.num_ceps, np.float32))
         out = {k: int(getattr(info, k)) for k, _ in FbankInfo._fields_}
         out.update(basis=basis, fb=fb, first=first, dct=dct, lifter=lifter)
         return out
 
-    def last_ms(self):
-        """alacgpu_fbank_last_ms: HIP events around the kernels of the last pass."""
-        ms = ctypes.c_float()
-        _check(self._lib.alacgpu_fbank_last_ms(self._h, ctypes.byref(ms)))
-        return ms.value
-
-    def synchronize(self):
-        _check(self._lib.alacgpu_fbank_synchronize(self._h))
-
     def __call__(self, waveform):
         """A float32 tensor [..., T] -> [..., F, cols] (layout frames) or [..., cols, F] (bins) on the handle's device (made
         contiguous, flattened to rows). ValueError where T has no frame (T < frame_length)."""
-        import torch
-        dev = torch.device("cuda", self.device)
         T = int(waveform.shape[-1])
         frames = self.out_frames(T)
         if not frames:
             raise ValueError("%d samples have no frame of %d" % (T, self.config.frame_length))
-        rows = 1
-        for d in waveform.shape[:-1]:
-            rows *= int(d)
-        x = waveform.to(dev).contiguous().reshape(rows, T)
         shape = (frames, self.cols) if self.layout == "frames" else (self.cols, frames)
-        out = torch.empty((rows,) + shape, dtype=torch.float32, device=dev)
-        if rows:
-            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
-            self.features_device(x.data_ptr(), T, rows, T, out.data_ptr(), self.cols * frames, shape[1], sync=True)
-        return out.reshape(tuple(waveform.shape[:-1]) + shape)
+        return self._over_rows(waveform, shape,
+                               lambda x, rows, out: self.features_device(x, T, rows, T, out, self.cols * frames, shape[1], sync=True))
 
 
 def NewKaldiFeatures(*args, **kw):
@@ -1382,14 +1339,7 @@ _KALDIS = {}  # (device, every field of the configuration) -> KaldiFeatures: a p
 
 
 def _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, **kw):
-    import torch
-    if isinstance(waveform, np.ndarray):
-        if waveform.dtype != np.float32:
-            raise ValueError("waveform must be float32")
-    elif not isinstance(waveform, torch.Tensor) or waveform.dtype is not torch.float32:
-        raise ValueError("waveform must be a float32 torch tensor or numpy array")
-    if waveform.ndim < 1:
-        raise ValueError("waveform must be [..., T]")
+    _float32_input(waveform)
     # torchaudio's _get_waveform_and_window_properties: milliseconds -> samples
     W, h = int(sample_frequency * frame_length * 0.001), int(sample_frequency * frame_shift * 0.001)
     c = _fbank_config(sample_frequency, W, h, kw["num_mel_bins"], kw["num_ceps"], kw["round_to_power_of_two"], kw["snip_edges"],
@@ -1397,14 +1347,9 @@ def _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean,
                       kw["htk_compat"], kw["use_power"], True, kw["layout"], kw["preemphasis_coefficient"], kw["blackman_coeff"],
                       kw["low_freq"], kw["high_freq"], kw["energy_floor"], kw["scale"], kw["cepstral_lifter"], kw["dither"],
                       kw["vtln_warp"])
-    if isinstance(waveform, np.ndarray):
-        waveform = torch.from_numpy(np.ascontiguousarray(waveform))
-    if device is None:
-        device = (waveform.device.index or 0) if waveform.is_cuda else 0
+    waveform, device = _on_device(waveform, device)
     key = (device,) + tuple(getattr(c, k) for k, _ in FbankConfig._fields_)
-    if key not in _KALDIS:
-        _KALDIS[key] = KaldiFeatures(sample_frequency, W, h, device=device, **kw)
-    out = _KALDIS[key](waveform)
+    out = _cached(_KALDIS, key, lambda: KaldiFeatures(sample_frequency, W, h, device=device, **kw))(waveform)
     if subtract_mean:  # over the frames, as torchaudio's _subtract_column_mean: a torch op, as Whisper's post-processing is
         out = out - out.mean(dim=-2 if kw["layout"] == "frames" else -1, keepdim=True)
     return out

@@ -23,9 +23,6 @@ using alack::set_err;
 
 namespace {
 
-/* alac_fbank_rows goes in slices, each far below a dispatch's 2^32 work-items: 2^22 workgroups of 256 */
-constexpr uint64_t kTilesPerLaunch = (uint64_t)1 << 22;
-
 __global__ void __launch_bounds__(kThreads) alac_fbank_rows(Params p, uint64_t first_tile) {
     extern __shared__ __attribute__((aligned(16))) float lds[]; /* the plan's lds_floats */
     const uint64_t b = first_tile + blockIdx.x;
@@ -52,23 +49,14 @@ namespace alack {
 
 hipError_t fbank_launch(hipStream_t stream, const Params& p, uint32_t lds_bytes) {
     if (p.m.rows == 0 || p.m.out_frames == 0) return hipSuccess;
-    const uint64_t tiles = p.m.rows * p.m.tiles_per_row;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
-        const uint64_t m = tiles - t0 < kTilesPerLaunch ? tiles - t0 : kTilesPerLaunch;
-        hipLaunchKernelGGL(alac_fbank_rows, dim3((unsigned)m), dim3(kThreads), lds_bytes, stream, p, t0);
-    }
-    return hipGetLastError();
+    return launch_tiles(alac_fbank_rows, p.m.rows * p.m.tiles_per_row, kThreads, lds_bytes, stream, p);
 }
 
 } /* namespace alack */
 
 /* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
-struct alacgpu_fbank {
-    int device = 0;
+struct __attribute__((visibility("hidden"))) alacgpu_fbank : alack::PassHandle { /* hidden: its destructor is no export */
     Plan plan;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; /* around the kernels of the last pass */
-    bool timed = false;
     float* d_bt = nullptr;
     float* d_fbw = nullptr;
     int32_t* d_first = nullptr;
@@ -77,20 +65,6 @@ struct alacgpu_fbank {
 };
 
 namespace {
-void release(alacgpu_fbank* r) {
-    (void)hipSetDevice(r->device);
-    if (r->stream) (void)hipStreamSynchronize(r->stream);
-    if (r->d_bt) (void)hipFree(r->d_bt);
-    if (r->d_fbw) (void)hipFree(r->d_fbw);
-    if (r->d_first) (void)hipFree(r->d_first);
-    if (r->d_dct) (void)hipFree(r->d_dct);
-    if (r->d_lifter) (void)hipFree(r->d_lifter);
-    if (r->ev0) (void)hipEventDestroy(r->ev0);
-    if (r->ev1) (void)hipEventDestroy(r->ev1);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;
-}
-
 Config config_of(const alacgpu_fbank_config* c) {
     Config k;
     k.sample_rate = c->sample_rate;
@@ -120,14 +94,6 @@ Config config_of(const alacgpu_fbank_config* c) {
     k.vtln_warp = c->vtln_warp;
     return k;
 }
-
-/* a table on the device; an empty one still gets a block, so that the kernel's arguments are never NULL */
-template <typename T>
-hipError_t upload(T** d, const std::vector<T>& v) {
-    hipError_t h = hipMalloc((void**)d, (v.empty() ? 1 : v.size()) * sizeof(T));
-    if (h == hipSuccess && !v.empty()) h = hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return h;
-}
 } /* namespace */
 
 extern "C" {
@@ -156,20 +122,15 @@ int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu
         delete r;
         return ALACGPU_E_ARG;
     }
-    r->device = device;
-    const Plan& pl = r->plan;
-    hipError_t h = hipSetDevice(device);
-    if (h == hipSuccess) h = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    if (h == hipSuccess) h = hipEventCreate(&r->ev0);
-    if (h == hipSuccess) h = hipEventCreate(&r->ev1);
-    if (h == hipSuccess) h = upload(&r->d_bt, pl.bt);
-    if (h == hipSuccess) h = upload(&r->d_fbw, pl.fbw);
-    if (h == hipSuccess) h = upload(&r->d_first, pl.first);
-    if (h == hipSuccess) h = upload(&r->d_dct, pl.dct);
-    if (h == hipSuccess) h = upload(&r->d_lifter, pl.lifter);
-    if (h != hipSuccess) {
-        set_err("Kaldi feature handle creation failed: %s", hipGetErrorString(h));
-        release(r);
+    r->open(device);
+    r->upload(&r->d_bt, r->plan.bt);
+    r->upload(&r->d_fbw, r->plan.fbw);
+    r->upload(&r->d_first, r->plan.first);
+    r->upload(&r->d_dct, r->plan.dct);
+    r->upload(&r->d_lifter, r->plan.lifter);
+    if (r->err != hipSuccess) {
+        set_err("Kaldi feature handle creation failed: %s", hipGetErrorString(r->err));
+        alacgpu_fbank_destroy(r);
         return ALACGPU_E_HIP;
     }
     *out = r;
@@ -177,28 +138,16 @@ int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu
 }
 
 void alacgpu_fbank_destroy(alacgpu_fbank* r) {
-    if (r) release(r);
+    if (!r) return;
+    r->close();
+    delete r;
 }
 
 void* alacgpu_fbank_stream(alacgpu_fbank* r) { return r ? (void*)r->stream : nullptr; }
 
-int alacgpu_fbank_synchronize(alacgpu_fbank* r) {
-    if (!r) return ALACGPU_E_ARG;
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return ALACGPU_E_OK;
-}
+int alacgpu_fbank_synchronize(alacgpu_fbank* r) { return r ? r->synchronize() : ALACGPU_E_ARG; }
 
-int alacgpu_fbank_last_ms(alacgpu_fbank* r, float* ms) {
-    if (!r || !ms || !r->timed) {
-        set_err(!r || !ms ? "null argument" : "no feature pass on this handle yet");
-        return ALACGPU_E_ARG;
-    }
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipEventSynchronize(r->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, r->ev0, r->ev1));
-    return ALACGPU_E_OK;
-}
+int alacgpu_fbank_last_ms(alacgpu_fbank* r, float* ms) { return r ? r->last_ms(ms, "feature") : alack::null_argument(); }
 
 uint64_t alacgpu_fbank_out_frames(const alacgpu_fbank* r, uint64_t in_frames) {
     if (!r || in_frames > ((uint64_t)1 << 61)) return 0;
@@ -208,10 +157,7 @@ uint64_t alacgpu_fbank_out_frames(const alacgpu_fbank* r, uint64_t in_frames) {
 int alacgpu_fbank_plan(const alacgpu_fbank* r, alacgpu_fbank_info* info, float* basis_out, size_t basis_cap, float* fb_out,
                        size_t fb_cap, int32_t* first_out, size_t first_cap, float* dct_out, size_t dct_cap, float* lifter_out,
                        size_t lifter_cap) {
-    if (!r || !info) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r || !info) return alack::null_argument();
     const Plan& pl = r->plan;
     if ((basis_out && basis_cap < pl.basis.size()) || (fb_out && fb_cap < pl.fbw.size()) || (first_out && first_cap < pl.first.size()) ||
         (dct_out && dct_cap < pl.dct.size()) || (lifter_out && lifter_cap < pl.lifter.size())) {
@@ -239,10 +185,7 @@ int alacgpu_fbank_plan(const alacgpu_fbank* r, alacgpu_fbank_info* info, float* 
 
 int alacgpu_fbank_device(alacgpu_fbank* r, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
                          size_t out_row_stride, size_t out_inner_stride, int sync) {
-    if (!r) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r) return alack::null_argument();
     if (rows == 0 || alacgpu_fbank_out_frames(r, in_frames) == 0) {
         if (rows && in_frames > ((uint64_t)1 << 61)) {
             set_err("Kaldi features: %zu samples are more than one pass takes", in_frames);
@@ -259,13 +202,7 @@ int alacgpu_fbank_device(alacgpu_fbank* r, const float* d_in, size_t in_row_stri
                 (unsigned long long)alacgpu_fbank_out_frames(r, in_frames), r->plan.cols);
         return ALACGPU_E_ARG;
     }
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipEventRecord(r->ev0, r->stream));
-    HIP_TRY(alack::fbank_launch(r->stream, p, r->plan.lds_floats * 4u));
-    HIP_TRY(hipEventRecord(r->ev1, r->stream));
-    r->timed = true;
-    if (sync) HIP_TRY(hipStreamSynchronize(r->stream));
-    return ALACGPU_E_OK;
+    return r->run(sync, [&](hipStream_t s) { return alack::fbank_launch(s, p, r->plan.lds_floats * 4u); });
 }
 
 } /* extern "C" */

@@ -25,9 +25,6 @@ using alack::set_err;
 
 namespace {
 
-/* alac_mel_rows goes in slices, each far below a dispatch's 2^32 work-items: 2^22 workgroups of 256 */
-constexpr uint64_t kTilesPerLaunch = (uint64_t)1 << 22;
-
 __global__ void __launch_bounds__(kThreads) alac_mel_rows(Params p, uint64_t first_tile) {
     extern __shared__ __attribute__((aligned(16))) float lds[]; /* the plan's lds_floats */
     const uint64_t b = first_tile + blockIdx.x;
@@ -53,23 +50,14 @@ namespace alack {
 
 hipError_t mel_launch(hipStream_t stream, const Params& p, uint32_t lds_bytes) {
     if (p.rows == 0 || p.out_frames == 0) return hipSuccess;
-    const uint64_t tiles = p.rows * p.tiles_per_row;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
-        const uint64_t m = tiles - t0 < kTilesPerLaunch ? tiles - t0 : kTilesPerLaunch;
-        hipLaunchKernelGGL(alac_mel_rows, dim3((unsigned)m), dim3(kThreads), lds_bytes, stream, p, t0);
-    }
-    return hipGetLastError();
+    return launch_tiles(alac_mel_rows, p.rows * p.tiles_per_row, kThreads, lds_bytes, stream, p);
 }
 
 } /* namespace alack */
 
 /* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
-struct alacgpu_mel {
-    int device = 0;
+struct __attribute__((visibility("hidden"))) alacgpu_mel : alack::PassHandle { /* hidden: its destructor is no export */
     Plan plan;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; /* around the kernels of the last pass */
-    bool timed = false;
     uint32_t transform = ALACGPU_MEL_TRANSFORM_DIRECT;
     alacmelfft::Plan fft; /* transform = fft: the plan in use; `plan` then is its base */
     float* d_w32 = nullptr;
@@ -81,21 +69,6 @@ struct alacgpu_mel {
 };
 
 namespace {
-void release(alacgpu_mel* r) {
-    (void)hipSetDevice(r->device);
-    if (r->stream) (void)hipStreamSynchronize(r->stream);
-    if (r->d_bt) (void)hipFree(r->d_bt);
-    if (r->d_w32) (void)hipFree(r->d_w32);
-    if (r->d_tw) (void)hipFree(r->d_tw);
-    if (r->d_pos) (void)hipFree(r->d_pos);
-    if (r->d_fbw) (void)hipFree(r->d_fbw);
-    if (r->d_first) (void)hipFree(r->d_first);
-    if (r->ev0) (void)hipEventDestroy(r->ev0);
-    if (r->ev1) (void)hipEventDestroy(r->ev1);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;
-}
-
 Config config_of(const alacgpu_mel_config* c) {
     Config k;
     k.sample_rate = c->sample_rate;
@@ -157,35 +130,18 @@ int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel
         delete r;
         return ALACGPU_E_ARG;
     }
-    r->device = device;
-    const Plan& pl = r->plan;
-    const bool fft = r->transform == ALACGPU_MEL_TRANSFORM_FFT;
-    const size_t table = (pl.bt.empty() ? 1 : pl.bt.size()) * sizeof(float);
-    const size_t fbw = (pl.fbw.empty() ? 1 : pl.fbw.size()) * sizeof(float);
-    const size_t firsts = (pl.first.empty() ? 1 : pl.first.size()) * sizeof(int32_t);
-    hipError_t h = hipSetDevice(device);
-    if (h == hipSuccess) h = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    if (h == hipSuccess) h = hipEventCreate(&r->ev0);
-    if (h == hipSuccess) h = hipEventCreate(&r->ev1);
-    if (h == hipSuccess) h = hipMalloc((void**)&r->d_bt, table);
-    if (h == hipSuccess) h = hipMalloc((void**)&r->d_fbw, fbw);
-    if (h == hipSuccess) h = hipMalloc((void**)&r->d_first, firsts);
-    if (h == hipSuccess && !fft) h = hipMemcpy(r->d_bt, pl.bt.data(), table, hipMemcpyHostToDevice);
-    if (fft) {
-        const alacmelfft::Plan& fp = r->fft;
-        if (h == hipSuccess) h = hipMalloc((void**)&r->d_w32, fp.w32.size() * sizeof(float));
-        if (h == hipSuccess) h = hipMalloc((void**)&r->d_tw, fp.tw.size() * sizeof(float));
-        if (h == hipSuccess) h = hipMalloc((void**)&r->d_pos, fp.pos.size() * sizeof(uint32_t));
-        if (h == hipSuccess) h = hipMemcpy(r->d_w32, fp.w32.data(), fp.w32.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (h == hipSuccess) h = hipMemcpy(r->d_tw, fp.tw.data(), fp.tw.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (h == hipSuccess) h = hipMemcpy(r->d_pos, fp.pos.data(), fp.pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    r->open(device);
+    r->upload(&r->d_bt, r->plan.bt); /* transform = fft: no basis, one element that nothing reads */
+    r->upload(&r->d_fbw, r->plan.fbw);
+    r->upload(&r->d_first, r->plan.first);
+    if (r->transform == ALACGPU_MEL_TRANSFORM_FFT) {
+        r->upload(&r->d_w32, r->fft.w32);
+        r->upload(&r->d_tw, r->fft.tw);
+        r->upload(&r->d_pos, r->fft.pos);
     }
-    if (h == hipSuccess && !pl.fbw.empty()) h = hipMemcpy(r->d_fbw, pl.fbw.data(), pl.fbw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (h == hipSuccess && !pl.first.empty())
-        h = hipMemcpy(r->d_first, pl.first.data(), pl.first.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (h != hipSuccess) {
-        set_err("spectrogram handle creation failed: %s", hipGetErrorString(h));
-        release(r);
+    if (r->err != hipSuccess) {
+        set_err("spectrogram handle creation failed: %s", hipGetErrorString(r->err));
+        alacgpu_mel_destroy(r);
         return ALACGPU_E_HIP;
     }
     *out = r;
@@ -193,28 +149,16 @@ int alacgpu_mel_create(int device, const alacgpu_mel_config* config, alacgpu_mel
 }
 
 void alacgpu_mel_destroy(alacgpu_mel* r) {
-    if (r) release(r);
+    if (!r) return;
+    r->close();
+    delete r;
 }
 
 void* alacgpu_mel_stream(alacgpu_mel* r) { return r ? (void*)r->stream : nullptr; }
 
-int alacgpu_mel_synchronize(alacgpu_mel* r) {
-    if (!r) return ALACGPU_E_ARG;
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return ALACGPU_E_OK;
-}
+int alacgpu_mel_synchronize(alacgpu_mel* r) { return r ? r->synchronize() : ALACGPU_E_ARG; }
 
-int alacgpu_mel_last_ms(alacgpu_mel* r, float* ms) {
-    if (!r || !ms || !r->timed) {
-        set_err(!r || !ms ? "null argument" : "no spectrogram pass on this handle yet");
-        return ALACGPU_E_ARG;
-    }
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipEventSynchronize(r->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, r->ev0, r->ev1));
-    return ALACGPU_E_OK;
-}
+int alacgpu_mel_last_ms(alacgpu_mel* r, float* ms) { return r ? r->last_ms(ms, "spectrogram") : alack::null_argument(); }
 
 uint64_t alacgpu_mel_out_frames(const alacgpu_mel* r, uint64_t in_frames) {
     if (!r || in_frames > ((uint64_t)1 << 61)) return 0;
@@ -223,10 +167,7 @@ uint64_t alacgpu_mel_out_frames(const alacgpu_mel* r, uint64_t in_frames) {
 
 int alacgpu_mel_plan(const alacgpu_mel* r, alacgpu_mel_info* info, float* basis_out, size_t basis_cap, float* fb_out,
                      size_t fb_cap, int32_t* first_out, size_t first_cap) {
-    if (!r || !info) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r || !info) return alack::null_argument();
     const Plan& pl = r->plan;
     if ((basis_out && basis_cap < pl.basis.size()) || (fb_out && fb_cap < pl.fbw.size()) || (first_out && first_cap < pl.first.size())) {
         set_err("capacity below the plan's %zu basis entries / %zu filterbank entries / %zu filters", pl.basis.size(), pl.fbw.size(),
@@ -250,10 +191,7 @@ int alacgpu_mel_plan(const alacgpu_mel* r, alacgpu_mel_info* info, float* basis_
 
 int alacgpu_mel_fft_plan(const alacgpu_mel* r, alacgpu_mel_fft_info* info, float* window_out, size_t window_cap, float* twiddle_out,
                          size_t twiddle_cap) {
-    if (!r || !info) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r || !info) return alack::null_argument();
     const alacmelfft::Plan& fp = r->fft;
     if ((window_out && window_cap < fp.w32.size()) || (twiddle_out && twiddle_cap < fp.tw.size())) {
         set_err("capacity below the plan's %zu window entries / %zu twiddle entries", fp.w32.size(), fp.tw.size());
@@ -278,10 +216,7 @@ int alacgpu_mel_fft_plan(const alacgpu_mel* r, alacgpu_mel_fft_info* info, float
 
 int alacgpu_mel_device(alacgpu_mel* r, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
                        size_t out_row_stride, size_t out_bin_stride, int sync) {
-    if (!r) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r) return alack::null_argument();
     if (rows == 0 || alacgpu_mel_out_frames(r, in_frames) == 0) {
         if (rows && in_frames > ((uint64_t)1 << 61)) {
             set_err("spectrogram: %zu frames are more than one pass takes", in_frames);
@@ -301,14 +236,8 @@ int alacgpu_mel_device(alacgpu_mel* r, const float* d_in, size_t in_row_stride, 
                 r->plan.bins, (unsigned long long)alacgpu_mel_out_frames(r, in_frames));
         return ALACGPU_E_ARG;
     }
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipEventRecord(r->ev0, r->stream));
-    if (fft) HIP_TRY(alack::melfft_launch(r->stream, q, r->plan.lds_floats * 4u));
-    else HIP_TRY(alack::mel_launch(r->stream, p, r->plan.lds_floats * 4u));
-    HIP_TRY(hipEventRecord(r->ev1, r->stream));
-    r->timed = true;
-    if (sync) HIP_TRY(hipStreamSynchronize(r->stream));
-    return ALACGPU_E_OK;
+    const uint32_t lds_bytes = r->plan.lds_floats * 4u;
+    return r->run(sync, [&](hipStream_t s) { return fft ? alack::melfft_launch(s, q, lds_bytes) : alack::mel_launch(s, p, lds_bytes); });
 }
 
 } /* extern "C" */

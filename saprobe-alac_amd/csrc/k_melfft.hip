@@ -11,14 +11,12 @@
  */
 #include <hip/hip_runtime.h>
 
+#include "alac_host.h"
 #include "alac_melfft.h"
 
 using namespace alacmelfft;
 
 namespace {
-
-/* as alac_mel_rows: slices far below a dispatch's 2^32 work-items */
-constexpr uint64_t kTilesPerLaunch = (uint64_t)1 << 22;
 
 __global__ void __launch_bounds__(kThreads) alac_melfft_rows(Params p, uint64_t first_tile) {
     extern __shared__ __attribute__((aligned(16))) float lds[]; /* the plan's lds_floats */
@@ -55,12 +53,7 @@ namespace alack {
 
 hipError_t melfft_launch(hipStream_t stream, const Params& p, uint32_t lds_bytes) {
     if (p.m.rows == 0 || p.m.out_frames == 0) return hipSuccess;
-    const uint64_t tiles = p.m.rows * p.m.tiles_per_row;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
-        const uint64_t m = tiles - t0 < kTilesPerLaunch ? tiles - t0 : kTilesPerLaunch;
-        hipLaunchKernelGGL(alac_melfft_rows, dim3((unsigned)m), dim3(kThreads), lds_bytes, stream, p, t0);
-    }
-    return hipGetLastError();
+    return launch_tiles(alac_melfft_rows, p.m.rows * p.m.tiles_per_row, kThreads, lds_bytes, stream, p);
 }
 
 } /* namespace alack */

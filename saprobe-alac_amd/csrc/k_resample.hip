@@ -22,9 +22,6 @@ using alack::set_err;
 
 namespace {
 
-/* alac_resample_rows goes in slices, each far below a dispatch's 2^32 work-items: 2^22 workgroups of 256 */
-constexpr uint64_t kTilesPerLaunch = (uint64_t)1 << 22;
-
 __global__ void __launch_bounds__(kThreads) alac_resample_rows(Params p, uint64_t first_tile) {
     __shared__ __attribute__((aligned(16))) float stage[kStageFloats];
     __shared__ __attribute__((aligned(16))) float outb[kOutFloats];
@@ -46,48 +43,23 @@ namespace alack {
 
 hipError_t resample_launch(hipStream_t stream, const Params& p) {
     if (p.rows == 0 || p.out_frames == 0) return hipSuccess;
-    const uint64_t tiles = p.rows * p.tiles_per_row;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += kTilesPerLaunch) {
-        const uint64_t m = tiles - t0 < kTilesPerLaunch ? tiles - t0 : kTilesPerLaunch;
-        hipLaunchKernelGGL(alac_resample_rows, dim3((unsigned)m), dim3(kThreads), 0, stream, p, t0);
-    }
-    return hipGetLastError();
+    return launch_tiles(alac_resample_rows, p.rows * p.tiles_per_row, kThreads, 0, stream, p);
 }
 
 } /* namespace alack */
 
 /* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
-struct alacgpu_resampler {
-    int device = 0;
+struct __attribute__((visibility("hidden"))) alacgpu_resampler : alack::PassHandle { /* hidden: its destructor is no export */
     Plan plan;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; /* around the kernels of the last pass */
-    bool timed = false;
     float* d_ht = nullptr;
     int32_t* d_first = nullptr;
 };
-
-namespace {
-void release(alacgpu_resampler* r) {
-    (void)hipSetDevice(r->device);
-    if (r->stream) (void)hipStreamSynchronize(r->stream);
-    if (r->d_ht) (void)hipFree(r->d_ht);
-    if (r->d_first) (void)hipFree(r->d_first);
-    if (r->ev0) (void)hipEventDestroy(r->ev0);
-    if (r->ev1) (void)hipEventDestroy(r->ev1);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;
-}
-} /* namespace */
 
 extern "C" {
 
 int alacgpu_resampler_create(int device, uint32_t orig_freq, uint32_t new_freq, uint32_t lowpass_filter_width, double rolloff,
                              alacgpu_resampler** out) {
-    if (!out) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!out) return alack::null_argument();
     *out = nullptr;
     alacgpu_resampler* r = new (std::nothrow) alacgpu_resampler();
     if (!r) {
@@ -101,19 +73,12 @@ int alacgpu_resampler_create(int device, uint32_t orig_freq, uint32_t new_freq, 
         delete r;
         return ALACGPU_E_ARG;
     }
-    r->device = device;
-    const size_t table = r->plan.ht.size() * sizeof(float), firsts = r->plan.first.size() * sizeof(int32_t);
-    hipError_t h = hipSetDevice(device);
-    if (h == hipSuccess) h = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    if (h == hipSuccess) h = hipEventCreate(&r->ev0);
-    if (h == hipSuccess) h = hipEventCreate(&r->ev1);
-    if (h == hipSuccess) h = hipMalloc((void**)&r->d_ht, table);
-    if (h == hipSuccess) h = hipMalloc((void**)&r->d_first, firsts);
-    if (h == hipSuccess) h = hipMemcpy(r->d_ht, r->plan.ht.data(), table, hipMemcpyHostToDevice);
-    if (h == hipSuccess) h = hipMemcpy(r->d_first, r->plan.first.data(), firsts, hipMemcpyHostToDevice);
-    if (h != hipSuccess) {
-        set_err("resampler creation failed: %s", hipGetErrorString(h));
-        release(r);
+    r->open(device);
+    r->upload(&r->d_ht, r->plan.ht);
+    r->upload(&r->d_first, r->plan.first);
+    if (r->err != hipSuccess) {
+        set_err("resampler creation failed: %s", hipGetErrorString(r->err));
+        alacgpu_resampler_destroy(r);
         return ALACGPU_E_HIP;
     }
     *out = r;
@@ -121,28 +86,16 @@ int alacgpu_resampler_create(int device, uint32_t orig_freq, uint32_t new_freq, 
 }
 
 void alacgpu_resampler_destroy(alacgpu_resampler* r) {
-    if (r) release(r);
+    if (!r) return;
+    r->close();
+    delete r;
 }
 
 void* alacgpu_resampler_stream(alacgpu_resampler* r) { return r ? (void*)r->stream : nullptr; }
 
-int alacgpu_resampler_synchronize(alacgpu_resampler* r) {
-    if (!r) return ALACGPU_E_ARG;
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return ALACGPU_E_OK;
-}
+int alacgpu_resampler_synchronize(alacgpu_resampler* r) { return r ? r->synchronize() : ALACGPU_E_ARG; }
 
-int alacgpu_resampler_last_ms(alacgpu_resampler* r, float* ms) {
-    if (!r || !ms || !r->timed) {
-        set_err(!r || !ms ? "null argument" : "no resampling pass on this handle yet");
-        return ALACGPU_E_ARG;
-    }
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipEventSynchronize(r->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, r->ev0, r->ev1));
-    return ALACGPU_E_OK;
-}
+int alacgpu_resampler_last_ms(alacgpu_resampler* r, float* ms) { return r ? r->last_ms(ms, "resampling") : alack::null_argument(); }
 
 uint64_t alacgpu_resample_out_frames(const alacgpu_resampler* r, uint64_t in_frames) {
     uint64_t of = 0;
@@ -152,10 +105,7 @@ uint64_t alacgpu_resample_out_frames(const alacgpu_resampler* r, uint64_t in_fra
 
 int alacgpu_resampler_plan(const alacgpu_resampler* r, alacgpu_resample_info* info, float* h_out, size_t h_cap,
                            int32_t* first_out, size_t first_cap) {
-    if (!r || !info) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r || !info) return alack::null_argument();
     const Plan& pl = r->plan;
     if ((h_out && h_cap < pl.h.size()) || (first_out && first_cap < pl.first.size())) {
         set_err("capacity below the plan's %zu table entries / %zu phases", pl.h.size(), pl.first.size());
@@ -173,10 +123,7 @@ int alacgpu_resampler_plan(const alacgpu_resampler* r, alacgpu_resample_info* in
 
 int alacgpu_resample_device(alacgpu_resampler* r, const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames,
                             float* d_out, size_t out_row_stride, int sync) {
-    if (!r) {
-        set_err("null argument");
-        return ALACGPU_E_ARG;
-    }
+    if (!r) return alack::null_argument();
     if (rows == 0 || in_frames == 0) return ALACGPU_E_OK;
     Params p;
     if (!make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, r->d_ht, r->d_first, &p)) {
@@ -185,13 +132,7 @@ int alacgpu_resample_device(alacgpu_resampler* r, const float* d_in, size_t in_r
                 (unsigned long long)alacgpu_resample_out_frames(r, in_frames));
         return ALACGPU_E_ARG;
     }
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipEventRecord(r->ev0, r->stream));
-    HIP_TRY(alack::resample_launch(r->stream, p));
-    HIP_TRY(hipEventRecord(r->ev1, r->stream));
-    r->timed = true;
-    if (sync) HIP_TRY(hipStreamSynchronize(r->stream));
-    return ALACGPU_E_OK;
+    return r->run(sync, [&](hipStream_t s) { return alack::resample_launch(s, p); });
 }
 
 } /* extern "C" */

@@ -13,10 +13,10 @@
 
 #include <cstdint>
 #include <memory>
-#include <stdexcept>
 #include <vector>
 
 #include "../../include/alacgpu.h"
+#include "pass_handle.hpp"
 
 namespace alac {
 
@@ -75,9 +75,7 @@ class KaldiFeatures {
 public:
     explicit KaldiFeatures(const alacgpu_fbank_config& config, int device = 0) {
         alacgpu_fbank* h = nullptr;
-        const int rc = alacgpu_fbank_create(device, &config, &h);
-        if (rc == ALACGPU_E_ARG) throw std::invalid_argument(alacgpu_last_error());
-        if (rc != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::check(alacgpu_fbank_create(device, &config, &h));
         h_.reset(h);
     }
 
@@ -88,45 +86,36 @@ public:
     // out_inner_stride + f (layout bins); exactly those are written
     void FeaturesDevice(const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out, size_t out_row_stride,
                         size_t out_inner_stride, bool sync = false) {
-        const int rc = alacgpu_fbank_device(h_.get(), d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride,
-                                            sync ? 1 : 0);
-        if (rc == ALACGPU_E_ARG) throw std::invalid_argument(alacgpu_last_error());
-        if (rc != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::check(alacgpu_fbank_device(h_.get(), d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride,
+                                           sync ? 1 : 0));
     }
 
     KaldiPlan Plan() const {
         KaldiPlan p;
-        if (alacgpu_fbank_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0) != ALACGPU_E_OK)
-            throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_fbank_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0));
         p.basis.resize((size_t)2 * p.info.n_freqs * p.info.frame_length);
         p.fb.resize((size_t)p.info.num_mel_bins * p.info.taps);
         p.first.resize(p.info.num_mel_bins);
         p.dct.resize((size_t)p.info.num_ceps * p.info.num_mel_bins);
         p.lifter.resize(p.info.num_ceps);
-        if (alacgpu_fbank_plan(h_.get(), &p.info, p.basis.data(), p.basis.size(), p.fb.data(), p.fb.size(), p.first.data(),
-                               p.first.size(), p.dct.data(), p.dct.size(), p.lifter.data(), p.lifter.size()) != ALACGPU_E_OK)
-            throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_fbank_plan(h_.get(), &p.info, p.basis.data(), p.basis.size(), p.fb.data(), p.fb.size(), p.first.data(),
+                                        p.first.size(), p.dct.data(), p.dct.size(), p.lifter.data(), p.lifter.size()));
         return p;
     }
 
     // milliseconds of the last pass: HIP events around its kernels
     float LastMs() {
         float ms = 0;
-        if (alacgpu_fbank_last_ms(h_.get(), &ms) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_fbank_last_ms(h_.get(), &ms));
         return ms;
     }
 
     void* Stream() const { return alacgpu_fbank_stream(h_.get()); }
-    void Synchronize() {
-        if (alacgpu_fbank_synchronize(h_.get()) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
-    }
+    void Synchronize() { detail::must(alacgpu_fbank_synchronize(h_.get())); }
     alacgpu_fbank* handle() const { return h_.get(); }
 
 private:
-    struct Del {
-        void operator()(alacgpu_fbank* m) const { alacgpu_fbank_destroy(m); }
-    };
-    std::unique_ptr<alacgpu_fbank, Del> h_;
+    detail::Handle<alacgpu_fbank, alacgpu_fbank_destroy> h_;
 };
 
 inline std::unique_ptr<KaldiFeatures> NewKaldiFeatures(const alacgpu_fbank_config& config, int device = 0) {

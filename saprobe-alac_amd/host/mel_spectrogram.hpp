@@ -13,10 +13,10 @@
 
 #include <cstdint>
 #include <memory>
-#include <stdexcept>
 #include <vector>
 
 #include "../../include/alacgpu.h"
+#include "pass_handle.hpp"
 
 namespace alac {
 
@@ -59,9 +59,7 @@ class MelSpectrogram {
 public:
     explicit MelSpectrogram(const alacgpu_mel_config& config, int device = 0) {
         alacgpu_mel* h = nullptr;
-        const int rc = alacgpu_mel_create(device, &config, &h);
-        if (rc == ALACGPU_E_ARG) throw std::invalid_argument(alacgpu_last_error());
-        if (rc != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::check(alacgpu_mel_create(device, &config, &h));
         h_.reset(h);
     }
 
@@ -71,57 +69,46 @@ public:
     // d_out + r * out_row_stride + b * out_bin_stride + f for b < bins, f < OutFrames(in_frames); exactly those are written
     void MelDevice(const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out, size_t out_row_stride,
                    size_t out_bin_stride, bool sync = false) {
-        const int rc = alacgpu_mel_device(h_.get(), d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride,
-                                          sync ? 1 : 0);
-        if (rc == ALACGPU_E_ARG) throw std::invalid_argument(alacgpu_last_error());
-        if (rc != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::check(alacgpu_mel_device(h_.get(), d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_bin_stride,
+                                         sync ? 1 : 0));
     }
 
     MelPlan Plan() const {
         MelPlan p;
-        if (alacgpu_mel_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0, nullptr, 0) != ALACGPU_E_OK)
-            throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_mel_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0, nullptr, 0));
         alacgpu_mel_fft_info fft{};
-        if (alacgpu_mel_fft_plan(h_.get(), &fft, nullptr, 0, nullptr, 0) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_mel_fft_plan(h_.get(), &fft, nullptr, 0, nullptr, 0));
         // a handle with transform = fft builds no basis: 0 entries
         p.basis.resize(fft.transform == ALACGPU_MEL_TRANSFORM_DIRECT ? (size_t)2 * p.info.n_freqs * p.info.n_fft : 0);
         p.fb.resize((size_t)p.info.n_mels * p.info.taps);
         p.first.resize(p.info.n_mels);
-        if (alacgpu_mel_plan(h_.get(), &p.info, p.basis.data(), p.basis.size(), p.fb.data(), p.fb.size(), p.first.data(),
-                             p.first.size()) != ALACGPU_E_OK)
-            throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_mel_plan(h_.get(), &p.info, p.basis.data(), p.basis.size(), p.fb.data(), p.fb.size(), p.first.data(),
+                                      p.first.size()));
         return p;
     }
 
     MelFftPlan FftPlan() const {
         MelFftPlan p;
-        if (alacgpu_mel_fft_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_mel_fft_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0));
         p.window.resize(p.info.window_entries);
         p.twiddle.resize(p.info.twiddle_entries);
-        if (alacgpu_mel_fft_plan(h_.get(), &p.info, p.window.data(), p.window.size(), p.twiddle.data(), p.twiddle.size()) !=
-            ALACGPU_E_OK)
-            throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_mel_fft_plan(h_.get(), &p.info, p.window.data(), p.window.size(), p.twiddle.data(), p.twiddle.size()));
         return p;
     }
 
     // milliseconds of the last pass: HIP events around its kernels
     float LastMs() {
         float ms = 0;
-        if (alacgpu_mel_last_ms(h_.get(), &ms) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_mel_last_ms(h_.get(), &ms));
         return ms;
     }
 
     void* Stream() const { return alacgpu_mel_stream(h_.get()); }
-    void Synchronize() {
-        if (alacgpu_mel_synchronize(h_.get()) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
-    }
+    void Synchronize() { detail::must(alacgpu_mel_synchronize(h_.get())); }
     alacgpu_mel* handle() const { return h_.get(); }
 
 private:
-    struct Del {
-        void operator()(alacgpu_mel* m) const { alacgpu_mel_destroy(m); }
-    };
-    std::unique_ptr<alacgpu_mel, Del> h_;
+    detail::Handle<alacgpu_mel, alacgpu_mel_destroy> h_;
 };
 
 inline std::unique_ptr<MelSpectrogram> NewMelSpectrogram(const alacgpu_mel_config& config, int device = 0) {

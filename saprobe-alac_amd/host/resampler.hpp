@@ -10,10 +10,10 @@
 
 #include <cstdint>
 #include <memory>
-#include <stdexcept>
 #include <vector>
 
 #include "../../include/alacgpu.h"
+#include "pass_handle.hpp"
 
 namespace alac {
 
@@ -27,9 +27,7 @@ class Resampler {
 public:
     Resampler(uint32_t orig_freq, uint32_t new_freq, int device = 0, uint32_t lowpass_filter_width = 6, double rolloff = 0.99) {
         alacgpu_resampler* h = nullptr;
-        const int rc = alacgpu_resampler_create(device, orig_freq, new_freq, lowpass_filter_width, rolloff, &h);
-        if (rc == ALACGPU_E_ARG) throw std::invalid_argument(alacgpu_last_error());
-        if (rc != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::check(alacgpu_resampler_create(device, orig_freq, new_freq, lowpass_filter_width, rolloff, &h));
         h_.reset(h);
     }
 
@@ -39,39 +37,31 @@ public:
     // OutFrames(in_frames); exactly those columns of every output row are written
     void ResampleDevice(const float* d_in, size_t in_row_stride, size_t rows, size_t in_frames, float* d_out,
                         size_t out_row_stride, bool sync = false) {
-        const int rc = alacgpu_resample_device(h_.get(), d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, sync ? 1 : 0);
-        if (rc == ALACGPU_E_ARG) throw std::invalid_argument(alacgpu_last_error());
-        if (rc != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::check(alacgpu_resample_device(h_.get(), d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, sync ? 1 : 0));
     }
 
     ResamplePlan Plan() const {
         ResamplePlan p;
-        if (alacgpu_resampler_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_resampler_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0));
         p.h.resize((size_t)p.info.n * p.info.taps);
         p.first.resize(p.info.n);
-        if (alacgpu_resampler_plan(h_.get(), &p.info, p.h.data(), p.h.size(), p.first.data(), p.first.size()) != ALACGPU_E_OK)
-            throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_resampler_plan(h_.get(), &p.info, p.h.data(), p.h.size(), p.first.data(), p.first.size()));
         return p;
     }
 
     // milliseconds of the last pass: HIP events around its kernels
     float LastMs() {
         float ms = 0;
-        if (alacgpu_resampler_last_ms(h_.get(), &ms) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
+        detail::must(alacgpu_resampler_last_ms(h_.get(), &ms));
         return ms;
     }
 
     void* Stream() const { return alacgpu_resampler_stream(h_.get()); }
-    void Synchronize() {
-        if (alacgpu_resampler_synchronize(h_.get()) != ALACGPU_E_OK) throw std::runtime_error(alacgpu_last_error());
-    }
+    void Synchronize() { detail::must(alacgpu_resampler_synchronize(h_.get())); }
     alacgpu_resampler* handle() const { return h_.get(); }
 
 private:
-    struct Del {
-        void operator()(alacgpu_resampler* r) const { alacgpu_resampler_destroy(r); }
-    };
-    std::unique_ptr<alacgpu_resampler, Del> h_;
+    detail::Handle<alacgpu_resampler, alacgpu_resampler_destroy> h_;
 };
 
 inline std::unique_ptr<Resampler> NewResampler(uint32_t orig_freq, uint32_t new_freq, int device = 0,

@@ -103,7 +103,9 @@ def test_refusals_in_the_library_source():
     before it plans or touches HIP, with a message that names the rule, and nothing falls back to the direct transform."""
     src = open(os.path.join(ROOT, "saprobe-alac_amd", "csrc", "k_mel.hip")).read()
     body = src[src.index("int alacgpu_mel_create("):src.index("void alacgpu_mel_destroy(")]
-    assert body.index("config->transform > ALACGPU_MEL_TRANSFORM_FFT") < body.index("size_ok(") < body.index("hipSetDevice")
+    host = open(os.path.join(ROOT, "saprobe-alac_amd", "csrc", "alac_host.h")).read()
+    assert "hipSetDevice" in host[host.index("void open(int dev)"):host.index("void upload(")] and "hip" not in body[:body.index("r->open(")]
+    assert body.index("config->transform > ALACGPU_MEL_TRANSFORM_FFT") < body.index("size_ok(") < body.index("r->open(device)")  # the first HIP call
     assert "2^a 3^b 5^c" in body
     hdr = open(os.path.join(ROOT, "include", "alacgpu.h")).read()
     cfg = hdr[hdr.index("typedef struct alacgpu_mel_config"):hdr.index("} alacgpu_mel_config;")]
