@@ -6,7 +6,10 @@ WHOLE buffer is compared bit for bit: the values, the zeros, and every element o
 sentinel. The slots are written by hand (wave_ref.hand_slots): random bytes behind a slot's frames and in failed slots,
 which must not show.
 
+The inputs come from the lists of tests/clip_ref.py, which tests/test_gpu_clip_geometry.py runs on the device.
+
 * depths 16/20/24/32 x FLOAT/INT x channels 1/2/6/8; frame lengths 1/7/16/33/4096 x clip lengths 1/3/255/256/257/1000;
+* tiles of 294 and 334 segments (FL 7 and 3), FL 2 with three channels, FL 1 at the smallest pitch (clip_ref.ADDED);
 * every begin % 4 x every base offset of 0..3 elements, with odd strides;
 * short and failed slots inside a clip, limit cutting a clip, begin at / around / past the batch and at 2^64 - 1, limit 0 and
   above n, hostile d_frames, NULL d_status / d_valid / d_clip_status, no clips, no packets;
@@ -23,23 +26,12 @@ from tests import clip_ref as cr
 from tests import wave_ref as wr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U64 = (1 << 64) - 1
+U64 = cr.U64
 
 
 @pytest.fixture(scope="module")
 def sim():
     return cr.build_clip_sim()
-
-
-def slots(rng, n, fl, depth, ch, pattern="short", failed=(), extra=0, exact=False):
-    """(out, frames, status): hand-written slots; the stride the decode's fast one plus `extra`, or exactly the frame bytes."""
-    fb = fl * ch * wr.BPS[depth]
-    stride = fb if exact else (fb + 15) // 16 * 16 + extra
-    frames = wr.frame_counts(rng, n, fl, pattern)
-    status = np.zeros(n, np.int32)
-    for k, i in enumerate(failed):
-        status[i] = (0x1101, 3, 0x2202)[k % 3]
-    return wr.hand_slots(rng, n, fl, depth, ch, stride, frames), frames, status
 
 
 def run_sim(S, fl, depth, ch, out, frames, status, begin, limit, L, wtype, base=0, slack=None, pcm_mis=0, want_valid=True,
@@ -91,60 +83,62 @@ def check(S, fl, depth, ch, out, frames, status, begin, limit, L, wtype, **kw):
     return ref, r_valid, r_cstat
 
 
-def spread(rng, n, fl, L):
-    """Clip descriptors all over a batch of n slots: in one slot, across slot boundaries, over the short and failed slots in
-    the middle, at the batch's end, and a few at random -> (begin, limit)."""
-    total = n * fl
-    begin = [0, 1, 2, 3, fl - 1, fl, fl + 1, max(total // 2 - L // 2, 0), max(total - L, 0), max(total - L, 0) + 1, total - 1]
-    begin += [int(x) for x in rng.integers(0, total, 5)]
-    limit = [n] * len(begin)
-    return begin, limit
-
-
-@pytest.mark.parametrize("ch", [1, 2, 6, 8])
-@pytest.mark.parametrize("depth", [16, 20, 24, 32])
+@pytest.mark.parametrize("ch", cr.CHANNELS)
+@pytest.mark.parametrize("depth", cr.DEPTHS)
 def test_host_build_equals_numpy_over_depths_and_channels(sim, depth, ch):
-    rng = np.random.default_rng(depth * 10 + ch)
-    fl, n, L = 33, 12, 100
-    out, frames, status = slots(rng, n, fl, depth, ch, failed=(4,))
-    begin, limit = spread(rng, n, fl, L)
-    for wtype in (wr.FLOAT, wr.INT):
-        check(sim, fl, depth, ch, out, frames, status, begin, limit, L, wtype)
+    for run in cr.depth_channel_runs(depth, ch):
+        check(sim, *run.args(), **run.kw)
 
 
-@pytest.mark.parametrize("L", [1, 3, 255, 256, 257, 1000])
-@pytest.mark.parametrize("fl", [1, 7, 16, 33, 4096])
+@pytest.mark.parametrize("L", cr.GRID_L)
+@pytest.mark.parametrize("fl", cr.GRID_FL)
 def test_frame_lengths_and_clip_lengths(sim, fl, L):
     """Clips inside one slot, over many slots, and longer than a tile (8-channel 32-bit tiles are 256 columns, fewer at the
     smallest frame lengths)."""
-    rng = np.random.default_rng(fl * 1000 + L)
-    n = max(3, min(1200, (L + 300) // fl + 3))
-    for depth, ch, wtype in ((16, 2, wr.FLOAT), (32, 8, wr.INT), (24, 6, wr.FLOAT)):
-        out, frames, status = slots(rng, n, fl, depth, ch, failed=(n // 2 + 1,) if n > 4 else ())
-        begin, limit = spread(rng, n, fl, L)
-        check(sim, fl, depth, ch, out, frames, status, begin, limit, L, wtype)
+    runs = list(cr.grid_runs(fl, L))
+    assert [(r.depth, r.ch, r.wtype) for r in runs] == list(cr.GRID_FORMATS)
+    for run in runs:
+        check(sim, *run.args(), **run.kw)
 
 
-@pytest.mark.parametrize("depth,ch,fl,L", [(16, 2, 33, 257), (24, 6, 7, 255), (32, 1, 4096, 1000), (20, 8, 16, 256), (16, 1, 1, 300)])
+@pytest.mark.parametrize("depth,ch,fl,L", cr.ADDED)
+def test_added_geometries(sim, depth, ch, fl, L):
+    """More than 256 segments in one tile (the second turn of the segment-entry loop), FL 2 with three channels, and the
+    smallest pitch, three chunks; each case reaches what it is there for."""
+    runs = list(cr.added_runs(depth, ch, fl, L))
+    geo = runs[0].geometry(sim.clip_sim_tile_cols(fl, depth, ch))
+    want = {(32, 1, 7, 2100): dict(tile_cols=2048, tiles_per_clip=2, chunks=4, nseg=294),
+            (16, 1, 3, 1000): dict(tile_cols=1024, tiles_per_clip=1, chunks=3, nseg=334),
+            (24, 3, 2, 900): dict(tile_cols=448, tiles_per_clip=3, chunks=4, nseg=226),
+            (16, 1, 1, 300): dict(tile_cols=256, tiles_per_clip=2, chunks=3, nseg=256)}[(depth, ch, fl, L)]
+    assert geo == want, geo
+    for run in runs:
+        check(sim, *run.args(), **run.kw)
+
+
+def test_the_shared_lists_reach_the_geometry_they_are_there_for(sim):
+    """Across the grid and the added geometries: a tile of more than 256 segments, the 3-chunk pitch, two tiles per clip at 8 x 32
+    bits, clips shorter than a quad; and the staging of every one of them fits the segment table."""
+    geos = cr.list_geometries(sim.clip_sim_tile_cols)
+    assert max(g["nseg"] for g in geos.values()) > 256 and geos[(16, 2, 1, 1000)]["nseg"] == 259
+    assert min(g["chunks"] for g in geos.values()) == 3 and geos[(16, 2, 1, 256)]["chunks"] == 3
+    assert geos[(32, 8, 4096, 257)]["tile_cols"] == 256 and geos[(32, 8, 4096, 257)]["tiles_per_clip"] == 2
+    assert any(k[3] < 4 for k in geos)
+    assert all(g["nseg"] * g["chunks"] * 16 <= sim.clip_sim_stage_bytes() for g in geos.values())
+
+
+@pytest.mark.parametrize("depth,ch,fl,L", cr.ALIGN_CASES)
 def test_every_alignment_gives_the_same_values(sim, depth, ch, fl, L):
     """Every begin % 4 with every base offset of 0..3 elements, odd channel and clip strides, slots at odd byte alignments."""
-    rng = np.random.default_rng(depth + ch + fl)
-    n = max(4, (L + 40) // fl + 3)
-    for pcm_mis, extra in ((0, 0), (5, 3), (8, 16)):
-        out, frames, status = slots(rng, n, fl, depth, ch, pattern="odd", failed=(2,), extra=extra)
-        for base in range(4):
-            begin = [fl + b for b in range(4)] + [5 * b for b in range(4)]
-            for wtype, slack in ((wr.FLOAT, None), (wr.INT, 3 + L % 2)):
-                check(sim, fl, depth, ch, out, frames, status, begin, [n] * len(begin), L, wtype, base=base, slack=slack, pcm_mis=pcm_mis)
+    runs = list(cr.alignment_runs(depth, ch, fl, L))
+    assert len(runs) == 24
+    for run in runs:
+        check(sim, *run.args(), **run.kw)
 
 
 def test_short_and_failed_slots_leave_a_zero_gap(sim):
     """Worked by hand: slot 1 holds 5 of 16 frames, slot 2 failed with a frame count left standing."""
-    rng = np.random.default_rng(1)
-    fl, depth, ch, n, L = 16, 16, 2, 4, 48
-    frames = np.array([16, 5, 16, 16], np.uint32)
-    status = np.array([0, 0, 0x1101, 0], np.int32)
-    out = wr.hand_slots(rng, n, fl, depth, ch, fl * ch * 2, frames)
+    fl, depth, ch, n, L, out, frames, status = cr.short_and_failed_case()
     ref, valid, cstat = check(sim, fl, depth, ch, out, frames, status, [8, 0, 40], [n, n, n], L, wr.FLOAT)
     assert list(valid) == [8 + 5 + 0 + 8, 16 + 5 + 0, 0 + 16] and list(cstat) == [0x1101, 0x1101, 0x1101]
     assert not ref[0, :, 8 + 5:8 + 32].any() and not ref[2, :, :8].any() and not ref[2, :, 24:].any()
@@ -158,26 +152,20 @@ def test_short_and_failed_slots_leave_a_zero_gap(sim):
 
 
 def test_limit_cuts_a_clip(sim):
-    rng = np.random.default_rng(2)
-    fl, depth, ch, n, L = 16, 24, 2, 6, 40
-    frames = np.full(n, fl, np.uint32)
-    status = np.zeros(n, np.int32)
-    status[3] = 7
-    out = wr.hand_slots(rng, n, fl, depth, ch, fl * ch * 3, frames)
-    begin, limit = [20, 20, 20, 20, 20, 50], [n, 3, 2, 1, 0, 3]
+    fl, depth, ch, n, L, out, frames, status, begin, limit = cr.limit_case()
     ref, valid, cstat = check(sim, fl, depth, ch, out, frames, status, begin, limit, L, wr.INT)
     # the failed slot 3 is touched only under the full limit; a limit at or below the clip's first slot leaves nothing
     assert list(valid) == [40 - 12, 28, 12, 0, 0, 0] and list(cstat) == [7, 0, 0, 0, 0, 0]
     assert ref[1, :, :28].any() and not ref[1, :, 28:].any() and not ref[3].any()
 
 
-@pytest.mark.parametrize("depth,ch,fl,L", [(16, 2, 33, 100), (32, 8, 7, 257), (24, 1, 4096, 5000)])
+@pytest.mark.parametrize("depth,ch,fl,L", cr.PAST_CASES)
 def test_descriptors_at_and_past_the_batch(sim, depth, ch, fl, L):
     """begin at, just before and past n * frame_length and at the top of 64 bits; limit 0 and above n: zeros where the grid
     has no slot, no read outside the slots."""
     rng = np.random.default_rng(L)
     n = 5
-    out, frames, status = slots(rng, n, fl, depth, ch, failed=(1,))
+    out, frames, status = cr.slots(rng, n, fl, depth, ch, failed=(1,))
     total = n * fl
     begin = [total - 1, total, total + 1, max(total - L, 0), max(total - L, 0) + 1, total + L, U64, U64 - 1, U64 - L, U64 - L + 1, 1 << 63, (1 << 63) - 1,
              (1 << 32) - 1, 1 << 32, 0, 0, 0, 3, fl]
@@ -189,30 +177,24 @@ def test_descriptors_at_and_past_the_batch(sim, depth, ch, fl, L):
 
 
 def test_hostile_frame_counts_are_clamped(sim):
-    rng = np.random.default_rng(5)
-    fl, depth, ch, n, L = 100, 16, 2, 12, 333
-    out, frames, _ = slots(rng, n, fl, depth, ch, pattern="hostile")
-    assert frames[n // 3] == fl + 5 and frames[(2 * n) // 3] == 0xFFFFFFFF
-    begin, limit = spread(rng, n, fl, L)
-    ref, valid, _ = check(sim, fl, depth, ch, out, frames, None, begin, limit, L, wr.FLOAT)
-    assert valid.max() <= L
+    run = cr.hostile_run()
+    assert run.frames[len(run.frames) // 3] == run.fl + 5 and run.frames[(2 * len(run.frames)) // 3] == 0xFFFFFFFF and run.status is None
+    ref, valid, _ = check(sim, *run.args(), **run.kw)
+    assert valid.max() <= run.L
 
 
 def test_null_status_valid_and_clip_status(sim):
-    rng = np.random.default_rng(6)
-    fl, depth, ch, n, L = 33, 24, 2, 9, 257
-    out, frames, status = slots(rng, n, fl, depth, ch, pattern="odd", failed=(3,))
-    begin, limit = spread(rng, n, fl, L)
-    check(sim, fl, depth, ch, out, frames, None, begin, limit, L, wr.FLOAT)
-    check(sim, fl, depth, ch, out, frames, status, begin, limit, L, wr.INT, want_valid=False)
-    check(sim, fl, depth, ch, out, frames, status, begin, limit, L, wr.INT, want_status=False)
-    check(sim, fl, depth, ch, out, frames, None, begin, limit, L, wr.FLOAT, want_valid=False, want_status=False)
+    runs = list(cr.null_runs())
+    assert [(r.status is None, r.kw.get("want_valid", True), r.kw.get("want_status", True)) for r in runs] == [
+        (True, True, True), (False, False, True), (False, True, False), (True, False, False)]
+    for run in runs:
+        check(sim, *run.args(), **run.kw)
 
 
 def test_no_clips_and_no_packets(sim):
     rng = np.random.default_rng(7)
     fl, depth, ch, L = 33, 16, 2, 70
-    out, frames, status = slots(rng, 4, fl, depth, ch)
+    out, frames, status = cr.slots(rng, 4, fl, depth, ch)
     img, lead, cs, ps, _, _ = run_sim(sim, fl, depth, ch, out, frames, status, [], [], L, wr.FLOAT)
     assert np.all(img == wr.SENTINEL)  # nothing is touched
     assert sim.clip_sim_run(fl, depth, ch, None, 0, None, None, 0, None, None, 0, L, wr.FLOAT, None, 0, 0, None, None, 0) == 0
@@ -221,18 +203,15 @@ def test_no_clips_and_no_packets(sim):
     assert not ref.any() and not valid.any() and not cstat.any()
 
 
-@pytest.mark.parametrize("depth,ch,fl,L", [(16, 2, 33, 100), (24, 3, 7, 257), (32, 8, 64, 300), (16, 1, 4096, 1000)])
+@pytest.mark.parametrize("depth,ch,fl,L", cr.EXACT_CASES)
 def test_slots_that_end_at_an_inaccessible_page(sim, depth, ch, fl, L):
     """pcm_stride exactly the frame bytes and a short last slot, whose last frame's last byte is the last accessible one: a read
     behind a slot's frames that leaves the buffer is fatal here."""
-    rng = np.random.default_rng(fl)
-    n = 6
-    out, frames, status = slots(rng, n, fl, depth, ch, failed=(2,), exact=True)
-    frames[n - 1] = max(fl - 3, 1)
+    n = cr.EXACT_SLOTS
+    out, frames, status, begin = cr.exact_stride_case(depth, ch, fl, L)
     bpf = ch * wr.BPS[depth]
+    assert out.shape == (n, fl * bpf) and frames[n - 1] == max(fl - 3, 1)
     guard = (n - 1) * out.shape[1] + int(frames[n - 1]) * bpf
-    total = n * fl
-    begin = [max(total - L, 0), max(total - L // 2, 0), total - 1, total - 3, total, 0, (n - 1) * fl, U64]
     for wtype in (wr.FLOAT, wr.INT):
         check(sim, fl, depth, ch, out, frames, status, begin, [n] * len(begin), L, wtype, guard_bytes=guard)
     # hostile: the last slot claims more frames than it has room for; the clamp to frame_length keeps the reads inside

@@ -156,6 +156,32 @@ def test_pass_without_sync(torch, pkg, sim):
     assert_same_image(img, mr.expected_image(y, img.size, lay[5], lay[3], lay[4]), "sync=False", lay)
 
 
+def test_small_inputs_and_no_work(torch, pkg):
+    """tests/test_gpu_mel.py's test on an FFT handle: calls without work, which touch nothing, and what the entry refuses before a
+    launch."""
+    cfg = mr.CASES["tiny"]
+    with new_fft(pkg, cfg) as ms:
+        assert ms.fft_plan()["transform"] == 1 and ms.out_frames(40) == 11 and cfg.bins == 5 and ms.out_frames(8) == 0
+        buf = torch.full((1024,), 7.0, dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        B = buf.data_ptr()
+        ms.mel_device(B, 40, 0, 40, B + 2048, 55, 11)       # no rows
+        ms.mel_device(B, 40, 2, 8, B + 2048, 55, 11)        # rows of n_fft / 2 samples: no frame
+        ms.mel_device(None, 0, 0, 0, None, 0, 0)
+        ms.synchronize()
+        assert bool((buf == 7.0).all().item())
+        for bad in [(None, 40, 2, 40, B + 2048, 55, 11), (B, 40, 2, 40, None, 55, 11), (B + 2, 40, 2, 40, B + 2048, 55, 11),
+                    (B, 40, 2, 40, B + 2049, 55, 11), (B, 39, 2, 40, B + 2048, 55, 11), (B, 40, 2, 40, B + 2048, 55, 10),
+                    (B, 40, 2, 40, B + 2048, 54, 11), (B, 1 << 62, 2, 40, B + 2048, 55, 11), (B, 40, 2, 40, B + 2048, 1 << 62, 11)]:
+            with pytest.raises(ValueError):
+                ms.mel_device(*bad)
+        ms.synchronize()
+        assert bool((buf == 7.0).all().item())
+        ms.mel_device(B, 40, 2, 40, B + 2048, 55, 11)       # and the same call with everything in order does write
+        assert not bool((buf[512:512 + 110] == 7.0).any().item()) and bool((buf[:512] == 7.0).all().item())
+        assert bool((buf[512 + 110:] == 7.0).all().item())
+
+
 def test_python_entries(torch, pkg, sim):
     """mel_spectrogram, spectrogram and whisper_log_mel with transform="fft" give the host build's bits; the cache keeps a direct
     and an FFT handle of one parameter set apart; transform="direct" gives the bits of a call without the keyword."""

@@ -1,6 +1,6 @@
-"""The second launch of the six tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
-alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip), alac_wave_pack (k_wavepack.hip), alac_mel_rows (k_mel.hip) and
-alac_fbank_rows (k_fbank.hip). Each launch gets the slice's
+"""The second launch of the seven tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
+alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip), alac_wave_pack (k_wavepack.hip), alac_mel_rows (k_mel.hip),
+alac_melfft_rows (k_melfft.hip) and alac_fbank_rows (k_fbank.hip). Each launch gets the slice's
 first tile as first_tile; only a batch of more than 2^22 tiles has a second slice, and a launch that lost its first_tile would
 corrupt such batches alone, silently.
 
@@ -17,6 +17,7 @@ import pytest
 from tests import clip_ref as cr
 from tests import kaldi_ref as kr
 from tests import mel_ref as mr
+from tests import melfft_ref as fr
 from tests import resample_ref as rr
 from tests import wave_ref as wr
 from tests import wavepack_ref as pr
@@ -210,6 +211,37 @@ def test_second_launch_of_alac_mel_rows(torch, pkg):
     torch.cuda.synchronize()
     with pkg.NewMelSpectrogram(**cfg.kwargs()) as ms:
         assert ms.out_frames(T) == F and N * -(-F // ms.plan()["tile_frames"]) > SLICE
+        ms.mel_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, K * F, F, sync=True)
+    assert_cycle(torch, buf[LEAD:LEAD + N * K * F], np.ascontiguousarray(want7).view(np.int32), "rows")
+    assert_guards(buf, N * K * F, fill)
+
+
+def test_second_launch_of_alac_melfft_rows(torch, pkg):
+    """The same with transform="fft": N rows of 3 samples, n_fft 4, win_length 4, hop 2, centred, no mel stage: 2 frames of 3
+    bins, tile_frames 64, so tiles_per_row = 1, tile = row and the second launch has first_tile = 2^22; M = 2, so one radix-2 pass
+    runs (n_fft 2 has none). Row r is class r % 7; the expectation is the host build's output for the 7 rows (50 MB in, 101 MB
+    out).
+
+    A launch that ignored first_tile would compute rows 0 .. 4 098 again and leave the rows from 2^22 on unwritten (the
+    sentinel); one that wrote to the slice's rows but read from the batch's start would give row 2^22 + j the spectrogram of
+    row j, whose class j % 7 is not (2^22 + j) % 7."""
+    sim = fr.build_melfft_sim()
+    cfg = mr.Cfg(8000, 4, 2, 4)
+    T, F, K = 3, 2, 3
+    rows7 = np.random.default_rng(16).uniform(-1, 1, (7, T)).astype(np.float32)
+    rows7[3] = [1.0, -1.0, 1.0]
+    img, lay = fr.sim_image(sim, cfg, rows7)
+    assert mr.out_frames(cfg, T) == F and cfg.K == K
+    want7 = mr.rows_of(img, 7, K, F, lay[5], lay[3], lay[4])
+    assert want7.shape == (7, K, F) and len({w.tobytes() for w in want7}) == 7
+    x = cycled(torch, rows7, N)
+    fill = mr.SENTINEL - (1 << 32)
+    buf = sentinel_buffer(torch, N * K * F, fill, torch.int32)
+    torch.cuda.synchronize()
+    with pkg.NewMelSpectrogram(transform="fft", **cfg.kwargs()) as ms:
+        fft = ms.fft_plan()
+        assert fft["transform"] == 1 and fft["radix"] == [2] and fft["tile_frames"] == 64
+        assert ms.out_frames(T) == F and N * -(-F // fft["tile_frames"]) > SLICE
         ms.mel_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, K * F, F, sync=True)
     assert_cycle(torch, buf[LEAD:LEAD + N * K * F], np.ascontiguousarray(want7).view(np.int32), "rows")
     assert_guards(buf, N * K * F, fill)
