@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import edge_pcm
+from tests.far_buffers import _need_gb
 from tests.test_encoder_host import BPS, EncSim, make_pcm, oracle_round_trip
 
 pytestmark = pytest.mark.gpu
@@ -310,12 +311,6 @@ def _check_cycled_batch(torch, pkg, ocfg, n, pcm7, blob7, sizes7):
     rest = int(prefix[n % 7].item())
     assert torch.equal(d_blob[full * period:full * period + rest], row[:rest])
     assert bool((d_blob[full * period + rest:] == 0xAB).all())
-
-
-def _need_gb(torch, gb):
-    free, _ = torch.cuda.mem_get_info()
-    if free < gb * (1 << 30):
-        pytest.skip("needs %d GB of device memory, %.1f free" % (gb, free / (1 << 30)))
 
 
 def test_gpu_two_launches_of_alac_enc_pack(pkg, torch, synth, oracle, enc_sim):
