@@ -594,6 +594,20 @@ int alacgpu_mel_fft_plan(const alacgpu_mel* mel, alacgpu_mel_fft_info* info, flo
  * finite, scale 0, energy_floor < 0, not 0 <= low_freq < Nyquist, 0 < high <= Nyquist, low < high, a filter whose weights
  * are not one run, or four frames that do not fit 64 KB of LDS. The handle owns a stream, an event pair and the tables on the
  * device; it is single-caller, like a decoder.
+ *
+ * alacgpu_fbank_create_transform with ALACGPU_FBANK_TRANSFORM_FFT (opt-in; k_fbankfft.hip, alac_fbankfft.h)
+ * runs the frame's steps one after the other in float32 and a mixed-radix FFT out of LDS in place of the chains over the folded
+ * basis; frames, energy, mel, log, MFCC and output are the same functions. The DFT size N must be even, in [2, 2048], with M = N /
+ * 2 = 2^a 3^b 5^c: with round_to_power_of_two every frame_length in [2, 2048], without it frame_length itself. Any other size is
+ * ALACGPU_E_ARG before any HIP call (there is no fall-back to the direct transform), and so is a transform above 1.
+ *     mean    remove_dc_offset: P = 256 / tile_frames classes, s_j = the float32 sum of x[n], n = j, j + P, .. < W upwards from
+ *             +0.0f; for d = P / 2 .. 1: s_j += s_{j + d}, j < d; mean = s_0 / (float)W (a division). Otherwise +0.0f, v = x.
+ *     v[n]    = x[n] - mean;  y[n] = fmaf(-c32, v[n - 1], v[n]), v[-1] = v[0], c32 = float(preemphasis_coefficient), y = v at 0
+ *     z[n]    = ws[n] * y[n], ws[n] = float(scale * window[n]); +0.0f for W <= n < N;  Z[m] = z[2 m] + i z[2 m + 1]
+ *     p[k]    from Z by the passes and the split step of ALACGPU_MEL_TRANSFORM_FFT above
+ * with every float operation in a fixed order and none contracted, so up to the logs every build gives the same bits; they are
+ * not the direct transform's, except the energy column, which is. A constant frame whose sum and mean are exact gives +0.0 in
+ * every mel column, as Kaldi does.
  */
 enum {
     ALACGPU_FBANK_WINDOW_HANNING = 0,
@@ -603,6 +617,7 @@ enum {
     ALACGPU_FBANK_WINDOW_BLACKMAN = 4
 };
 enum { ALACGPU_FBANK_LAYOUT_FRAMES = 0, ALACGPU_FBANK_LAYOUT_BINS = 1 };
+enum { ALACGPU_FBANK_TRANSFORM_DIRECT = 0, ALACGPU_FBANK_TRANSFORM_FFT = 1 };
 typedef struct alacgpu_fbank_config {
     uint32_t sample_rate;
     uint32_t frame_length;          /* W, samples: 1 .. 2048 */
@@ -631,6 +646,9 @@ typedef struct alacgpu_fbank_config {
 } alacgpu_fbank_config;
 typedef struct alacgpu_fbank alacgpu_fbank;
 int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu_fbank** out);
+/* alacgpu_fbank_create with a transform, ALACGPU_FBANK_TRANSFORM_*: 0 is alacgpu_fbank_create itself. Every other entry serves
+ * both kinds of handle. */
+int alacgpu_fbank_create_transform(int device, const alacgpu_fbank_config* config, uint32_t transform, alacgpu_fbank** out);
 void alacgpu_fbank_destroy(alacgpu_fbank* fb);
 /* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
  * milliseconds: HIP events around its kernels (valid after a sync). */
@@ -661,6 +679,19 @@ typedef struct alacgpu_fbank_info {
 int alacgpu_fbank_plan(const alacgpu_fbank* fb, alacgpu_fbank_info* info, float* basis_out, size_t basis_cap, float* fb_out,
                        size_t fb_cap, int32_t* first_out, size_t first_cap, float* dct_out, size_t dct_cap, float* lifter_out,
                        size_t lifter_cap);
+/* The plan of the handle's transform, as alacgpu_mel_fft_plan. On a handle with ALACGPU_FBANK_TRANSFORM_FFT (whose
+ * alacgpu_fbank_plan reports a basis of 0 entries: none is built; basis_out is left alone): tile_frames and lds_bytes (the FFT's
+ * own choice, which alacgpu_fbank_plan reports as well), batch_frames, pitch, the passes' radices in order, and (where the
+ * pointers are not NULL and the capacities suffice) the window ws[n_fft] = float(scale * window[n]), +0.0f from frame_length on,
+ * and the twiddle table laid out as alacgpu_mel_fft_plan's. On a direct handle transform is 0, tile_frames and lds_bytes are
+ * alacgpu_fbank_plan's, and everything else is 0. */
+typedef struct alacgpu_fbank_fft_info {
+    uint32_t transform, tile_frames, lds_bytes, batch_frames, pitch, n_passes;
+    uint32_t radix[8];
+    uint32_t window_entries, twiddle_entries;
+} alacgpu_fbank_fft_info;
+int alacgpu_fbank_fft_plan(const alacgpu_fbank* fb, alacgpu_fbank_fft_info* info, float* window_out, size_t window_cap,
+                           float* twiddle_out, size_t twiddle_cap);
 
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);

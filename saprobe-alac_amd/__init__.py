@@ -286,6 +286,7 @@ _EXPORTS = {
     "alacgpu_mel_fft_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                             ctypes.c_size_t]),
     "alacgpu_fbank_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_fbank_create_transform": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
     "alacgpu_fbank_destroy": (None, [ctypes.c_void_p]),
     "alacgpu_fbank_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "alacgpu_fbank_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
@@ -296,6 +297,8 @@ _EXPORTS = {
     "alacgpu_fbank_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                           ctypes.c_void_p, ctypes.c_size_t]),
+    "alacgpu_fbank_fft_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                              ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -1241,8 +1244,22 @@ class FbankInfo(ctypes.Structure):
                                                "cols", "tile_frames", "lds_bytes")]
 
 
+class FbankFftInfo(ctypes.Structure):
+    """alacgpu_fbank_fft_info (include/alacgpu.h)."""
+
+    _fields_ = MelFftInfo._fields_
+
+
+_FBANK_TRANSFORMS = {"direct": 0, "fft": 1}
 _FBANK_WINDOWS = {"hanning": 0, "hamming": 1, "povey": 2, "rectangular": 3, "blackman": 4}
 _FBANK_LAYOUTS = {"frames": 0, "bins": 1}
+
+
+def _fbank_transform(transform):
+    """"direct" or "fft" -> ALACGPU_FBANK_TRANSFORM_*; ValueError for anything else"""
+    if not isinstance(transform, str) or transform not in _FBANK_TRANSFORMS:
+        raise ValueError("transform is 'direct' or 'fft', not %r" % (transform,))
+    return _FBANK_TRANSFORMS[transform]
 
 
 def _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps, round_to_power_of_two, snip_edges, remove_dc_offset,
@@ -1277,6 +1294,10 @@ class KaldiFeatures(_RowPass):
     [..., cols, F]. log_energy=False keeps the energy column unlogged (for checks). MFCC with htk_compat and without use_energy
     ends in sqrt(2) C0 (plan()["dct"][0] is sqrt(2 / num_mel_bins) there). ValueError when no plan can be built:
     dither != 0, vtln_warp != 1, use_power False and use_energy without raw_energy among them, before any HIP call.
+    transform="fft" (keyword only; the default "direct" is the fmaf chains over the folded basis) removes the mean, pre-emphasises
+    and windows each frame in float32 and computes the powers by a mixed-radix FFT: the DFT size (the next power of two >=
+    frame_length with round_to_power_of_two, else frame_length) must be even with its half 2^a 3^b 5^c, any other is a ValueError,
+    never a fall-back; the result is fixed bit for bit as well, but only its energy column is the direct transform's.
     Single-caller, bound to one device and one stream. out_frames(T) is alacgpu_fbank_out_frames: 1 + (T - W) / h with snip_edges,
     (T + h / 2) / h without; 0 for T < W."""
 
@@ -1287,13 +1308,19 @@ class KaldiFeatures(_RowPass):
                  snip_edges=True, remove_dc_offset=True, window_type="povey", use_log_fbank=True, use_energy=False, raw_energy=True,
                  htk_compat=False, use_power=True, log_energy=True, layout="frames", preemphasis_coefficient=0.97,
                  blackman_coeff=0.42, low_freq=20.0, high_freq=0.0, energy_floor=1.0, scale=1.0, cepstral_lifter=22.0, dither=0.0,
-                 vtln_warp=1.0, device=0):
+                 vtln_warp=1.0, device=0, *, transform="direct"):
         super().__init__()
+        self.transform = transform
+        self._transform = _fbank_transform(transform)
         self.config = _fbank_config(sample_rate, frame_length, frame_shift, num_mel_bins, num_ceps, round_to_power_of_two, snip_edges,
                                     remove_dc_offset, window_type, use_log_fbank, use_energy, raw_energy, htk_compat, use_power,
                                     log_energy, layout, preemphasis_coefficient, blackman_coeff, low_freq, high_freq, energy_floor,
                                     scale, cepstral_lifter, dither, vtln_warp)
-        self._create(device, ctypes.byref(self.config))
+        if self._transform:
+            self._CREATE = "alacgpu_fbank_create_transform"
+            self._create(device, ctypes.byref(self.config), self._transform)
+        else:
+            self._create(device, ctypes.byref(self.config))
         self.layout = layout
         self.cols = int(num_ceps) if int(num_ceps) else int(num_mel_bins) + int(bool(use_energy))
 
@@ -1308,14 +1335,26 @@ class KaldiFeatures(_RowPass):
     def plan(self):
         """alacgpu_fbank_plan -> dict: the numbers of alacgpu_fbank_info and the host copies of the tables the kernel uses: basis
         [2, n_freqs, frame_length] float32 (C, then S, folded), fb [num_mel_bins, taps], first [num_mel_bins] int32, dct
-        [num_ceps, num_mel_bins] and lifter [num_ceps]."""
+        [num_ceps, num_mel_bins] and lifter [num_ceps]. A handle with transform="fft" has no basis: [2, 0, frame_length]."""
         info = FbankInfo()
         basis, fb, first, dct, lifter = _fetch_plan(
-            self._lib.alacgpu_fbank_plan, self._h, info, lambda i: np.zeros((2, i.n_freqs, i.frame_length), np.float32),
+            self._lib.alacgpu_fbank_plan, self._h, info,
+            lambda i: np.zeros((2, 0 if self._transform else i.n_freqs, i.frame_length), np.float32),
             lambda i: np.zeros((i.num_mel_bins, i.taps), np.float32), lambda i: np.zeros(i.num_mel_bins, np.int32),
             lambda i: np.zeros((i.num_ceps, i.num_mel_bins), np.float32), lambda i: np.zeros(i.num_ceps, np.float32))
         out = {k: int(getattr(info, k)) for k, _ in FbankInfo._fields_}
         out.update(basis=basis, fb=fb, first=first, dct=dct, lifter=lifter)
+        return out
+
+    def fft_plan(self):
+        """alacgpu_fbank_fft_plan -> dict: transform (0 direct, 1 fft), tile_frames, lds_bytes, batch_frames, pitch, n_passes, radix
+        (the passes' radices in order), and the tables window [n_fft] float32 (scale * window, zeros from frame_length on) and
+        twiddle float32 (laid out as MelSpectrogram.fft_plan's). On a direct handle: transform 0, no passes, empty tables."""
+        info = FbankFftInfo()
+        window, twiddle = _fetch_plan(self._lib.alacgpu_fbank_fft_plan, self._h, info, lambda i: np.zeros(i.window_entries, np.float32),
+                                      lambda i: np.zeros(i.twiddle_entries, np.float32))
+        out = {k: int(getattr(info, k)) for k in ("transform", "tile_frames", "lds_bytes", "batch_frames", "pitch", "n_passes")}
+        out.update(radix=[int(r) for r in info.radix[:info.n_passes]], window=window, twiddle=twiddle)
         return out
 
     def __call__(self, waveform):
@@ -1338,8 +1377,9 @@ def NewKaldiFeatures(*args, **kw):
 _KALDIS = {}  # (device, every field of the configuration) -> KaldiFeatures: a plan is built once per process
 
 
-def _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, **kw):
+def _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, transform, **kw):
     _float32_input(waveform)
+    which = _fbank_transform(transform)
     # torchaudio's _get_waveform_and_window_properties: milliseconds -> samples
     W, h = int(sample_frequency * frame_length * 0.001), int(sample_frequency * frame_shift * 0.001)
     c = _fbank_config(sample_frequency, W, h, kw["num_mel_bins"], kw["num_ceps"], kw["round_to_power_of_two"], kw["snip_edges"],
@@ -1348,8 +1388,8 @@ def _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean,
                       kw["low_freq"], kw["high_freq"], kw["energy_floor"], kw["scale"], kw["cepstral_lifter"], kw["dither"],
                       kw["vtln_warp"])
     waveform, device = _on_device(waveform, device)
-    key = (device,) + tuple(getattr(c, k) for k, _ in FbankConfig._fields_)
-    out = _cached(_KALDIS, key, lambda: KaldiFeatures(sample_frequency, W, h, device=device, **kw))(waveform)
+    key = (device, which) + tuple(getattr(c, k) for k, _ in FbankConfig._fields_)
+    out = _cached(_KALDIS, key, lambda: KaldiFeatures(sample_frequency, W, h, device=device, transform=transform, **kw))(waveform)
     if subtract_mean:  # over the frames, as torchaudio's _subtract_column_mean: a torch op, as Whisper's post-processing is
         out = out - out.mean(dim=-2 if kw["layout"] == "frames" else -1, keepdim=True)
     return out
@@ -1359,15 +1399,17 @@ def kaldi_fbank(waveform, sample_frequency=16000, blackman_coeff=0.42, dither=0.
                 frame_shift=10.0, high_freq=0.0, htk_compat=False, low_freq=20.0, num_mel_bins=23, preemphasis_coefficient=0.97,
                 raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True, snip_edges=True, subtract_mean=False,
                 use_energy=False, use_log_fbank=True, use_power=True, vtln_warp=1.0, window_type="povey", scale=1.0,
-                layout="frames", device=None):
+                layout="frames", device=None, *, transform="direct"):
     """torchaudio.compliance.kaldi.fbank(waveform, ...) in one pass on the device, with torchaudio's keyword names and defaults
     (frame_length / frame_shift in milliseconds; sample_frequency an integer): a float32 tensor [..., T] (CUDA, CPU or numpy;
     the last two are uploaded) -> [..., F, num_mel_bins (+ 1 with use_energy)] on cuda:`device`, or [..., cols, F] with
     layout="bins". scale multiplies the waveform (32768 for recipes made for 16-bit sample values) at no cost. ValueError for
     dither != 0, vtln_warp != 1, use_power=False, use_energy without raw_energy, parameters without a plan, another dtype, or
     T below one frame (torchaudio returns frames there without snip_edges; this does not). The tables of a (device, parameter
-    set) are built once and kept."""
-    return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, num_mel_bins=num_mel_bins, num_ceps=0,
+    set) are built once and kept. transform="fft" takes the FFT in place of the direct transform (KaldiFeatures); the two have
+    handles of their own."""
+    return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, transform, num_mel_bins=num_mel_bins,
+                  num_ceps=0,
                   round_to_power_of_two=round_to_power_of_two, snip_edges=snip_edges, remove_dc_offset=remove_dc_offset,
                   window_type=window_type, use_log_fbank=use_log_fbank, use_energy=use_energy, raw_energy=raw_energy,
                   htk_compat=htk_compat, use_power=use_power, layout=layout, preemphasis_coefficient=preemphasis_coefficient,
@@ -1378,13 +1420,14 @@ def kaldi_fbank(waveform, sample_frequency=16000, blackman_coeff=0.42, dither=0.
 def kaldi_mfcc(waveform, sample_frequency=16000, blackman_coeff=0.42, cepstral_lifter=22.0, dither=0.0, energy_floor=1.0,
                frame_length=25.0, frame_shift=10.0, high_freq=0.0, htk_compat=False, low_freq=20.0, num_ceps=13, num_mel_bins=23,
                preemphasis_coefficient=0.97, raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True, snip_edges=True,
-               subtract_mean=False, use_energy=False, vtln_warp=1.0, window_type="povey", scale=1.0, layout="frames", device=None):
+               subtract_mean=False, use_energy=False, vtln_warp=1.0, window_type="povey", scale=1.0, layout="frames", device=None,
+               *, transform="direct"):
     """torchaudio.compliance.kaldi.mfcc(waveform, ...) in one pass on the device: as kaldi_fbank, -> [..., F, num_ceps] (1 <=
     num_ceps <= num_mel_bins). Column 0 is C0, or the log energy with use_energy; htk_compat moves it to the end, and where
     it is C0 (no use_energy) it leaves there as sqrt(2) C0, as in Kaldi and torchaudio."""
     if isinstance(num_ceps, bool) or int(num_ceps) != num_ceps or int(num_ceps) < 1:
         raise ValueError("num_ceps is an integer in [1, num_mel_bins]")
-    return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, num_mel_bins=num_mel_bins,
+    return _kaldi(waveform, sample_frequency, frame_length, frame_shift, subtract_mean, device, transform, num_mel_bins=num_mel_bins,
                   num_ceps=num_ceps, round_to_power_of_two=round_to_power_of_two, snip_edges=snip_edges,
                   remove_dc_offset=remove_dc_offset, window_type=window_type, use_log_fbank=True, use_energy=use_energy,
                   raw_energy=raw_energy, htk_compat=htk_compat, use_power=True, layout=layout,

@@ -284,18 +284,12 @@ inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t batch, uint32_t* 
     return a + pt + (uint64_t)2u * batch * pl.pitch;
 }
 
-/* false: no plan: what alacmel::make_plan refuses, an n_fft that is odd or whose half has a prime factor above 5, or four
- * frames that do not fit the LDS budget */
-inline bool make_plan(const alacmel::Config& c, Plan* out) {
-    if (!size_ok(c.n_fft)) return false;
-    Plan pl;
-    if (!alacmel::make_plan(c, &pl.base, false)) return false;
-    const uint32_t N = pl.base.N, W = pl.base.W, M = pl.M = N / 2u;
+/* The transform of size N alone (size_ok(N)): M, the radices and passes, the twiddle table with `split`, pos and the pitch of
+ * *pl; nothing else of it is touched. false: more passes than kMaxPasses. alac_fbankfft.h's plan calls it as well. */
+inline bool make_passes(uint32_t N, Plan* out) {
+    Plan& pl = *out;
+    const uint32_t M = pl.M = N / 2u;
     const double pi = 3.14159265358979323846;
-
-    pl.w32.assign(N, 0.0f);
-    const uint32_t off = (N - W) / 2u;
-    for (uint32_t j = 0; j < W; j++) pl.w32[off + j] = (float)(W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W));
 
     uint32_t left = M;
     for (uint32_t r : {5u, 3u, 4u, 2u})
@@ -342,6 +336,23 @@ inline bool make_plan(const alacmel::Config& c, Plan* out) {
     }
 
     pl.pitch = (M + ((M - 1u) >> 4)) | 1u;
+    return true;
+}
+
+/* false: no plan: what alacmel::make_plan refuses, an n_fft that is odd or whose half has a prime factor above 5, or four
+ * frames that do not fit the LDS budget */
+inline bool make_plan(const alacmel::Config& c, Plan* out) {
+    if (!size_ok(c.n_fft)) return false;
+    Plan pl;
+    if (!alacmel::make_plan(c, &pl.base, false)) return false;
+    const uint32_t N = pl.base.N, W = pl.base.W;
+    const double pi = 3.14159265358979323846;
+
+    pl.w32.assign(N, 0.0f);
+    const uint32_t off = (N - W) / 2u;
+    for (uint32_t j = 0; j < W; j++) pl.w32[off + j] = (float)(W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W));
+
+    if (!make_passes(N, &pl)) return false;
     uint32_t tf = kMaxTile;
     while (tf > kMinTile && lds_need(pl, tf, tf, nullptr, nullptr) > kLdsFloats) tf /= 2u;
     uint32_t batch = tf;

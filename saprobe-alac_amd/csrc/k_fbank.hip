@@ -10,12 +10,15 @@
  *                    scale live in the table); the powers into an LDS tile, the mel chains and the log out of it; for MFCC the
  *                    DCT and lifter out of the log-mel tile; the results through LDS into 16-byte stores
  * No matrix instruction, no atomic; everything is written with vector stores.
+ * A handle made with ALACGPU_FBANK_TRANSFORM_FFT runs alac_fbankfft_rows (k_fbankfft.hip over alac_fbankfft.h) in its place: it
+ * owns the window, twiddle and position tables and no basis.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "alac_fbank.h"
+#include "alac_fbankfft.h"
 #include "alac_host.h"
 
 using namespace alacfb;
@@ -57,6 +60,11 @@ hipError_t fbank_launch(hipStream_t stream, const Params& p, uint32_t lds_bytes)
 /* ---- host side (alac_host.h) ---------------------------------------------------------------------------------------- */
 struct __attribute__((visibility("hidden"))) alacgpu_fbank : alack::PassHandle { /* hidden: its destructor is no export */
     Plan plan;
+    uint32_t transform = ALACGPU_FBANK_TRANSFORM_DIRECT;
+    alacfbfft::Plan fft; /* transform = fft: the plan in use; `plan` then is its base */
+    float* d_ws = nullptr;
+    float* d_tw = nullptr;
+    uint32_t* d_pos = nullptr;
     float* d_bt = nullptr;
     float* d_fbw = nullptr;
     int32_t* d_first = nullptr;
@@ -99,6 +107,10 @@ Config config_of(const alacgpu_fbank_config* c) {
 extern "C" {
 
 int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu_fbank** out) {
+    return alacgpu_fbank_create_transform(device, config, ALACGPU_FBANK_TRANSFORM_DIRECT, out);
+}
+
+int alacgpu_fbank_create_transform(int device, const alacgpu_fbank_config* config, uint32_t transform, alacgpu_fbank** out) {
     if (!out || !config) {
         if (out) *out = nullptr;
         set_err("null argument");
@@ -110,7 +122,29 @@ int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu
         set_err("out of memory");
         return ALACGPU_E_ARG;
     }
-    if (!make_plan(config_of(config), &r->plan)) {
+    if (transform > ALACGPU_FBANK_TRANSFORM_FFT) {
+        set_err("transform %u is neither ALACGPU_FBANK_TRANSFORM_DIRECT (0) nor ALACGPU_FBANK_TRANSFORM_FFT (1)", transform);
+        delete r;
+        return ALACGPU_E_ARG;
+    }
+    r->transform = transform;
+    const Config cfg = config_of(config);
+    const uint32_t n_fft = alacfbfft::n_fft_of(cfg);
+    if (transform == ALACGPU_FBANK_TRANSFORM_FFT && n_fft && !alacmelfft::size_ok(n_fft)) {
+        set_err("no FFT plan for frame_length %u (DFT size %u): with transform = fft the DFT size (the next power of two >= "
+                "frame_length with round_to_power_of_two, else frame_length) is even, in [2, %u], and its half is 2^a 3^b 5^c (the "
+                "direct transform takes every frame_length in [1, %u])", config->frame_length, n_fft, kMaxFft, kMaxFft);
+        delete r;
+        return ALACGPU_E_ARG;
+    }
+    bool planned;
+    if (transform == ALACGPU_FBANK_TRANSFORM_FFT) {
+        planned = alacfbfft::make_plan(cfg, &r->fft);
+        if (planned) r->plan = r->fft.base;
+    } else {
+        planned = make_plan(cfg, &r->plan);
+    }
+    if (!planned) {
         set_err("no Kaldi feature plan for frame_length %u, frame_shift %u at %u Hz, %u mel bins in [%g, %g] Hz, %u ceps: "
                 "frame_length in [1, %u], frame_shift >= 1, flags 0 or 1, window_type 0..4, layout 0..1, dither 0 (was %g), "
                 "vtln_warp 1 (was %g), use_power 1 (was %u), use_energy only with raw_energy, 1 <= num_mel_bins <= %u, num_ceps <= "
@@ -123,11 +157,16 @@ int alacgpu_fbank_create(int device, const alacgpu_fbank_config* config, alacgpu
         return ALACGPU_E_ARG;
     }
     r->open(device);
-    r->upload(&r->d_bt, r->plan.bt);
+    r->upload(&r->d_bt, r->plan.bt); /* transform = fft: no basis, one element that nothing reads */
     r->upload(&r->d_fbw, r->plan.fbw);
     r->upload(&r->d_first, r->plan.first);
     r->upload(&r->d_dct, r->plan.dct);
     r->upload(&r->d_lifter, r->plan.lifter);
+    if (transform == ALACGPU_FBANK_TRANSFORM_FFT) {
+        r->upload(&r->d_ws, r->fft.ws);
+        r->upload(&r->d_tw, r->fft.fft.tw);
+        r->upload(&r->d_pos, r->fft.fft.pos);
+    }
     if (r->err != hipSuccess) {
         set_err("Kaldi feature handle creation failed: %s", hipGetErrorString(r->err));
         alacgpu_fbank_destroy(r);
@@ -175,11 +214,36 @@ int alacgpu_fbank_plan(const alacgpu_fbank* r, alacgpu_fbank_info* info, float* 
     info->cols = pl.cols;
     info->tile_frames = pl.tile_frames;
     info->lds_bytes = pl.lds_floats * 4u;
-    if (basis_out) memcpy(basis_out, pl.basis.data(), pl.basis.size() * sizeof(float));
+    if (basis_out && !pl.basis.empty()) memcpy(basis_out, pl.basis.data(), pl.basis.size() * sizeof(float));
     if (fb_out) memcpy(fb_out, pl.fbw.data(), pl.fbw.size() * sizeof(float));
     if (first_out) memcpy(first_out, pl.first.data(), pl.first.size() * sizeof(int32_t));
     if (dct_out && !pl.dct.empty()) memcpy(dct_out, pl.dct.data(), pl.dct.size() * sizeof(float));
     if (lifter_out && !pl.lifter.empty()) memcpy(lifter_out, pl.lifter.data(), pl.lifter.size() * sizeof(float));
+    return ALACGPU_E_OK;
+}
+
+int alacgpu_fbank_fft_plan(const alacgpu_fbank* r, alacgpu_fbank_fft_info* info, float* window_out, size_t window_cap,
+                           float* twiddle_out, size_t twiddle_cap) {
+    if (!r || !info) return alack::null_argument();
+    const alacfbfft::Plan& fp = r->fft;
+    if ((window_out && window_cap < fp.ws.size()) || (twiddle_out && twiddle_cap < fp.fft.tw.size())) {
+        set_err("capacity below the plan's %zu window entries / %zu twiddle entries", fp.ws.size(), fp.fft.tw.size());
+        return ALACGPU_E_ARG;
+    }
+    memset(info, 0, sizeof(*info));
+    info->transform = r->transform;
+    info->tile_frames = r->plan.tile_frames;
+    info->lds_bytes = r->plan.lds_floats * 4u;
+    if (r->transform == ALACGPU_FBANK_TRANSFORM_FFT) {
+        info->batch_frames = fp.batch;
+        info->pitch = fp.fft.pitch;
+        info->n_passes = fp.fft.n_pass;
+        for (uint32_t s = 0; s < fp.fft.n_pass; s++) info->radix[s] = fp.fft.radix[s];
+        info->window_entries = (uint32_t)fp.ws.size();
+        info->twiddle_entries = (uint32_t)fp.fft.tw.size();
+        if (window_out) memcpy(window_out, fp.ws.data(), fp.ws.size() * sizeof(float));
+        if (twiddle_out) memcpy(twiddle_out, fp.fft.tw.data(), fp.fft.tw.size() * sizeof(float));
+    }
     return ALACGPU_E_OK;
 }
 
@@ -193,16 +257,21 @@ int alacgpu_fbank_device(alacgpu_fbank* r, const float* d_in, size_t in_row_stri
         }
         return ALACGPU_E_OK;
     }
+    const bool fft = r->transform == ALACGPU_FBANK_TRANSFORM_FFT;
     Params p;
-    if (!make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, r->d_bt, r->d_fbw,
-                     r->d_first, r->d_dct, r->d_lifter, &p)) {
+    alacfbfft::Params q;
+    if (fft ? !alacfbfft::make_params(r->fft, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, r->d_ws,
+                                      r->d_tw, r->d_pos, r->d_fbw, r->d_first, r->d_dct, r->d_lifter, &q)
+            : !make_params(r->plan, d_in, in_row_stride, rows, in_frames, d_out, out_row_stride, out_inner_stride, r->d_bt, r->d_fbw,
+                           r->d_first, r->d_dct, r->d_lifter, &p)) {
         set_err("Kaldi features: a NULL or misaligned buffer, a stride (%zu in, %zu out rows, %zu out %s) below what it spans (%zu "
                 "samples, %llu frames of %u columns), or sizes that overflow", in_row_stride, out_row_stride, out_inner_stride,
                 r->plan.cfg.layout == kLayoutBins ? "bins" : "frames", in_frames,
                 (unsigned long long)alacgpu_fbank_out_frames(r, in_frames), r->plan.cols);
         return ALACGPU_E_ARG;
     }
-    return r->run(sync, [&](hipStream_t s) { return alack::fbank_launch(s, p, r->plan.lds_floats * 4u); });
+    const uint32_t lds_bytes = r->plan.lds_floats * 4u;
+    return r->run(sync, [&](hipStream_t s) { return fft ? alack::fbankfft_launch(s, q, lds_bytes) : alack::fbank_launch(s, p, lds_bytes); });
 }
 
 } /* extern "C" */

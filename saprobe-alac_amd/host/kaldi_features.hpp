@@ -2,12 +2,15 @@
 // has no counterpart: it hands out PCM).
 //
 //   NewKaldiFeatures(config)              -> throws std::invalid_argument where no plan can be built
+//   NewKaldiFeatures(config, device, ALACGPU_FBANK_TRANSFORM_FFT)   the opt-in FFT transform (the default is the direct one)
 //   FbankConfig(sample_rate, W, h, ...)   an alacgpu_fbank_config with Kaldi's defaults (lengths in samples)
 //   MfccConfig(sample_rate, W, h, ...)    the same for MFCC
 //   KaldiFeatures::OutFrames(T)           1 + (T - W) / h with snip_edges, (T + h / 2) / h without; 0 for T < W
 //   KaldiFeatures::FeaturesDevice(...)    float32 rows on the device -> [rows][F][cols] or [rows][cols][F], asynchronous on
 //                                         Stream() unless sync
-//   KaldiFeatures::Plan()                 the numbers and the host copies of the tables the kernel uses
+//   KaldiFeatures::Plan()                 the numbers and the host copies of the tables the kernel uses (an FFT handle has no
+//                                         basis: it is empty)
+//   KaldiFeatures::FftPlan()              the transform's own numbers and tables (alacgpu_fbank_fft_plan)
 // Header-only; link with -lalacgpu. Every pass runs the HIP kernel: there is no CPU path.
 #pragma once
 
@@ -71,11 +74,17 @@ struct KaldiPlan {
     std::vector<float> lifter;  // [num_ceps]
 };
 
+struct KaldiFftPlan {
+    alacgpu_fbank_fft_info info{};
+    std::vector<float> window;  // [n_fft]: float(scale * window[n]), zeros from frame_length on
+    std::vector<float> twiddle; // 8 roots, each pass's twiddles, the split step's n_fft / 2 + 1 pairs
+};
+
 class KaldiFeatures {
 public:
-    explicit KaldiFeatures(const alacgpu_fbank_config& config, int device = 0) {
+    explicit KaldiFeatures(const alacgpu_fbank_config& config, int device = 0, uint32_t transform = ALACGPU_FBANK_TRANSFORM_DIRECT) {
         alacgpu_fbank* h = nullptr;
-        detail::check(alacgpu_fbank_create(device, &config, &h));
+        detail::check(alacgpu_fbank_create_transform(device, &config, transform, &h));
         h_.reset(h);
     }
 
@@ -93,13 +102,24 @@ public:
     KaldiPlan Plan() const {
         KaldiPlan p;
         detail::must(alacgpu_fbank_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0));
-        p.basis.resize((size_t)2 * p.info.n_freqs * p.info.frame_length);
+        alacgpu_fbank_fft_info fft{};
+        detail::must(alacgpu_fbank_fft_plan(h_.get(), &fft, nullptr, 0, nullptr, 0));
+        if (fft.transform == ALACGPU_FBANK_TRANSFORM_DIRECT) p.basis.resize((size_t)2 * p.info.n_freqs * p.info.frame_length);
         p.fb.resize((size_t)p.info.num_mel_bins * p.info.taps);
         p.first.resize(p.info.num_mel_bins);
         p.dct.resize((size_t)p.info.num_ceps * p.info.num_mel_bins);
         p.lifter.resize(p.info.num_ceps);
         detail::must(alacgpu_fbank_plan(h_.get(), &p.info, p.basis.data(), p.basis.size(), p.fb.data(), p.fb.size(), p.first.data(),
                                         p.first.size(), p.dct.data(), p.dct.size(), p.lifter.data(), p.lifter.size()));
+        return p;
+    }
+
+    KaldiFftPlan FftPlan() const {
+        KaldiFftPlan p;
+        detail::must(alacgpu_fbank_fft_plan(h_.get(), &p.info, nullptr, 0, nullptr, 0));
+        p.window.resize(p.info.window_entries);
+        p.twiddle.resize(p.info.twiddle_entries);
+        detail::must(alacgpu_fbank_fft_plan(h_.get(), &p.info, p.window.data(), p.window.size(), p.twiddle.data(), p.twiddle.size()));
         return p;
     }
 
@@ -118,8 +138,9 @@ private:
     detail::Handle<alacgpu_fbank, alacgpu_fbank_destroy> h_;
 };
 
-inline std::unique_ptr<KaldiFeatures> NewKaldiFeatures(const alacgpu_fbank_config& config, int device = 0) {
-    return std::make_unique<KaldiFeatures>(config, device);
+inline std::unique_ptr<KaldiFeatures> NewKaldiFeatures(const alacgpu_fbank_config& config, int device = 0,
+                                                       uint32_t transform = ALACGPU_FBANK_TRANSFORM_DIRECT) {
+    return std::make_unique<KaldiFeatures>(config, device, transform);
 }
 
 }  // namespace alac
