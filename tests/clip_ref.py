@@ -9,15 +9,12 @@ so that no descriptor wraps around: slot i is the frames [i * fl, (i + 1) * fl) 
 begin[j] + t, a sample when that does not overflow, its slot lies below min(limit[j], n) and its frame below the slot's f,
 zero otherwise. Samples are unpacked and converted by tests/wave_ref.py. All comparisons are bit-exact."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import wave_ref as wr
 
-ROOT = wr.ROOT
-SIM_DIR = wr.SIM_DIR
 SENTINEL = wr.SENTINEL
 
 
@@ -67,13 +64,7 @@ def expected_image(ref, elems, base, cs, ps):
 
 
 def build_clip_sim():
-    so = os.path.join(SIM_DIR, "libclip_sim.so")
-    csrc = os.path.join(ROOT, "saprobe-alac_amd", "csrc")
-    srcs = [os.path.join(SIM_DIR, "clip_sim.cpp"), os.path.join(csrc, "alac_clips.h"), os.path.join(csrc, "alac_waveform.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-shared", "-o", so,
-                               srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("clip_sim.cpp", "libclip_sim.so", host_build.SIM)
     vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
     L.clip_sim_run.argtypes = [u32, u32, u32, vp, u64, vp, vp, u64, vp, vp, u64, u32, ctypes.c_int, vp, u64, u64, vp, vp, u64]
     for fn in (L.clip_sim_tile_cols, L.clip_sim_stage_need):

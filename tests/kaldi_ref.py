@@ -11,15 +11,13 @@ table of both suites; and the host build of that header (tests/host_sim/fbank_si
     it leaves as sqrt(2) C0: D's row 0 is sqrt(2 / M) there"""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import mel_ref as mr
 
 ROOT = mr.ROOT
-SIM_DIR = mr.SIM_DIR
 U = mr.U
 EPS = 2.0 ** -23
 WINDOWS = {"hanning": 0, "hamming": 1, "povey": 2, "rectangular": 3, "blackman": 4}
@@ -334,17 +332,8 @@ def lds_rule(cfg):
 
 
 # ---- the host build ------------------------------------------------------------------------------------------------------
-def _csrc(*names):
-    return [os.path.join(ROOT, "saprobe-alac_amd", "csrc", n) for n in names]
-
-
 def build_fbank_sim():
-    so = os.path.join(SIM_DIR, "libfbank_sim.so")
-    srcs = [os.path.join(SIM_DIR, "fbank_sim.cpp")] + _csrc("alac_fbank.h", "alac_mel.h", "alac_waveform.h")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas",
-                               "-shared", "-o", so, srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("fbank_sim.cpp", "libfbank_sim.so", host_build.SIM_FP)
     vp, u64 = ctypes.c_void_p, ctypes.c_uint64
     L.fbank_sim_plan.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64]
     L.fbank_sim_run.argtypes = [vp, vp, vp, u64, u64, u64, vp, u64, u64, ctypes.c_int]
@@ -355,14 +344,7 @@ def build_fbank_sim():
 
 def build_fbank_shim(pkg):
     """tests/host_sim/fbank_shim.cpp over host/kaldi_features.hpp, linked with the library"""
-    so = os.path.join(SIM_DIR, "libfbank_shim.so")
-    srcs = [os.path.join(SIM_DIR, "fbank_shim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "host", "kaldi_features.hpp"),
-            os.path.join(ROOT, "include", "alacgpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        libdir = os.path.dirname(pkg.lib_path())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", "-o", so, srcs[0], "-L" + libdir, "-lalacgpu",
-                               "-Wl,-rpath," + libdir])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("fbank_shim.cpp", "libfbank_shim.so", host_build.SHIM, host_build.library(pkg))
     vp, sz = ctypes.c_void_p, ctypes.c_size_t
     L.fbank_shim_run.restype = ctypes.c_long
     L.fbank_shim_run.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, vp, vp, vp]

@@ -16,17 +16,15 @@ x - mean is the point.
     energy  kaldi_ref.prelog_bounds' (the same function computes it, so the same ceiling holds)"""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import kaldi_ref as kr
 from tests import mel_ref as mr
 from tests import melfft_ref as fr
 
 ROOT = kr.ROOT
-SIM_DIR = kr.SIM_DIR
 U = kr.U
 Cfg = kr.Cfg
 THREADS = 256
@@ -126,16 +124,8 @@ def share(cfg, plan, x, got, what=""):
 
 
 # ---- the host build -----------------------------------------------------------------------------------------------------
-SIM_FLAGS = ["-O2", "-ffp-contract=off", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"]
-SIM_SRCS = [os.path.join(SIM_DIR, "fbankfft_sim.cpp")] + kr._csrc("alac_fbankfft.h", "alac_fbank.h", "alac_melfft.h", "alac_mel.h",
-                                                                   "alac_waveform.h")
-
-
 def build_fbankfft_sim():
-    so = os.path.join(SIM_DIR, "libfbankfft_sim.so")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SIM_SRCS):
-        subprocess.check_call(["g++"] + SIM_FLAGS + ["-shared", "-o", so, SIM_SRCS[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("fbankfft_sim.cpp", "libfbankfft_sim.so", host_build.SIM_FP)
     vp, u64 = ctypes.c_void_p, ctypes.c_uint64
     L.fbankfft_sim_plan.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64]
     L.fbankfft_sim_run.argtypes = [vp, vp, vp, u64, u64, u64, vp, u64, u64, ctypes.c_int]
@@ -144,14 +134,7 @@ def build_fbankfft_sim():
 
 def build_fbankfft_shim(pkg):
     """tests/host_sim/fbankfft_shim.cpp over host/kaldi_features.hpp, linked with the library"""
-    so = os.path.join(SIM_DIR, "libfbankfft_shim.so")
-    srcs = [os.path.join(SIM_DIR, "fbankfft_shim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "host", "kaldi_features.hpp"),
-            os.path.join(ROOT, "include", "alacgpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        libdir = os.path.dirname(pkg.lib_path())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", "-o", so, srcs[0], "-L" + libdir, "-lalacgpu",
-                               "-Wl,-rpath," + libdir])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("fbankfft_shim.cpp", "libfbankfft_shim.so", host_build.SHIM, host_build.library(pkg))
     vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
     L.fbankfft_shim_run.restype = ctypes.c_long
     L.fbankfft_shim_run.argtypes = [vp, u32, vp, sz, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]

@@ -9,13 +9,12 @@ that header for the tests.
     log: s log(max(v, floor)), s = 10 for db"""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
+from tests import host_build
+
+ROOT = host_build.ROOT
 
 SCALES = {None: 0, "htk": 1, "slaney": 2}
 LOGS = {None: 0, "ln": 1, "log10": 2, "db": 3}
@@ -226,13 +225,7 @@ def whisper_post(logmel):
 
 # ---- the host build ---------------------------------------------------------------------------------------------------
 def build_mel_sim():
-    so = os.path.join(SIM_DIR, "libmel_sim.so")
-    csrc = os.path.join(ROOT, "saprobe-alac_amd", "csrc")
-    srcs = [os.path.join(SIM_DIR, "mel_sim.cpp"), os.path.join(csrc, "alac_mel.h"), os.path.join(csrc, "alac_waveform.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas",
-                               "-shared", "-o", so, srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("mel_sim.cpp", "libmel_sim.so", host_build.SIM_FP)
     vp, u64 = ctypes.c_void_p, ctypes.c_uint64
     L.mel_sim_plan.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64]
     L.mel_sim_run.argtypes = [vp, vp, vp, u64, u64, u64, vp, u64, u64, ctypes.c_int]
@@ -243,14 +236,7 @@ def build_mel_sim():
 
 def build_mel_shim(pkg):
     """tests/host_sim/mel_shim.cpp over host/mel_spectrogram.hpp, linked with the library"""
-    so = os.path.join(SIM_DIR, "libmel_shim.so")
-    srcs = [os.path.join(SIM_DIR, "mel_shim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "host", "mel_spectrogram.hpp"),
-            os.path.join(ROOT, "include", "alacgpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        libdir = os.path.dirname(pkg.lib_path())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", "-o", so, srcs[0], "-L" + libdir, "-lalacgpu",
-                               "-Wl,-rpath," + libdir])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("mel_shim.cpp", "libmel_shim.so", host_build.SHIM, host_build.library(pkg))
     vp, u32, sz, dbl, i = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_double, ctypes.c_int
     L.mel_shim_run.restype = ctypes.c_long
     L.mel_shim_run.argtypes = [u32, u32, u32, u32, dbl, dbl, u32, i, i, i, i, dbl, vp, sz, sz, sz, vp, sz, sz, vp, vp, vp, sz, vp, sz,

@@ -12,17 +12,14 @@ with weights of modulus at most 1 each and adds its own roundings (4 u (|A| + |B
     |dX[k]| <= e = eta sqrt(N) ||v||_2
     dp = (2 |X| e + e^2)(1 + 2 u) + 2 u p;   dmel = sum fb dp + taps u sum fb (p + dp)"""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import mel_ref
 from tests.mel_ref import Cfg, U
 
 ROOT = mel_ref.ROOT
-SIM_DIR = mel_ref.SIM_DIR
-CSRC = os.path.join(ROOT, "saprobe-alac_amd", "csrc")
 
 G = {2: 5.0, 3: 10.0, 4: 6.0, 5: 15.0}
 SPLIT_SHARE, WINDOW_SHARE = 4.0, 1.0
@@ -95,16 +92,8 @@ def share(cfg, plan, x, got, what=""):
 
 
 # ---- the host build ---------------------------------------------------------------------------------------------------
-SIM_FLAGS = ["-O2", "-ffp-contract=off", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"]
-SIM_SRCS = [os.path.join(SIM_DIR, "melfft_sim.cpp"), os.path.join(CSRC, "alac_melfft.h"), os.path.join(CSRC, "alac_mel.h"),
-            os.path.join(CSRC, "alac_waveform.h")]
-
-
 def build_melfft_sim():
-    so = os.path.join(SIM_DIR, "libmelfft_sim.so")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SIM_SRCS):
-        subprocess.check_call(["g++"] + SIM_FLAGS + ["-shared", "-o", so, SIM_SRCS[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("melfft_sim.cpp", "libmelfft_sim.so", host_build.SIM_FP)
     vp, u64 = ctypes.c_void_p, ctypes.c_uint64
     L.melfft_sim_plan.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64]
     L.melfft_sim_run.argtypes = [vp, vp, vp, u64, u64, u64, vp, u64, u64, ctypes.c_int]
@@ -113,14 +102,7 @@ def build_melfft_sim():
 
 def build_melfft_shim(pkg):
     """tests/host_sim/melfft_shim.cpp over host/mel_spectrogram.hpp, linked with the library"""
-    so = os.path.join(SIM_DIR, "libmelfft_shim.so")
-    srcs = [os.path.join(SIM_DIR, "melfft_shim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "host", "mel_spectrogram.hpp"),
-            os.path.join(ROOT, "include", "alacgpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        libdir = os.path.dirname(pkg.lib_path())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-fPIC", "-shared", "-o", so, srcs[0], "-L" + libdir, "-lalacgpu",
-                               "-Wl,-rpath," + libdir])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("melfft_shim.cpp", "libmelfft_shim.so", host_build.SHIM, host_build.library(pkg))
     vp, u32, sz, i = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int
     L.melfft_shim_run.restype = ctypes.c_long
     L.melfft_shim_run.argtypes = [u32, u32, u32, u32, u32, i, u32, vp, sz, sz, sz, vp, sz, sz, vp, vp, sz, vp, sz]

@@ -6,13 +6,10 @@ that header for the tests.
     out_frames(T) = ceil(new * T / orig);  y[j * n + i] = sum_k H[i][k] x[j * o + k - width], x zero outside [0, T)"""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
+from tests import host_build
 
 # every pair the plan must accept
 PAIRS = [(44100, 16000), (16000, 44100), (44100, 48000), (48000, 44100), (48000, 16000), (8000, 48000), (96000, 44100),
@@ -161,13 +158,7 @@ def impulse_expected(h32, first, offsets, T, orig, new, W=6, rolloff=0.99, ampli
 
 # ---- the host build ---------------------------------------------------------------------------------------------------
 def build_resample_sim():
-    so = os.path.join(SIM_DIR, "libresample_sim.so")
-    csrc = os.path.join(ROOT, "saprobe-alac_amd", "csrc")
-    srcs = [os.path.join(SIM_DIR, "resample_sim.cpp"), os.path.join(csrc, "alac_resample.h"), os.path.join(csrc, "alac_waveform.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-shared", "-o", so,
-                               srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("resample_sim.cpp", "libresample_sim.so", host_build.SIM)
     vp, u32, u64, dbl = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
     L.resample_sim_plan.argtypes = [u32, u32, u32, dbl, vp, vp, u64, vp, u64]
     L.resample_sim_run.argtypes = [u32, u32, u32, dbl, vp, u64, u64, u64, vp, u64, ctypes.c_int]

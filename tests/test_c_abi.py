@@ -13,6 +13,8 @@ import subprocess
 
 import pytest
 
+from tests import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "alacgpu.h")
 
@@ -21,10 +23,9 @@ HDR = os.path.join(ROOT, "include", "alacgpu.h")
 def smoke_bin(pkg, tmp_path_factory):
     pkg.build()
     out = str(tmp_path_factory.mktemp("c_abi") / "smoke")
-    lib_dir = os.path.dirname(pkg.lib_path())
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-o", out, os.path.join(ROOT, "tests", "c_abi", "smoke.c"), "-L", lib_dir, "-lalacgpu",
-                           "-Wl,-rpath," + lib_dir])
+    host_build.compile(os.path.join(ROOT, "tests", "c_abi", "smoke.c"), out,
+                       ["-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include")],
+                       host_build.library(pkg), cc="gcc")
     return out
 
 

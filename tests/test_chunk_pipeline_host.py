@@ -7,27 +7,22 @@ sides of one to four chunks for every order class, and coefficients driven throu
 countdown's wave-wide maximum is the identity here; what it does with lanes near and far from the limits side by side is
 checked on the GPU only."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import chunk_pipeline_cases as cases
+from tests import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+def build_chunk_sim():
+    return host_build.shared("chunk_sim.cpp", "libchunk_sim.so", host_build.SIM)
 
 
 @pytest.fixture(scope="module")
 def chunk_sim(oracle):
     """Host build with the countdown (tests/host_sim/chunk_sim.cpp), called like conftest's lane_sim."""
-    d = os.path.join(ROOT, "tests", "host_sim")
-    so = os.path.join(d, "libchunk_sim.so")
-    srcs = [os.path.join(d, f) for f in ("chunk_sim.cpp", "lane_sim.cpp")] + [
-        os.path.join(ROOT, "saprobe-alac_amd", "csrc", h) for h in ("alac_wave.h", "alac_regular.h", "alac_split.h", "alac_duo.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fwrapv", "-fPIC", "-std=c++17", "-Wno-unknown-pragmas", "-shared", "-o", so, srcs[0]])
-    L = ctypes.CDLL(so)
+    L = build_chunk_sim()
     vp = ctypes.c_void_p
     L.lane_sim_decode_batch.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp,
                                         ctypes.c_int, ctypes.c_int, vp, ctypes.c_int]

@@ -188,26 +188,18 @@ def test_streaming_decoder_errors(pkg, stream, synth, oracle, tmp_path):
 
 # ---- the C++ host mirrors (saprobe-alac_amd/host/mp4_demux.hpp, stream_decoder.hpp) through a ctypes shim ---------
 import ctypes
-import os
-import subprocess
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
+
 _SENTINELS = ["ErrNoALACTrack", "ErrInvalidEntry", "ErrInvalidBoxSize", "ErrNoChunkOffset", "ErrInvalidCo64",
               "ErrNoStsc", "ErrInvalidStsc", "ErrNoStsz", "ErrInvalidStsz"]  # enum order of mp4_demux.hpp
 
 
 def _build_shim(with_decoder, pkg=None):
-    d = os.path.join(_ROOT, "tests", "host_sim")
-    so = os.path.join(d, "libhost_shim_gpu.so" if with_decoder else "libhost_shim_cpu.so")
-    host = os.path.join(_ROOT, "saprobe-alac_amd", "host")
-    srcs = [os.path.join(d, "host_shim.cpp")] + [os.path.join(host, h) for h in os.listdir(host)]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-pthread", "-shared", "-o", so, srcs[0]]
-        if with_decoder:
-            libdir = os.path.dirname(pkg.lib_path())
-            cmd += ["-DSHIM_WITH_DECODER", "-L" + libdir, "-lalacgpu", "-Wl,-rpath," + libdir]
-        subprocess.check_call(cmd)
-    return ctypes.CDLL(so)
+    flags = host_build.SHIM + ["-pthread"]
+    if with_decoder:
+        return host_build.shared("host_shim.cpp", "libhost_shim_gpu.so", flags + ["-DSHIM_WITH_DECODER"], host_build.library(pkg))
+    return host_build.shared("host_shim.cpp", "libhost_shim_cpu.so", flags)
 
 
 def _cpp_demux(L, data):

@@ -7,26 +7,18 @@ gfx950 kernels of k_enc.hip run.
 * the compression bar: no larger than synth's WARM order 8 / mixRes 2 packets of the same PCM;
 * the cookie parses back to the encoder's config."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
+from tests import host_build
+
 BPS = {16: 2, 20: 3, 24: 3, 32: 4}
 SHIFT = {16: 0, 20: 0, 24: 1, 32: 2}
 
 
 def build_enc_sim():
-    so = os.path.join(SIM_DIR, "libenc_sim.so")
-    srcs = [os.path.join(SIM_DIR, "enc_sim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "csrc", "alac_enc.h"),
-            os.path.join(ROOT, "include", "alacgpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fwrapv", "-fPIC", "-std=c++17", "-Wno-unknown-pragmas", "-pthread", "-shared",
-                               "-o", so, srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("enc_sim.cpp", "libenc_sim.so", host_build.SIM + ["-pthread"])
     vp, u64 = ctypes.c_void_p, ctypes.c_uint64
     L.enc_sim_max_bytes.restype = u64
     L.enc_sim_max_bytes.argtypes = [vp, u64]

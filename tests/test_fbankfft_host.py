@@ -19,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import host_build
 from tests import kaldi_ref as kr
 from tests import kaldifft_ref as kf
 from tests import melfft_ref as fr
@@ -253,8 +254,8 @@ def test_standalone_program_builds_and_runs(tmp_path):
     parameter sets (W odd below N; asr; full with one frame in the transform buffer), the input ending at the buffer's last
     element and at an inaccessible page, the LDS image exactly the plan's size."""
     exe = str(tmp_path / "fbankfft_san")
-    subprocess.check_call(["g++", "-O1", "-ffp-contract=off", "-fwrapv", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-o", exe,
-                           os.path.join(kf.SIM_DIR, "fbankfft_san_main.cpp")])
+    host_build.compile("fbankfft_san_main.cpp", exe,
+                       ["-O1", "-ffp-contract=off", "-fwrapv", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     print(r.stdout)
     assert r.returncode == 0, r.stdout

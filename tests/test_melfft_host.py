@@ -17,6 +17,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import host_build
 from tests import mel_ref as mr
 from tests import melfft_ref as fr
 
@@ -184,8 +185,8 @@ def test_standalone_program_builds_and_runs(tmp_path):
     under the sanitizers on a CPU: here it is built plainly and run once, so that it stays in step with the header. Three parameter
     sets, the input ending at the buffer's last element and at an inaccessible page, the LDS image exactly the plan's size."""
     exe = str(tmp_path / "melfft_san")
-    subprocess.check_call(["g++", "-O1", "-ffp-contract=off", "-fwrapv", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-o", exe,
-                           os.path.join(fr.SIM_DIR, "melfft_san_main.cpp")])
+    host_build.compile("melfft_san_main.cpp", exe,
+                       ["-O1", "-ffp-contract=off", "-fwrapv", "-std=c++17", "-Wall", "-Wno-unknown-pragmas"])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     print(r.stdout)
     assert r.returncode == 0, r.stdout

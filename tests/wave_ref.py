@@ -7,13 +7,11 @@ The restatement imports nothing of the code under test. It starts from decoded s
     cast rounding to nearest even; INT = the int32; STREAM placed by np.cumsum, PACKETS zero-padded.
 All comparisons are bit-exact: floats are compared as their uint32 views."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
+from tests import host_build
+
 BPS = {16: 2, 20: 3, 24: 3, 32: 4}
 WIDTH = {16: 16, 20: 24, 24: 24, 32: 32}
 STREAM, PACKETS = 0, 1
@@ -147,12 +145,7 @@ def frame_counts(rng, n, fl, pattern):
 
 # ---- the host build --------------------------------------------------------------------------------------------------
 def build_wave_sim():
-    so = os.path.join(SIM_DIR, "libwave_sim.so")
-    srcs = [os.path.join(SIM_DIR, "wave_sim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "csrc", "alac_waveform.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-shared", "-o", so,
-                               srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("wave_sim.cpp", "libwave_sim.so", host_build.SIM)
     vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
     L.wave_sim_run.argtypes = [u32, u32, u32, vp, u64, vp, vp, u64, ctypes.c_int, ctypes.c_int, vp, u64, u64, vp]
     L.wave_sim_tile_frames.restype = u32

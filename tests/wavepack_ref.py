@@ -9,14 +9,12 @@ The restatement imports nothing of the code under test. With q = the depth:
     bytes   wave_ref.pack_samples of the [frames, channels] integers
 All comparisons are on bytes."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import wave_ref as wr
 
-ROOT = wr.ROOT
 STREAM, PACKETS, FLOAT, INT = wr.STREAM, wr.PACKETS, wr.FLOAT, wr.INT
 PCM_SENTINEL = 0x5A
 WAVE_SENTINEL = 0x7FC00BAD  # a NaN as float32, beyond every container but the 32-bit one as int32: read by mistake, it counts
@@ -106,12 +104,7 @@ def random_wave(rng, ch, total, depth, wtype, loud=0.02):
 
 # ---- the host build --------------------------------------------------------------------------------------------------
 def build_pack_sim():
-    so = os.path.join(wr.SIM_DIR, "libpack_sim.so")
-    srcs = [os.path.join(wr.SIM_DIR, "pack_sim.cpp"), os.path.join(ROOT, "saprobe-alac_amd", "csrc", "alac_wavepack.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fwrapv", "-fPIC", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-shared", "-o", so,
-                               srcs[0]])
-    L = ctypes.CDLL(so)
+    L = host_build.shared("pack_sim.cpp", "libpack_sim.so", host_build.SIM)
     vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
     L.pack_sim_run.argtypes = [u32, u32, u32, vp, ctypes.c_int, ctypes.c_int, u64, u64, u64, vp, vp, u64, vp]
     L.pack_sim_tile_frames.restype = u32
