@@ -693,6 +693,74 @@ typedef struct alacgpu_fbank_fft_info {
 int alacgpu_fbank_fft_plan(const alacgpu_fbank* fb, alacgpu_fbank_fft_info* info, float* window_out, size_t window_cap,
                            float* twiddle_out, size_t twiddle_cap);
 
+/*
+ * FEATURE NORMALISATION: float32 features [rows][frames][bins] with per-row lengths -> CMVN, max-clamp, affine and masked
+ * padding, one pass on a handle of its own (k_featnorm.hip, alac_featnorm.h; the feature kernels and every other
+ * are untouched). Element (r, f, b) is at d + r * row_stride + f * frame_stride + b * bin_stride (elements); one of the two
+ * inner strides is 1: bin stride 1 is the Kaldi pass's layout frames [rows][F][D], frame stride 1 its layout bins and the
+ * spectrogram pass's [rows][bins][F], and views of them (logmel[..., :-1]). n_r = clamp(d_lengths[r], 0, frames), frames where
+ * d_lengths is NULL. Per row, in this order:
+ *     stat      over the valid frames f < n_r only:
+ *               NONE      s = x
+ *               MEAN      per bin m = S / (float)n_r, s = x - m
+ *               MEAN_VAR  per bin d = x - m, v = Q / (float)n_r (Q the sum of d * d), rstd = 1.0f / sqrtf(v < var_floor ?
+ *                         var_floor : v), s = d * rstd: Kaldi's apply-cmvn --norm-vars with a floor, two passes over the
+ *                         deviations, never E[x^2] - m^2
+ *               MAX       M = the largest x of all bins and valid frames that is no NaN, c = M - range, s = x < c ? c : x
+ *     affine    y = s, y = y - shift[b] where a shift was given at create, y = y * scale[b] where a scale was: global CMVN
+ *               (x - mean) * istd, or Whisper's (x + 4) / 4 as shift -4, scale 0.25; without them no arithmetic
+ *     padding   y = pad_value for f >= n_r; the input there is never used, whatever it holds
+ * The sums S and Q are fixed: chunks of tile_frames consecutive frames (alacgpu_norm_plan; a function of bins alone), each a
+ * float32 chain in frame order from +0.0f, the chunks' sums added in chunk order from +0.0f; no operation is contracted and no
+ * atomic is used. The bits depend on n_r and tile_frames only: not on rows, nor on which axis is contiguous. sqrtf is the
+ * compiler's (correctly rounded under hipcc's default, 1 ulp as a bare v_sqrt_f32); every other operation is correctly rounded.
+ * alacgpu_norm_create copies shift and scale (bins floats each, either may be NULL) and is ALACGPU_E_ARG, before any HIP call,
+ * for a NULL config, bins outside [1, 4096], an unknown stat, var_floor that is not > 0 (in every mode), or stat MAX with a range
+ * that is negative or NaN. The handle owns a stream, an event pair, the two tables and a grow-only scratch block on the device
+ * (the chunks' partial results; a second pass of a shape allocates nothing); it is single-caller, like a decoder.
+ */
+enum { ALACGPU_NORM_STAT_NONE = 0, ALACGPU_NORM_STAT_MEAN = 1, ALACGPU_NORM_STAT_MEAN_VAR = 2, ALACGPU_NORM_STAT_MAX = 3 };
+typedef struct alacgpu_norm_config {
+    uint32_t bins;   /* 1 .. 4096 */
+    uint32_t stat;   /* ALACGPU_NORM_STAT_* */
+    float var_floor; /* > 0 */
+    float range;     /* >= 0; read with ALACGPU_NORM_STAT_MAX only */
+    float pad_value;
+} alacgpu_norm_config;
+typedef struct alacgpu_norm alacgpu_norm;
+int alacgpu_norm_create(int device, const alacgpu_norm_config* config, const float* shift, const float* scale, alacgpu_norm** out);
+void alacgpu_norm_destroy(alacgpu_norm* nm);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernels (valid after a sync). */
+void* alacgpu_norm_stream(alacgpu_norm* nm);
+int alacgpu_norm_synchronize(alacgpu_norm* nm);
+int alacgpu_norm_last_ms(alacgpu_norm* nm, float* ms);
+/* in_frames itself: the pass keeps every frame. 0 for a NULL handle. */
+uint64_t alacgpu_norm_out_frames(const alacgpu_norm* nm, uint64_t in_frames);
+/*
+ * rows x frames x bins elements of d_in -> the same elements of d_out, which has strides of its own and may be d_in with the
+ * same strides (in place; any other overlap is undefined). Every element (r, f < frames, b < bins) of the output is written
+ * exactly once and nothing else is touched; a row with n_r = 0 is all pad_value. d_lengths: int32 [rows] on the device, or
+ * NULL. d_stats: NULL, or [rows][2][bins] floats on the device: mean and rstd for MEAN_VAR, mean and 1.0 for MEAN, M in [r][0][0]
+ * for MAX; +0.0 everywhere else and in every row with n_r = 0. rows = 0 or frames = 0 succeeds and touches nothing.
+ * ALACGPU_E_ARG before any HIP call: a NULL handle; with work to do a NULL d_in or d_out, a base that is not 4-byte aligned,
+ * neither inner stride equal to 1, an inner stride below the other axis' extent (the stride of an axis of one element is free),
+ * a row stride below the row's extent, or sizes whose products overflow. Asynchronous on the handle's stream unless sync != 0:
+ * the input must be complete, or ordered on that stream, before the call.
+ */
+int alacgpu_norm_device(alacgpu_norm* nm, const float* d_in, size_t in_row_stride, size_t in_frame_stride, size_t in_bin_stride,
+                        size_t rows, size_t frames, const int32_t* d_lengths, float* d_out, size_t out_row_stride,
+                        size_t out_frame_stride, size_t out_bin_stride, float* d_stats, int sync);
+/* The plan the handle's kernels use: its numbers, the scratch block as it stands (address and bytes: they change only when a
+ * pass needs more), and (where the pointers are not NULL and the capacities, counted in entries, suffice) the host copies of
+ * shift and scale; shift_entries / scale_entries are bins, or 0 where none was given. */
+typedef struct alacgpu_norm_info {
+    uint32_t bins, stat, tile_frames, lds_bytes, shift_entries, scale_entries;
+    uint64_t scratch_bytes, scratch_address;
+} alacgpu_norm_info;
+int alacgpu_norm_plan(const alacgpu_norm* nm, alacgpu_norm_info* info, float* shift_out, size_t shift_cap, float* scale_out,
+                      size_t scale_cap);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

@@ -35,6 +35,7 @@ __all__ = [
     "load_clips", "Resampler", "NewResampler", "resample",
     "MelSpectrogram", "NewMelSpectrogram", "mel_spectrogram", "spectrogram", "whisper_log_mel",
     "KaldiFeatures", "NewKaldiFeatures", "kaldi_fbank", "kaldi_mfcc",
+    "NormConfig", "FeatureNorm", "NewFeatureNorm", "normalize_features", "kaldi_frame_counts", "load_features",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -299,6 +300,18 @@ _EXPORTS = {
                                           ctypes.c_void_p, ctypes.c_size_t]),
     "alacgpu_fbank_fft_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                               ctypes.c_size_t]),
+    "alacgpu_norm_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_norm_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_norm_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_norm_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_norm_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_norm_out_frames": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "alacgpu_norm_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                           ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_norm_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                         ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -1434,6 +1447,251 @@ def kaldi_mfcc(waveform, sample_frequency=16000, blackman_coeff=0.42, cepstral_l
                   preemphasis_coefficient=preemphasis_coefficient, blackman_coeff=blackman_coeff, low_freq=low_freq,
                   high_freq=high_freq, energy_floor=energy_floor, scale=scale, cepstral_lifter=cepstral_lifter, dither=dither,
                   vtln_warp=vtln_warp)
+
+
+# ---- FeatureNorm (new: CMVN, max-clamp, affine and masked padding behind the feature passes, per-row lengths) -----------
+class NormConfig(ctypes.Structure):
+    """alacgpu_norm_config (include/alacgpu.h)."""
+
+    _fields_ = [("bins", ctypes.c_uint32), ("stat", ctypes.c_uint32), ("var_floor", ctypes.c_float), ("range", ctypes.c_float),
+                ("pad_value", ctypes.c_float)]
+
+
+class NormInfo(ctypes.Structure):
+    """alacgpu_norm_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("bins", "stat", "tile_frames", "lds_bytes", "shift_entries", "scale_entries")] + [
+        ("scratch_bytes", ctypes.c_uint64), ("scratch_address", ctypes.c_uint64)]
+
+
+_NORM_STATS = {None: 0, "none": 0, "mean": 1, "mean_var": 2, "max": 3}
+
+
+def _norm_table(v, bins, name):
+    """shift / scale: None, a number (every bin's) or bins numbers -> None or a float32 array [bins]"""
+    if v is None:
+        return None
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v, dtype=np.float32)
+    if a.ndim == 0:
+        a = np.full(bins, a, np.float32)
+    if a.shape != (bins,):
+        raise ValueError("%s is a number or %d numbers" % (name, bins))
+    return np.ascontiguousarray(a)
+
+
+class FeatureNorm(_RowPass):
+    """float32 features with per-row lengths -> normalised features with the padding masked, on one MI355X (include/alacgpu.h:
+    alacgpu_norm_*). Per row over its first n = clamp(lengths, 0, frames) frames: stat "mean" subtracts each bin's mean,
+    "mean_var" also multiplies by 1 / sqrt(max(variance, var_floor)) (Kaldi's apply-cmvn --norm-vars), "max" clamps below (the
+    row's maximum over bins and frames) - range, "none" / None does nothing; then (x - shift) * scale where given (a number or
+    bins numbers each: global CMVN, or Whisper's shift -4, scale 0.25); then pad_value in every frame from n on, whatever the
+    input holds there. The sums run in a fixed order, so the result is the same bits for every batch size and for
+    both layouts. ValueError, before any HIP call, for bins outside [1, 4096], an unknown stat, var_floor <= 0, or "max" without
+    a range >= 0. Single-caller, bound to one device and one stream. out_frames(F) is F."""
+
+    _CREATE, _DESTROY, _OUT_FRAMES = "alacgpu_norm_create", "alacgpu_norm_destroy", "alacgpu_norm_out_frames"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_norm_last_ms", "alacgpu_norm_synchronize"
+
+    def __init__(self, bins, stat="mean", shift=None, scale=None, var_floor=1e-20, range=None, pad_value=0.0, device=0):
+        super().__init__()
+        if isinstance(bins, bool) or int(bins) != bins or not 0 <= int(bins) <= 0xFFFFFFFF:
+            raise ValueError("bins is an integer in [1, 4096]")
+        if not (stat is None or isinstance(stat, str)) or stat not in _NORM_STATS:
+            raise ValueError("stat is 'none', 'mean', 'mean_var' or 'max', not %r" % (stat,))
+        if _NORM_STATS[stat] == 3 and range is None:
+            raise ValueError("stat 'max' needs a range >= 0")
+        self.bins, self.stat = int(bins), stat or "none"
+        self.config = NormConfig(self.bins, _NORM_STATS[stat], float(var_floor), 0.0 if range is None else float(range), float(pad_value))
+        self.shift, self.scale = _norm_table(shift, self.bins, "shift"), _norm_table(scale, self.bins, "scale")
+        self._create(device, ctypes.byref(self.config), None if self.shift is None else self.shift.ctypes.data,
+                     None if self.scale is None else self.scale.ctypes.data)
+
+    def norm_device(self, d_in, in_strides, rows, frames, d_lengths, d_out, out_strides, d_stats=0, sync=True):
+        """alacgpu_norm_device: raw device pointers (ints; d_lengths and d_stats may be 0), in_strides / out_strides the (row,
+        frame, bin) strides in elements, one of the two inner ones 1. Exactly the rows x frames x bins elements of the output
+        are written; d_out may be d_in with the same strides. Runs on the handle's stream, which does not order against
+        torch's: synchronize the input first."""
+        _check(self._lib.alacgpu_norm_device(self._h, d_in, *[int(s) for s in in_strides], rows, frames, d_lengths or None, d_out,
+                                             *[int(s) for s in out_strides], d_stats or None, 1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_norm_plan -> dict: bins, stat, tile_frames (the frames of a chunk of the sums), lds_bytes, scratch_bytes and
+        scratch_address (the handle's block for the chunks' partial results as it stands: a second pass of a shape changes
+        neither), and shift / scale as float32 [bins], or None."""
+        info = NormInfo()
+        shift, scale = _fetch_plan(self._lib.alacgpu_norm_plan, self._h, info, lambda i: np.zeros(i.shift_entries, np.float32),
+                                   lambda i: np.zeros(i.scale_entries, np.float32))
+        out = {k: int(getattr(info, k)) for k in ("bins", "stat", "tile_frames", "lds_bytes", "scratch_bytes", "scratch_address")}
+        out.update(shift=shift if info.shift_entries else None, scale=scale if info.scale_entries else None)
+        return out
+
+    @staticmethod
+    def _strides(t, layout):
+        """A tensor [rows, F, bins] (layout frames) or [rows, bins, F] (bins) -> its (row, frame, bin) strides, or None where
+        neither inner stride is 1. The stride of an axis of one element is whatever torch keeps there: it is replaced."""
+        rs, a, b = (int(s) for s in t.stride())
+        fs, bs = (a, b) if layout == "frames" else (b, a)
+        frames, bins = (t.shape[1], t.shape[2]) if layout == "frames" else (t.shape[2], t.shape[1])
+        if frames == 1:
+            fs = bins if bs == 1 else 1
+        if bins == 1:
+            bs = frames if fs == 1 else 1
+        extent = (frames - 1) * fs + (bins - 1) * bs + 1
+        if t.shape[0] == 1:
+            rs = extent
+        if (fs != 1 and bs != 1) or rs < extent:
+            return None
+        return rs, fs, bs
+
+    def __call__(self, feats, lengths=None, layout="frames", out=None, return_stats=False):
+        """A float32 tensor [..., F, bins] (layout "frames", the Kaldi pass's default) or [..., bins, F] ("bins": its other
+        layout and the spectrogram pass's) -> the normalised tensor of the same shape on the handle's device. It works on the
+        tensor's own strides, views such as logmel[..., :-1] included, where one inner stride is 1 and the leading dimensions
+        flatten without a copy; anything else is made contiguous first. lengths: None (every frame is valid) or one integer
+        per row of the leading dimensions, the count of its valid FRAMES (kaldi_frame_counts); int32 on the device as
+        load_clips returns them is used in place. out: None for a new contiguous tensor, or a float32 tensor of feats' shape on
+        the device, feats itself for in place. return_stats: also the statistics [..., 2, bins] (alacgpu_norm_device).
+        ValueError for another dtype, a last-but-one / last dimension that is not bins, or lengths of another count."""
+        import torch
+        if layout not in _FBANK_LAYOUTS:
+            raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
+        if not self._h:
+            raise ValueError("the handle is closed")
+        if not isinstance(feats, torch.Tensor) or feats.dtype is not torch.float32 or feats.ndim < 2:
+            raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
+        if int(feats.shape[-1 if layout == "frames" else -2]) != self.bins:
+            raise ValueError("feats has %d bins, the handle %d" % (feats.shape[-1 if layout == "frames" else -2], self.bins))
+        dev = torch.device("cuda", self.device)
+        lead, inner = tuple(feats.shape[:-2]), tuple(feats.shape[-2:])
+        rows = 1
+        for d in lead:
+            rows *= int(d)
+        frames = int(inner[0 if layout == "frames" else 1])
+
+        def rows_of(t):
+            """[..., a, b] -> ([rows, a, b] without a copy, strides), or (None, None)"""
+            try:
+                v = t.view((rows,) + inner) if t.ndim != 3 else t
+            except RuntimeError:
+                return None, None
+            st = self._strides(v, layout) if v.numel() else (1, 1, 1)
+            return (v, st) if st else (None, None)
+
+        same = out is feats
+        if same and feats.device != dev:
+            raise ValueError("in place needs feats on the handle's device")
+        if out is not None and not same:
+            if not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or out.shape != feats.shape or out.device != dev:
+                raise ValueError("out must be a float32 tensor of feats' shape on the handle's device")
+        x = feats.to(dev)
+        xv, xs = rows_of(x)
+        if xv is None:
+            if same:
+                raise ValueError("in place needs a tensor whose rows flatten without a copy and whose frame or bin stride is 1")
+            xv, xs = rows_of(x.contiguous())
+        if same:
+            result, ov, os_ = feats, xv, xs
+        else:
+            result = torch.empty(feats.shape, dtype=torch.float32, device=dev) if out is None else out
+            ov, os_ = rows_of(result)
+            if ov is None:
+                raise ValueError("out needs rows that flatten without a copy and a frame or bin stride of 1")
+        d_len = 0
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor):
+                lengths = torch.as_tensor(np.asarray(lengths))
+            if lengths.numel() != rows or lengths.dtype.is_floating_point:
+                raise ValueError("lengths holds one integer per row: %d, not %d" % (rows, lengths.numel()))
+            info = torch.iinfo(torch.int32)
+            ln = lengths if lengths.dtype is torch.int32 else lengths.clamp(info.min, info.max).to(torch.int32)
+            ln = ln.to(dev).contiguous().reshape(rows)
+            d_len = ln.data_ptr()
+        stats = torch.empty((rows, 2, self.bins), dtype=torch.float32, device=dev) if return_stats else None
+        if rows and frames:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            self.norm_device(xv.data_ptr(), xs, rows, frames, d_len, ov.data_ptr(), os_, stats.data_ptr() if return_stats else 0,
+                             sync=True)
+        elif return_stats:
+            stats.zero_()
+        return (result, stats.reshape(lead + (2, self.bins))) if return_stats else result
+
+
+def NewFeatureNorm(bins, stat="mean", shift=None, scale=None, var_floor=1e-20, range=None, pad_value=0.0, device=0):
+    """A FeatureNorm (context manager); ValueError where no plan can be built."""
+    return FeatureNorm(bins, stat, shift, scale, var_floor, range, pad_value, device)
+
+
+_NORMS = {}  # (device, bins, stat, var_floor, range, pad_value, the bytes of shift and of scale) -> FeatureNorm
+
+
+def normalize_features(feats, lengths=None, stat="mean", layout="frames", shift=None, scale=None, var_floor=1e-20, range=None,
+                       pad_value=0.0, out=None, return_stats=False, device=None):
+    """FeatureNorm(bins, stat, ...)(feats, lengths, layout, out, return_stats) with the handle of a (device, parameter set) made
+    once and kept: feats a float32 tensor [..., F, bins] (layout "frames") or [..., bins, F] ("bins") on cuda:`device` (default:
+    the tensor's own, cuda:0 for a CPU tensor, which is uploaded). shift / scale enter the key by their bytes."""
+    import torch
+    if not isinstance(feats, torch.Tensor) or feats.ndim < 2:
+        raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
+    if layout not in _FBANK_LAYOUTS:
+        raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
+    bins = int(feats.shape[-1 if layout == "frames" else -2])
+    if device is None:
+        device = (feats.device.index or 0) if feats.is_cuda else 0
+    sh, sc = _norm_table(shift, bins, "shift"), _norm_table(scale, bins, "scale")
+    if not (stat is None or isinstance(stat, str)):
+        raise ValueError("stat is 'none', 'mean', 'mean_var' or 'max', not %r" % (stat,))
+    key = (device, bins, stat or "none", float(var_floor), None if range is None else float(range), float(pad_value),
+           None if sh is None else sh.tobytes(), None if sc is None else sc.tobytes())
+    norm = _cached(_NORMS, key, lambda: FeatureNorm(bins, stat, sh, sc, var_floor, range, pad_value, device))
+    return norm(feats, lengths, layout, out, return_stats)
+
+
+def kaldi_frame_counts(lengths, frame_length, frame_shift, snip_edges=True):
+    """Per-row sample counts (a tensor of integers, as load_clips' lengths) -> the int32 tensor of the frames that Kaldi's
+    framing gives a row of that many samples, frame_length / frame_shift in samples: KaldiFeatures.out_frames for every value:
+    1 + (T - W) // h with snip_edges, (T + h // 2) // h without, 0 for T < W. With snip_edges the first out_frames(T) frames of a
+    row that is zero-padded behind its T samples are the frames of the row cut to T, bit for bit: frame f reads the samples
+    [f h, f h + W) only. Without snip_edges that holds for every frame but the last few, which read up to W / 2 - h / 2 samples
+    behind T: they see the padding's zeros where Kaldi would reflect. And a lengths of load_clips is a count, not a prefix, where
+    a short packet lies in front of a file's last: the samples it counts are then not the row's first."""
+    import torch
+    W, h = int(frame_length), int(frame_shift)
+    if W < 1 or h < 1:
+        raise ValueError("frame_length and frame_shift are positive sample counts")
+    if not isinstance(lengths, torch.Tensor):
+        lengths = torch.as_tensor(np.asarray(lengths))
+    if lengths.dtype.is_floating_point:
+        raise ValueError("lengths holds integers")
+    T = lengths.to(torch.int64)
+    n = 1 + torch.div(T - W, h, rounding_mode="floor") if snip_edges else torch.div(T + h // 2, h, rounding_mode="floor")
+    return torch.where(T >= W, n, torch.zeros_like(n)).to(torch.int32)
+
+
+def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="fbank", norm="mean", channel=0, transform="direct",
+                  device=0, **kaldi_kwargs):
+    """Files to normalised features in one call: load_clips(sources, frame_offsets, num_frames, sample_rate=sample_rate) -> the
+    channel `channel` -> kaldi_fbank (kind "fbank") or kaldi_mfcc ("mfcc") with kaldi_kwargs (torchaudio's names; frames layout)
+    -> kaldi_frame_counts of load_clips' lengths -> FeatureNorm(stat=norm: "mean", "mean_var" or None, which only masks).
+    -> (feats [B, F, D], frame_lengths int32 [B], sample_rate): row j's first frame_lengths[j] frames are normalised over
+    themselves, the frames behind them are 0. Nothing but that composition; its two limits are kaldi_frame_counts'."""
+    if kind not in ("fbank", "mfcc"):
+        raise ValueError("kind is 'fbank' or 'mfcc', not %r" % (kind,))
+    if not (norm is None or isinstance(norm, str)) or norm not in (None, "mean", "mean_var"):
+        raise ValueError("norm is 'mean', 'mean_var' or None, not %r" % (norm,))
+    for k in ("layout", "subtract_mean", "sample_frequency", "device"):
+        if k in kaldi_kwargs:
+            raise ValueError("%s is not an argument of load_features" % k)
+    clips, lengths, rate = load_clips(sources, frame_offsets, num_frames, device=device, sample_rate=sample_rate)
+    if not 0 <= int(channel) < clips.shape[1]:
+        raise ValueError("channel %d of %d" % (channel, clips.shape[1]))
+    feats = (kaldi_fbank if kind == "fbank" else kaldi_mfcc)(clips[:, int(channel)], sample_frequency=rate, device=device,
+                                                            transform=transform, **kaldi_kwargs)
+    W = int(rate * kaldi_kwargs.get("frame_length", 25.0) * 0.001)
+    h = int(rate * kaldi_kwargs.get("frame_shift", 10.0) * 0.001)
+    counts = kaldi_frame_counts(lengths, W, h, kaldi_kwargs.get("snip_edges", True))
+    return normalize_features(feats, counts, stat=norm, out=feats, device=device), counts, rate
 
 
 def NewDecoder(source, device=0, window=1024):
