@@ -1,7 +1,7 @@
 /*
  * alac_gpu.h — what the kernel translation units of libalacgpu.so share: the gfx950 forms of the building-block
  * macros of alac_regular.h, the wave policies (GpuWave: LDS stager, bitstream rings, residual queue, DPP reductions;
- * GpuWaveMem: residuals from memory), the launch plan, and the kernels' declarations. The library is built from
+ * GpuWaveMem: residuals from memory), the launch plan (alac_plan.h), the sort's workspace, and the kernels' declarations. The library is built from
  * several translation units (k_sort, k_scan, k_dec16q, k_dec16g, k_dec24q, k_dec32q, k_decw24, k_decw32, k_split, alacgpu)
  * so that the kernels compile in parallel; nothing crosses between them on the device side.
  */
@@ -184,28 +184,17 @@ constexpr uint32_t kRingDw = ALAC_LDS_RING;                 /* bitstream ring, d
  * sits in the entropy chain (alac_regular.h: RingRd). Two spare slots behind the ring: slot kRingDw repeats slot 0. */
 constexpr uint32_t kRingSlots = kRingDw + 2;
 
-/* device-side launch plan, rebuilt by every decode */
-/* sort keys: 0..2047 regular packets (numU*32 + numV + KEY_WIDE, alac_regular.h); 2048 / 2049 irregular packets
- * (below). A workgroup holds packets of ONE key. */
-constexpr uint32_t kKeys = alac::KEY_IRREGULAR + 2u;
-constexpr uint32_t kKeyLegacy = alac::KEY_IRREGULAR;     /* decode_wave */
-constexpr uint32_t kKeyScan = alac::KEY_IRREGULAR + 1u;  /* decode_wave<SCAN> + split pipeline */
-struct Plan {
-    uint32_t count[kKeys];     /* packets per key */
-    uint32_t pkt_start[kKeys]; /* first index in perm[] */
-    uint32_t cursor[kKeys];    /* scatter cursors */
-    /* compact list of the non-empty keys in dispatch order (slowest first) */
-    uint32_t nk;
-    uint32_t list_key[kKeys];
-    uint32_t list_wave0[kKeys]; /* first block id */
-    uint32_t total_waves;
-    uint32_t irr_waves;  /* waves of the irregular keys (>= KEY_IRREGULAR): they come first */
-    uint32_t wide_waves; /* then those of the wide keys (KEY_WIDE..), then the narrow ones */
-    /* the pair kernels (k_decode_body.inc; [0] narrow keys, [1] wide): workgroups admitted per CU so far and the
-     * next item of the queue. Zeroed with the rest of the plan before every decode. */
-    uint32_t gate[2][512];
-    uint32_t balance[2][512]; /* per SIMD of the CU, a byte each: entropy waves - predictor waves placed there */
-    uint32_t queue[2];
+} /* namespace alack */
+#include "alac_plan.h" /* kKeys, Plan and the scan that fills it */
+namespace alack {
+
+/* What the sort pre-pass keeps in the handle's workspace from decode to decode (k_sort.hip): the global histogram of
+ * sort keys that the blocks of a classify kernel add to, and the ticket each block draws when it is done. The block
+ * that draws the last ticket makes the plan from the histogram and puts both back to zero, so they are zero whenever no
+ * classify kernel is running: zeroed once when allocated, and again by the host where a decode may have left them dirty. */
+struct SortWs {
+    uint32_t hist[kKeys];
+    uint32_t ticket;
 };
 
 /* LDS of the decode kernel (one wave per workgroup). Referenced by name, never through a generic pointer, so
@@ -475,12 +464,14 @@ __device__ __forceinline__ uint32_t avail_of(uint64_t blob_bytes, uint64_t off) 
 /* ---- kernels (one decode = these launches on the handle's stream) ---- */
 __global__ void alac_classify(alac::DevCfg cfg, const uint8_t* __restrict__ blob, uint64_t blob_bytes, const uint64_t* __restrict__ offsets,
                               const uint32_t* __restrict__ sizes, uint32_t n, uint16_t* __restrict__ keys, uint32_t* __restrict__ sizes_ws,
-                              uint32_t* __restrict__ frames_out, int32_t* __restrict__ status, Plan* plan);
-__global__ void alac_plan(Plan* plan, uint32_t ppw);
+                              uint32_t* __restrict__ frames_out, int32_t* __restrict__ status, uint32_t* __restrict__ rank, SortWs* ws, Plan* plan,
+                              uint32_t ppw_shift);
 __global__ void alac_cu_census(uint32_t* __restrict__ seen, uint32_t* __restrict__ arrived, uint32_t expect);
-__global__ void alac_scatter(const uint16_t* __restrict__ keys, uint32_t n, Plan* plan, uint32_t* __restrict__ perm);
+__global__ void alac_scatter(const uint16_t* __restrict__ keys, const uint32_t* __restrict__ rank, uint32_t n, const Plan* __restrict__ plan,
+                             uint32_t* __restrict__ perm, uint32_t* __restrict__ claims, uint32_t claim_dw);
 __global__ void alac_task_classify(alac::DevCfg cfg, const alac::ChanDesc* __restrict__ cd, const alac::PktDesc* __restrict__ pd,
-                                   const uint16_t* __restrict__ pkt_keys, uint32_t n_slots, uint16_t* __restrict__ keys, Plan* plan);
+                                   const uint16_t* __restrict__ pkt_keys, uint32_t n_slots, uint16_t* __restrict__ keys, uint32_t* __restrict__ rank,
+                                   SortWs* ws, Plan* plan, uint32_t ppw_shift);
 __global__ void alac_scan(alac::DevCfg cfg, const uint8_t* __restrict__ blob, uint64_t blob_bytes, const uint64_t* __restrict__ offsets,
                           const uint32_t* __restrict__ sizes, const uint32_t* __restrict__ perm, const Plan* __restrict__ plan,
                           uint8_t* __restrict__ out, uint64_t out_stride, uint32_t* __restrict__ frames_out,
@@ -564,7 +555,7 @@ struct PairArgs {
     int32_t* status;
     int32_t* scratch_u;
     const uint32_t* cu_number; /* 1 + the number of each CU (indexed like Plan::gate), 0 for CUs the census did not see */
-    uint32_t* claims; /* kClaimDw (four) words per wave slot of the plan, zeroed before every decode: whoever sets the first decodes the slot */
+    uint32_t* claims; /* kClaimDw (four) words per wave slot of the plan, zeroed by every decode (alac_scatter): whoever sets the first decodes the slot */
     uint32_t ppw;
     uint32_t n_cu; /* compute units of the device */
     uint32_t cap;  /* pairs one of them holds */

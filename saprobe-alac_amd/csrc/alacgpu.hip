@@ -6,9 +6,10 @@
  * path in this library: every decode entry launches the kernels.
  *
  * One decode = these launches on the handle's stream:
- *   alac_classify  one thread per packet: sort key from the first element header (a few bytes read)
- *   alac_plan      one wavefront: key histogram -> packet / wave ranges (irregular keys, then the longest predictors)
- *   alac_scatter   one thread per packet: counting-sort scatter into the lane permutation
+ *   alac_classify  one thread per packet: sort key from the first element header (a few bytes read) and the packet's rank
+ *                  inside its key; the last block to finish turns the key histogram into the plan: packet / wave ranges
+ *                  (irregular keys, then the longest predictors), the pair kernels' gate words zeroed
+ *   alac_scatter   one thread per packet: counting-sort scatter into the lane permutation; zeroes the claim words
  *   alac_scan      irregular packets, one wavefront per 64: status, frame count, where each channel starts; with
  *                  more than two channels also every channel's residuals, into the channel's row
  *   alac_decode_{16,24,32}q   regular packets: entropy, predictor, writer and spare wave per 64 same-key packets
@@ -16,7 +17,7 @@
  *   alac_decode_16g, alac_decode_w{24,32}   the gated twin (16-bit batches between the rounds) and the wide keys: a PAIR
  *                  of wavefronts (entropy; predictor + PCM) per 64 same-key packets (one kernel and compilation unit per
  *                  class: sample width x chanBits)
- *   alac_task_classify / alac_plan / alac_scatter / alac_chan_predict   (> 2 channels) one wavefront per 64
+ *   alac_task_classify / alac_scatter / alac_chan_predict   (> 2 channels) one wavefront per 64
  *                  (packet, channel) tasks of the same order: the predictor over the stored residuals, in place
  *   alac_interleave, alac_legacy   PCM of the scanned packets (frame order), whole-packet decoder for the rest
  * alacgpu_waveform_device is a pass of its own behind a decode (k_wave.hip, alac_waveform.h): PCM slots -> planar waveforms.
@@ -26,6 +27,8 @@
  * ((frame_length + 1) x 64 x int32 per workgroup, row-coalesced, written once and read once) or the sample rows
  * of the split pipeline.
  */
+#include <cassert>
+
 #include "alac_gpu.h"
 #include "alac_host.h"
 #include "alac_waveform.h"
@@ -195,6 +198,8 @@ struct alacgpu_decoder {
     hipEvent_t ev_start[kTimingSlots], ev_stop[kTimingSlots]; /* ring of per-launch event pairs */
     uint64_t launches;                                       /* since the last timing reset */
     DevBuf scratch_u, scratch_g, plan, cls, perm, sizes_ws;  /* kernel workspace */
+    DevBuf rank, sort_ws;                                    /* the sort's ranks (both sorts use them in turn) and its SortWs */
+    bool sort_dirty;                                         /* a decode did not get to its end: sort_ws may not be zero */
     DevBuf cd, pd, plan2, keys2, perm2, rows;                /* split pipeline (more than two channels) */
     Slot slots[kSlots];                                      /* host-entry staging */
     CopyPool* pool;
@@ -299,11 +304,16 @@ size_t max_waves(const alacgpu_decoder* dec, size_t n, uint32_t ppw) { return ma
 uint32_t pick_ppw(size_t n) {
     if (const char* e = getenv("ALACGPU_PPW")) {
         const int v = atoi(e);
-        if (v >= 1 && v <= 64) return (uint32_t)v;
+        if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) return (uint32_t)v; /* powers of two only */
     }
     uint32_t ppw = kWave;
     while (ppw > 1 && n / ppw < 256) ppw >>= 1;
     return ppw;
+}
+/* ... always a power of two: the plan's divisions by it are shifts (alac_plan.h) */
+uint32_t ppw_shift_of(uint32_t ppw) {
+    assert(ppw >= 1u && ppw <= kWave && (ppw & (ppw - 1u)) == 0u);
+    return (uint32_t)__builtin_ctz(ppw);
 }
 
 size_t row_stride_of(uint32_t frame_length) { return ((size_t)frame_length + 3u) & ~(size_t)3u; } /* 16-byte rows */
@@ -313,12 +323,19 @@ int reserve_workspace(alacgpu_decoder* dec, size_t n, uint32_t ppw) {
     int rc;
     if ((rc = dec->scratch_u.ensure(waves * u_tile_cells(dec->cfg.frame_length) * sizeof(int32_t)))) return rc;
     if ((rc = dec->scratch_g.ensure(waves * kFallbackSlots * ppw * sizeof(int32_t)))) return rc;
-    /* the plan and, behind it, the claim flags of the pair kernels (one per wave slot): zeroed together */
+    /* the plan and, behind it, the claim flags of the pair kernels (one per wave slot) */
     if ((rc = dec->plan.ensure(plan_bytes(waves)))) return rc;
+    /* the sort's histogram and ticket: zero from here on whenever no classify kernel is running (alac_gpu.h: SortWs) */
+    if (!dec->sort_ws.p) {
+        if ((rc = dec->sort_ws.ensure(sizeof(SortWs)))) return rc;
+        HIP_TRY(hipMemsetAsync(dec->sort_ws.p, 0, sizeof(SortWs), dec->stream));
+        dec->sort_dirty = false;
+    }
     if ((rc = dec->cls.ensure((n ? n : 1) * sizeof(uint16_t)))) return rc;
     if ((rc = dec->perm.ensure((n ? n : 1) * sizeof(uint32_t)))) return rc;
     if ((rc = dec->sizes_ws.ensure((n ? n : 1) * sizeof(uint32_t)))) return rc;
     const size_t ns = (n ? n : 1) * 8;
+    if ((rc = dec->rank.ensure((dec->cfg.num_channels > 2 ? ns : (n ? n : 1)) * sizeof(uint32_t)))) return rc;
     if ((rc = dec->cd.ensure(ns * sizeof(alac::ChanDesc)))) return rc;
     if ((rc = dec->pd.ensure((n ? n : 1) * sizeof(alac::PktDesc)))) return rc;
     if (dec->cfg.num_channels > 2) {
@@ -375,16 +392,21 @@ struct SideFork {
     }
 };
 
-/* the sort: keys, plan, lane permutation. d_sizes may be null (packet i = blob[offsets[i], offsets[i+1])) */
+/* the sort: keys and ranks, plan, lane permutation — two kernels (k_sort.hip). d_sizes may be null (packet i =
+ * blob[offsets[i], offsets[i+1])). The classify kernel counts in the handle's SortWs and leaves it zero again; a decode that
+ * failed after it was launched (sort_dirty, cleared by launch() at its end) may not have: zero it first then. */
 int sort_pass(const Launch& L, const uint32_t* d_sizes) {
     alacgpu_decoder* dec = L.dec;
     const uint32_t nb = (uint32_t)((L.n + 255) / 256);
-    HIP_TRY(hipMemsetAsync(L.plan(), 0, plan_bytes(L.waves), dec->stream));
+    if (dec->sort_dirty) HIP_TRY(hipMemsetAsync(dec->sort_ws.p, 0, sizeof(SortWs), dec->stream));
+    dec->sort_dirty = true;
     hipLaunchKernelGGL(alac_classify, dim3(nb), dim3(256), 0, dec->stream, L.c, L.d_blob, L.blob_bytes, L.d_offsets, d_sizes,
-                       (uint32_t)L.n, (uint16_t*)dec->cls.p, (uint32_t*)dec->sizes_ws.p, L.d_frames, L.d_status, L.plan());
-    hipLaunchKernelGGL(alac_plan, dim3(1), dim3(kWave), 0, dec->stream, L.plan(), L.ppw);
-    hipLaunchKernelGGL(alac_scatter, dim3(nb), dim3(256), 0, dec->stream, (const uint16_t*)dec->cls.p, (uint32_t)L.n, L.plan(),
-                       (uint32_t*)dec->perm.p);
+                       (uint32_t)L.n, (uint16_t*)dec->cls.p, (uint32_t*)dec->sizes_ws.p, L.d_frames, L.d_status, (uint32_t*)dec->rank.p,
+                       (SortWs*)dec->sort_ws.p, L.plan(), ppw_shift_of(L.ppw));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(alac_scatter, dim3(nb), dim3(256), 0, dec->stream, (const uint16_t*)dec->cls.p, (const uint32_t*)dec->rank.p,
+                       (uint32_t)L.n, (const Plan*)L.plan(), (uint32_t*)dec->perm.p, (uint32_t*)((uint8_t*)L.plan() + plan_claims_offset()),
+                       (uint32_t)(L.waves * kClaimDw));
     return ALACGPU_E_OK;
 }
 
@@ -467,13 +489,14 @@ int split_pipeline(const Launch& L) {
     const size_t n_slots = L.n * 8;
     const uint32_t nb2 = (uint32_t)((n_slots + 255) / 256);
     const uint32_t ppw2 = pick_ppw(L.n * dec->cfg.num_channels);
-    HIP_TRY(hipMemsetAsync(plan2, 0, sizeof(Plan), dec->stream));
+    /* the second sort, in the first one's form and through the same SortWs and ranks (the first sort's kernels are done
+     * with both: everything is on the handle's stream); no claim words behind this plan */
     hipLaunchKernelGGL(alac_task_classify, dim3(nb2), dim3(256), 0, dec->stream, L.c, (const alac::ChanDesc*)dec->cd.p,
                        (const alac::PktDesc*)dec->pd.p, (const uint16_t*)dec->cls.p, (uint32_t)n_slots,
-                       (uint16_t*)dec->keys2.p, plan2);
-    hipLaunchKernelGGL(alac_plan, dim3(1), dim3(kWave), 0, dec->stream, plan2, ppw2);
-    hipLaunchKernelGGL(alac_scatter, dim3(nb2), dim3(256), 0, dec->stream, (const uint16_t*)dec->keys2.p,
-                       (uint32_t)n_slots, plan2, (uint32_t*)dec->perm2.p);
+                       (uint16_t*)dec->keys2.p, (uint32_t*)dec->rank.p, (SortWs*)dec->sort_ws.p, plan2, ppw_shift_of(ppw2));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(alac_scatter, dim3(nb2), dim3(256), 0, dec->stream, (const uint16_t*)dec->keys2.p, (const uint32_t*)dec->rank.p,
+                       (uint32_t)n_slots, (const Plan*)plan2, (uint32_t*)dec->perm2.p, (uint32_t*)nullptr, 0u);
     hipLaunchKernelGGL(alac_chan_predict, dim3((uint32_t)max_waves(16u, n_slots, ppw2)), dim3(kWave), 0, dec->stream, L.c,
                        L.d_blob, L.blob_bytes, L.d_offsets, L.sz(), (const uint32_t*)dec->perm2.p, (const Plan*)plan2,
                        (const alac::ChanDesc*)dec->cd.p, (int32_t*)dec->rows.p, (uint64_t)row_stride_of(dec->cfg.frame_length), ppw2);
@@ -564,6 +587,7 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
     if (L.forked && (rc = side.join())) return rc;
     HIP_TRY(hipEventRecord(dec->ev_stop[slot], dec->stream));
     dec->launches++;
+    dec->sort_dirty = false; /* every kernel of the decode is in the stream: the classify kernels will run to their end */
     return ALACGPU_E_OK;
 }
 
@@ -609,7 +633,7 @@ void keep_at_most(std::vector<Buf*> bufs, size_t limit) {
  * trims the buffers of a handle on its way to the pool by them, really_destroy lets go of everything by them. (cu_number is
  * outside the trimming: only really_destroy releases it.) */
 std::vector<DevBuf*> device_buffers(alacgpu_decoder* d) {
-    std::vector<DevBuf*> v = {&d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->cd, &d->pd,
+    std::vector<DevBuf*> v = {&d->scratch_u, &d->scratch_g, &d->plan, &d->cls, &d->perm, &d->sizes_ws, &d->rank, &d->sort_ws, &d->cd, &d->pd,
                               &d->plan2, &d->keys2, &d->perm2, &d->rows, &d->wave_ws};
     for (Slot& s : d->slots) v.insert(v.end(), {&s.d_in, &s.d_out});
     return v;
@@ -761,6 +785,8 @@ void alacgpu_destroy(alacgpu_decoder* d) {
     /* nothing of this handle's last call may still be running when its belongings go to the next owner */
     if (synchronize_all(d)) {
         for (int k = 0; k < kSlots; k++) d->slots[k].busy = false;
+        if (d->sort_dirty) d->sort_ws.release(); /* a handle comes back from the pool clean: allocated again and zeroed by its next decode */
+        d->sort_dirty = false;
         keep_at_most(device_buffers(d), kPoolKeepDevice);
         keep_at_most(pinned_buffers(d), kPoolKeepPinned);
         std::lock_guard<std::mutex> g(g_pool_mu);
