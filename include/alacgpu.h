@@ -761,6 +761,68 @@ typedef struct alacgpu_norm_info {
 int alacgpu_norm_plan(const alacgpu_norm* nm, alacgpu_norm_info* info, float* shift_out, size_t shift_cap, float* scale_out,
                       size_t scale_cap);
 
+/*
+ * FRAME STACKING: float32 features [rows][frames][bins] with per-row lengths -> deltas, context splicing and subsampling with
+ * lengths of their own, one pass on a handle of its own (k_stack.hip, alac_stack.h; the normalisation pass and
+ * every other are untouched). The input is addressed as the normalisation pass's: element (r, f, b) at d + r * row_stride + f *
+ * frame_stride + b * bin_stride (elements), one of the two inner strides 1, the stride of an axis of one element free;
+ * n_r = clamp(d_lengths[r], 0, frames), frames where d_lengths is NULL.
+ *     weights   Kaldi's DeltaFeatures: w_0 = [1], w_k = w_(k-1) convolved with the ramp j = -window .. window, divided by sum j^2;
+ *               half-width M_k = k * window; exact integer numerators over (sum j^2)^k, rounded to float32 once at create
+ *     deltas    d_k[t][b] = the chain acc = fmaf(w_k[i], x[clamp(t + i, 0, n_r - 1)][b], acc), i = -M_k .. M_k in that order from
+ *               +0.0f, taps of weight zero skipped; d_0 = x, copied. Order 1 is torchaudio's compute_deltas(mode "replicate") with
+ *               win_length 2 window + 1; order 2 is Kaldi's add-deltas (one clamp, on x), not compute_deltas applied twice
+ *     output    G = ceil(frames / stride) frames of D = (left + right + 1) * (order + 1) * bins columns; m_r = ceil(n_r / stride);
+ *               y[r][g][(c * (order + 1) + k) * bins + b] = d_k[clamp(g * stride + c - left, 0, n_r - 1)][b] for g < m_r and
+ *               c = 0 .. left + right; pad_value for g >= m_r; d_out_lengths[r] = m_r
+ * add-deltas is left = right = 0, stride 1; splice-feats is order 0; subsample-feats is the stride alone; FunASR's apply_lfr(m,
+ * n) is left (m - 1) / 2, right m - 1 - left, stride n. The input at frames >= n_r is never read, whatever it holds. fmaf is
+ * correctly rounded and nothing else rounds: the bits depend on the row's own data and n_r only.
+ * alacgpu_stack_create is ALACGPU_E_ARG, before any HIP call, for a NULL config, bins outside [1, 4096], order above 2, window
+ * outside [1, 8] with an order above 0, left or right above 16, stride outside [1, 64], or D above 4096. The handle owns a
+ * stream, an event pair and the weights on the device; it is single-caller, like a decoder.
+ */
+typedef struct alacgpu_stack_config {
+    uint32_t bins;   /* 1 .. 4096 */
+    uint32_t order;  /* 0 .. 2 */
+    uint32_t window; /* 1 .. 8; read with order > 0 only */
+    uint32_t left;   /* 0 .. 16 frames of context in front */
+    uint32_t right;  /* 0 .. 16 behind */
+    uint32_t stride; /* 1 .. 64: every stride-th frame is kept */
+    float pad_value;
+} alacgpu_stack_config;
+typedef struct alacgpu_stack alacgpu_stack;
+int alacgpu_stack_create(int device, const alacgpu_stack_config* config, alacgpu_stack** out);
+void alacgpu_stack_destroy(alacgpu_stack* st);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernel (valid after a sync). */
+void* alacgpu_stack_stream(alacgpu_stack* st);
+int alacgpu_stack_synchronize(alacgpu_stack* st);
+int alacgpu_stack_last_ms(alacgpu_stack* st, float* ms);
+/* G = ceil(in_frames / stride). 0 for a NULL handle. */
+uint64_t alacgpu_stack_out_frames(const alacgpu_stack* st, uint64_t in_frames);
+/*
+ * rows x frames x bins elements of d_in -> rows x G x D elements of d_out, which has strides of its own (frame stride 1: [rows]
+ * [D][G]; bin stride 1: [rows][G][D]) whatever the input's layout. Every element (r, g < G, j < D) of the output is written
+ * exactly once and nothing else is touched but d_out_lengths (int32 [rows] on the device, or NULL). d_lengths: int32 [rows] on the
+ * device, or NULL. rows = 0 or frames = 0 succeeds and touches nothing. ALACGPU_E_ARG before any HIP call: a NULL handle; with
+ * work to do a NULL d_in or d_out, a base that is not 4-byte aligned, neither inner stride equal to 1, an inner stride below the
+ * other axis' extent, a row stride below the row's extent, an output whose span of addresses meets the input's (there is no in
+ * place: the shape differs), frames above 2^31 - 1, or sizes whose products overflow. Asynchronous on the handle's stream unless
+ * sync != 0: the input must be complete, or ordered on that stream, before the call.
+ */
+int alacgpu_stack_device(alacgpu_stack* st, const float* d_in, size_t in_row_stride, size_t in_frame_stride, size_t in_bin_stride,
+                         size_t rows, size_t frames, const int32_t* d_lengths, float* d_out, size_t out_row_stride,
+                         size_t out_frame_stride, size_t out_bin_stride, int32_t* d_out_lengths, int sync);
+/* The plan the handle's kernel uses: a tile is tile_out output frames of a row, stages at most tile_in input frames of tile_bins
+ * bins at a time (tile_bins = bins unless the images of one output frame would not fit) in lds_bytes <= 25 600 of LDS, all
+ * functions of the configuration alone; window is 0 at order 0; and (where the pointer is not NULL and the capacity, counted in
+ * entries, suffices) the weights: w_1 (w1_entries = 2 window + 1, or 0), then w_2 (w2_entries = 4 window + 1, or 0). */
+typedef struct alacgpu_stack_info {
+    uint32_t bins, order, window, left, right, stride, columns, tile_out, tile_in, tile_bins, lds_bytes, w1_entries, w2_entries;
+} alacgpu_stack_info;
+int alacgpu_stack_plan(const alacgpu_stack* st, alacgpu_stack_info* info, float* weights_out, size_t weights_cap);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

@@ -36,6 +36,7 @@ __all__ = [
     "MelSpectrogram", "NewMelSpectrogram", "mel_spectrogram", "spectrogram", "whisper_log_mel",
     "KaldiFeatures", "NewKaldiFeatures", "kaldi_fbank", "kaldi_mfcc",
     "NormConfig", "FeatureNorm", "NewFeatureNorm", "normalize_features", "kaldi_frame_counts", "load_features",
+    "StackConfig", "StackInfo", "FrameStack", "NewFrameStack", "stack_frames", "add_deltas", "lfr",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -312,6 +313,16 @@ _EXPORTS = {
                                            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
     "alacgpu_norm_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                          ctypes.c_size_t]),
+    "alacgpu_stack_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_stack_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_stack_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_stack_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_stack_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_stack_out_frames": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "alacgpu_stack_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_stack_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -1669,13 +1680,195 @@ def kaldi_frame_counts(lengths, frame_length, frame_shift, snip_edges=True):
     return torch.where(T >= W, n, torch.zeros_like(n)).to(torch.int32)
 
 
+# ---- FrameStack (new: deltas, context splicing and subsampling behind the normalisation, per-row lengths) ----------------
+class StackConfig(ctypes.Structure):
+    """alacgpu_stack_config (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("bins", "order", "window", "left", "right", "stride")] + [("pad_value", ctypes.c_float)]
+
+
+class StackInfo(ctypes.Structure):
+    """alacgpu_stack_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("bins", "order", "window", "left", "right", "stride", "columns", "tile_out", "tile_in",
+                                               "tile_bins", "lds_bytes", "w1_entries", "w2_entries")]
+
+
+def _stack_int(v, name, lo, hi):
+    if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+        raise ValueError("%s is an integer in [%d, %d], not %r" % (name, lo, hi, v))
+    return int(v)
+
+
+class FrameStack(_RowPass):
+    """float32 features with per-row lengths -> their deltas, spliced context and subsampling in one pass on one MI355X, with
+    lengths of their own (include/alacgpu.h: alacgpu_stack_*). Per row over its first n = clamp(lengths, 0, frames)
+    frames: d_0 = x, d_k = the delta features of order k <= order with Kaldi's weights (the ramp -window .. window over sum j^2,
+    convolved k times), every frame index clamped to [0, n - 1]: the row's own first and last valid frame are replicated, never
+    the padding behind them. Output frame g < m = ceil(n / stride) holds, for c = 0 .. left + right, the d_0 .. d_order of frame
+    clamp(g * stride + c - left, 0, n - 1), bins each: (left + right + 1) * (order + 1) * bins columns; the frames from m on are
+    pad_value. Order 1 is torchaudio.functional.compute_deltas(mode="replicate") with win_length = 2 * window + 1; order 2 is
+    Kaldi's add-deltas, with one clamp on x, and not compute_deltas applied twice (which clamps the deltas at the edges again).
+    order 0 is splice-feats, the stride alone subsample-feats, left (m - 1) // 2, right m - 1 - left, stride n FunASR's
+    apply_lfr(m, n). Each delta is one chain of float32 fused multiply-adds in tap order, so the bits depend on the row's own data
+    and n only: not on the batch, nor on either layout. ValueError, before any HIP call, for bins outside [1, 4096], order outside
+    [0, 2], window outside [1, 8] with an order above 0, left or right outside [0, 16], stride outside [1, 64], or more than 4096
+    columns. Single-caller, bound to one device and one stream. out_frames(F) is ceil(F / stride)."""
+
+    _CREATE, _DESTROY, _OUT_FRAMES = "alacgpu_stack_create", "alacgpu_stack_destroy", "alacgpu_stack_out_frames"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_stack_last_ms", "alacgpu_stack_synchronize"
+
+    def __init__(self, bins, order=0, window=2, left=0, right=0, stride=1, pad_value=0.0, device=0):
+        super().__init__()
+        self.bins, self.order = _stack_int(bins, "bins", 1, 4096), _stack_int(order, "order", 0, 2)
+        self.window = _stack_int(window, "window", 1, 8) if self.order else 0
+        self.left, self.right = _stack_int(left, "left", 0, 16), _stack_int(right, "right", 0, 16)
+        self.stride = _stack_int(stride, "stride", 1, 64)
+        self.columns = (self.left + self.right + 1) * (self.order + 1) * self.bins
+        self.config = StackConfig(self.bins, self.order, self.window, self.left, self.right, self.stride, float(pad_value))
+        self._create(device, ctypes.byref(self.config))
+
+    def stack_device(self, d_in, in_strides, rows, frames, d_lengths, d_out, out_strides, d_out_lengths=0, sync=True):
+        """alacgpu_stack_device: raw device pointers (ints; d_lengths and d_out_lengths may be 0), in_strides / out_strides the
+        (row, frame, bin) strides in elements, one of the two inner ones 1 in each. Exactly the rows x out_frames(frames) x columns
+        elements of the output and the rows out lengths are written; the output may not overlap the input. Runs on the handle's
+        stream, which does not order against torch's: synchronize the input first."""
+        _check(self._lib.alacgpu_stack_device(self._h, d_in, *[int(s) for s in in_strides], rows, frames, d_lengths or None, d_out,
+                                              *[int(s) for s in out_strides], d_out_lengths or None, 1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_stack_plan -> dict: the parameters, columns, tile_out (the output frames of a tile), tile_in (the input frames it
+        stages at most), tile_bins, lds_bytes, and w1 / w2: the delta weights as float32 [2 window + 1] / [4 window + 1], or
+        None above the order."""
+        info = StackInfo()
+        (w,) = _fetch_plan(self._lib.alacgpu_stack_plan, self._h, info, lambda i: np.zeros(i.w1_entries + i.w2_entries, np.float32))
+        out = {k: int(getattr(info, k)) for k, _ in StackInfo._fields_ if not k.endswith("_entries")}
+        out.update(w1=w[:info.w1_entries] if info.w1_entries else None, w2=w[info.w1_entries:] if info.w2_entries else None)
+        return out
+
+    def __call__(self, feats, lengths=None, layout="frames", out=None, out_layout=None):
+        """A float32 tensor [..., F, bins] (layout "frames") or [..., bins, F] ("bins") -> (y, out_lengths): y [..., G, columns]
+        (out_layout "frames") or [..., columns, G] ("bins"; default: layout) with G = out_frames(F), new and contiguous or `out`,
+        and out_lengths int32 [...] on the device, ceil(n / stride) per row. feats is used on its own strides, views such as
+        feats[..., :-1] included, under FeatureNorm's rule: one inner stride is 1 and the leading dimensions flatten without a
+        copy; anything else is made contiguous first. lengths: None (every frame is valid) or one integer per row, the count of
+        its valid frames. out: a float32 tensor of y's shape on the device that shares no memory with feats. ValueError for
+        another dtype, a bins dimension that is not the handle's, or lengths of another count."""
+        import torch
+        out_layout = layout if out_layout is None else out_layout
+        if layout not in _FBANK_LAYOUTS or out_layout not in _FBANK_LAYOUTS:
+            raise ValueError("layout and out_layout are 'frames' or 'bins', not %r / %r" % (layout, out_layout))
+        if not self._h:
+            raise ValueError("the handle is closed")
+        if not isinstance(feats, torch.Tensor) or feats.dtype is not torch.float32 or feats.ndim < 2:
+            raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
+        if int(feats.shape[-1 if layout == "frames" else -2]) != self.bins:
+            raise ValueError("feats has %d bins, the handle %d" % (feats.shape[-1 if layout == "frames" else -2], self.bins))
+        dev = torch.device("cuda", self.device)
+        lead = tuple(feats.shape[:-2])
+        rows = 1
+        for d in lead:
+            rows *= int(d)
+        frames = int(feats.shape[-2 if layout == "frames" else -1])
+        G = -(-frames // self.stride)
+        oshape = lead + ((G, self.columns) if out_layout == "frames" else (self.columns, G))
+
+        def rows_of(t, lay):
+            """[..., a, b] -> ([rows, a, b] without a copy, strides), or (None, None)"""
+            try:
+                v = t.view((rows,) + tuple(t.shape[-2:])) if t.ndim != 3 else t
+            except RuntimeError:
+                return None, None
+            st = FeatureNorm._strides(v, lay) if v.numel() else (1, 1, 1)
+            return (v, st) if st else (None, None)
+
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or tuple(out.shape) != oshape or
+                                out.device != dev):
+            raise ValueError("out must be a float32 tensor of shape %r on the handle's device" % (oshape,))
+        x = feats.to(dev)
+        xv, xs = rows_of(x, layout)
+        if xv is None:
+            xv, xs = rows_of(x.contiguous(), layout)
+        y = torch.empty(oshape, dtype=torch.float32, device=dev) if out is None else out
+        yv, ys = rows_of(y, out_layout)
+        if yv is None:
+            raise ValueError("out needs rows that flatten without a copy and a frame or bin stride of 1")
+        d_len = 0
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor):
+                lengths = torch.as_tensor(np.asarray(lengths))
+            if lengths.numel() != rows or lengths.dtype.is_floating_point:
+                raise ValueError("lengths holds one integer per row: %d, not %d" % (rows, lengths.numel()))
+            info = torch.iinfo(torch.int32)
+            ln = lengths if lengths.dtype is torch.int32 else lengths.clamp(info.min, info.max).to(torch.int32)
+            ln = ln.to(dev).contiguous().reshape(rows)
+            d_len = ln.data_ptr()
+        out_len = torch.zeros(rows, dtype=torch.int32, device=dev)
+        if rows and frames:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            self.stack_device(xv.data_ptr(), xs, rows, frames, d_len, yv.data_ptr(), ys, out_len.data_ptr(), sync=True)
+        return y, out_len.reshape(lead)
+
+
+def NewFrameStack(bins, order=0, window=2, left=0, right=0, stride=1, pad_value=0.0, device=0):
+    """A FrameStack (context manager); ValueError where no plan can be built."""
+    return FrameStack(bins, order, window, left, right, stride, pad_value, device)
+
+
+_STACKS = {}  # (device, bins, order, window, left, right, stride, pad_value) -> FrameStack
+
+
+def stack_frames(feats, lengths=None, order=0, window=2, left=0, right=0, stride=1, layout="frames", pad_value=0.0, out=None,
+                 out_layout=None, device=None):
+    """FrameStack(bins, order, ...)(feats, lengths, layout, out, out_layout) -> (y, out_lengths) with the handle of a (device,
+    parameter set) made once and kept: feats a float32 tensor [..., F, bins] (layout "frames") or [..., bins, F] ("bins") on
+    cuda:`device` (default: the tensor's own, cuda:0 for a CPU tensor, which is uploaded)."""
+    import torch
+    if not isinstance(feats, torch.Tensor) or feats.ndim < 2:
+        raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
+    if layout not in _FBANK_LAYOUTS:
+        raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
+    bins = int(feats.shape[-1 if layout == "frames" else -2])
+    if device is None:
+        device = (feats.device.index or 0) if feats.is_cuda else 0
+    order = _stack_int(order, "order", 0, 2)
+    key = (device, bins, order, _stack_int(window, "window", 1, 8) if order else 0, _stack_int(left, "left", 0, 16),
+           _stack_int(right, "right", 0, 16), _stack_int(stride, "stride", 1, 64), np.float32(pad_value).tobytes())
+    st = _cached(_STACKS, key, lambda: FrameStack(bins, order, window, left, right, stride, pad_value, device))
+    return st(feats, lengths, layout, out, out_layout)
+
+
+def add_deltas(feats, lengths=None, order=2, window=2, layout="frames", **kw):
+    """Kaldi's add-deltas: stack_frames(feats, lengths, order=order, window=window, layout=layout, ...) -> (y with (order + 1) *
+    bins columns: the features, their deltas and delta-deltas; out_lengths = the lengths). 13 MFCCs give the usual 39."""
+    return stack_frames(feats, lengths, order=order, window=window, layout=layout, **kw)
+
+
+def lfr(feats, lengths=None, m=7, n=6, layout="frames", **kw):
+    """FunASR's low-frame-rate stacking apply_lfr(m, n) per row: m frames stacked every n frames, the first frame replicated
+    (m - 1) // 2 times in front and the row's own last valid frame behind: stack_frames with left (m - 1) // 2, right m - 1 -
+    left, stride n -> (y with m * bins columns, out_lengths = ceil(lengths / n)). 80 bins at 7 / 6 give Paraformer's 560."""
+    m = _stack_int(m, "m", 1, 33)
+    left = (m - 1) // 2
+    return stack_frames(feats, lengths, left=left, right=m - 1 - left, stride=n, layout=layout, **kw)
+
+
 def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="fbank", norm="mean", channel=0, transform="direct",
-                  device=0, **kaldi_kwargs):
+                  device=0, deltas=0, delta_window=2, context=(0, 0), subsample=1, **kaldi_kwargs):
     """Files to normalised features in one call: load_clips(sources, frame_offsets, num_frames, sample_rate=sample_rate) -> the
     channel `channel` -> kaldi_fbank (kind "fbank") or kaldi_mfcc ("mfcc") with kaldi_kwargs (torchaudio's names; frames layout)
     -> kaldi_frame_counts of load_clips' lengths -> FeatureNorm(stat=norm: "mean", "mean_var" or None, which only masks).
     -> (feats [B, F, D], frame_lengths int32 [B], sample_rate): row j's first frame_lengths[j] frames are normalised over
-    themselves, the frames behind them are 0. Nothing but that composition; its two limits are kaldi_frame_counts'."""
+    themselves, the frames behind them are 0. Nothing but that composition; its two limits are kaldi_frame_counts'.
+    With deltas (0..2, delta_window frames each side), context (left, right) or subsample other than their defaults, stack_frames
+    runs behind the normalisation, which is Kaldi's order: feats is [B, ceil(F / subsample), (left + right + 1) * (deltas + 1) * D]
+    and frame_lengths its out_lengths. With the defaults that pass is not run."""
+    try:
+        left, right = context
+    except (TypeError, ValueError):
+        raise ValueError("context is (left, right), not %r" % (context,))
+    stacked = (_stack_int(deltas, "deltas", 0, 2), _stack_int(left, "context left", 0, 16), _stack_int(right, "context right", 0, 16),
+               _stack_int(subsample, "subsample", 1, 64)) != (0, 0, 0, 1)
     if kind not in ("fbank", "mfcc"):
         raise ValueError("kind is 'fbank' or 'mfcc', not %r" % (kind,))
     if not (norm is None or isinstance(norm, str)) or norm not in (None, "mean", "mean_var"):
@@ -1691,7 +1884,11 @@ def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="f
     W = int(rate * kaldi_kwargs.get("frame_length", 25.0) * 0.001)
     h = int(rate * kaldi_kwargs.get("frame_shift", 10.0) * 0.001)
     counts = kaldi_frame_counts(lengths, W, h, kaldi_kwargs.get("snip_edges", True))
-    return normalize_features(feats, counts, stat=norm, out=feats, device=device), counts, rate
+    feats = normalize_features(feats, counts, stat=norm, out=feats, device=device)
+    if stacked:
+        feats, counts = stack_frames(feats, counts, order=deltas, window=delta_window, left=left, right=right, stride=subsample,
+                                     device=device)
+    return feats, counts, rate
 
 
 def NewDecoder(source, device=0, window=1024):
