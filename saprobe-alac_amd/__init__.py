@@ -893,7 +893,7 @@ def NewPacketEncoder(config, device=0):
     return PacketEncoder(config, device)
 
 
-# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures): what they share -----------------
+# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures, FeatureNorm, FrameStack): what they share
 class _RowPass:
     """The handle of a row pass: _h (NULL once closed), _lib and device, and the entries every such handle has. A subclass names
     its C functions one by one (they are irregular: alacgpu_resampler_last_ms, but alacgpu_resample_out_frames), creates the
@@ -996,6 +996,80 @@ def _cached(cache, key, make):
     if key not in cache:
         cache[key] = make()
     return cache[key]
+
+
+# ---- the passes over feature tensors (FeatureNorm, FrameStack): one strided view with per-row lengths ----
+def _feature_strides(t, layout):
+    """A tensor [rows, F, bins] (layout frames) or [rows, bins, F] (bins) -> its (row, frame, bin) strides, or None where
+    neither inner stride is 1. The stride of an axis of one element is whatever torch keeps there: it is replaced."""
+    rs, a, b = (int(s) for s in t.stride())
+    fs, bs = (a, b) if layout == "frames" else (b, a)
+    frames, bins = (t.shape[1], t.shape[2]) if layout == "frames" else (t.shape[2], t.shape[1])
+    if frames == 1:
+        fs = bins if bs == 1 else 1
+    if bins == 1:
+        bs = frames if fs == 1 else 1
+    extent = (frames - 1) * fs + (bins - 1) * bs + 1
+    if t.shape[0] == 1:
+        rs = extent
+    if (fs != 1 and bs != 1) or rs < extent:
+        return None
+    return rs, fs, bs
+
+
+def _feature_rows(t, rows, layout):
+    """[..., a, b] -> ([rows, a, b] without a copy, strides), or (None, None)"""
+    try:
+        v = t.view((rows,) + tuple(t.shape[-2:])) if t.ndim != 3 else t
+    except RuntimeError:
+        return None, None
+    st = _feature_strides(v, layout) if v.numel() else (1, 1, 1)
+    return (v, st) if st else (None, None)
+
+
+def _feature_input(feats, layout, device):
+    """What the one-call functions check before they pick a handle -> (bins, the device index: None resolved to the tensor's
+    own, cuda:0 for what is on the host)"""
+    import torch
+    if not isinstance(feats, torch.Tensor) or feats.ndim < 2:
+        raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
+    if layout not in _FBANK_LAYOUTS:
+        raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
+    if device is None:
+        device = (feats.device.index or 0) if feats.is_cuda else 0
+    return int(feats.shape[-1 if layout == "frames" else -2]), device
+
+
+class _FeaturePass(_RowPass):
+    """A row pass over float32 features [..., F, bins] or [..., bins, F] with per-row lengths; the subclass sets bins."""
+
+    def _features(self, feats, layout):
+        """What a __call__ checks behind its layouts -> (the handle's torch device, the leading dimensions, rows, frames)"""
+        import torch
+        if not self._h:
+            raise ValueError("the handle is closed")
+        if not isinstance(feats, torch.Tensor) or feats.dtype is not torch.float32 or feats.ndim < 2:
+            raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
+        if int(feats.shape[-1 if layout == "frames" else -2]) != self.bins:
+            raise ValueError("feats has %d bins, the handle %d" % (feats.shape[-1 if layout == "frames" else -2], self.bins))
+        lead = tuple(feats.shape[:-2])
+        rows = int(np.prod(lead, dtype=np.int64))
+        return torch.device("cuda", self.device), lead, rows, int(feats.shape[-2 if layout == "frames" else -1])
+
+    @staticmethod
+    def _lengths(lengths, rows, dev):
+        """lengths (None, or one integer per row) -> None, or an int32 tensor [rows] on dev: lengths itself where it is one
+        already. The caller holds the tensor until its device call, which is synchronous, has returned."""
+        import torch
+        if lengths is None:
+            return None
+        if not isinstance(lengths, torch.Tensor):
+            lengths = torch.as_tensor(np.asarray(lengths))
+        if lengths.numel() != rows or lengths.dtype.is_floating_point:
+            raise ValueError("lengths holds one integer per row: %d, not %d" % (rows, lengths.numel()))
+        info = torch.iinfo(torch.int32)
+        ln = lengths if lengths.dtype is torch.int32 else lengths.clamp(info.min, info.max).to(torch.int32)
+        return ln.to(dev).contiguous().reshape(rows)
 
 
 # ---- Resampler (new: torchaudio.functional.resample's sinc_interp_hann on the device) ----------------------------------
@@ -1492,7 +1566,7 @@ def _norm_table(v, bins, name):
     return np.ascontiguousarray(a)
 
 
-class FeatureNorm(_RowPass):
+class FeatureNorm(_FeaturePass):
     """float32 features with per-row lengths -> normalised features with the padding masked, on one MI355X (include/alacgpu.h:
     alacgpu_norm_*). Per row over its first n = clamp(lengths, 0, frames) frames: stat "mean" subtracts each bin's mean,
     "mean_var" also multiplies by 1 / sqrt(max(variance, var_floor)) (Kaldi's apply-cmvn --norm-vars), "max" clamps below (the
@@ -1538,24 +1612,6 @@ class FeatureNorm(_RowPass):
         out.update(shift=shift if info.shift_entries else None, scale=scale if info.scale_entries else None)
         return out
 
-    @staticmethod
-    def _strides(t, layout):
-        """A tensor [rows, F, bins] (layout frames) or [rows, bins, F] (bins) -> its (row, frame, bin) strides, or None where
-        neither inner stride is 1. The stride of an axis of one element is whatever torch keeps there: it is replaced."""
-        rs, a, b = (int(s) for s in t.stride())
-        fs, bs = (a, b) if layout == "frames" else (b, a)
-        frames, bins = (t.shape[1], t.shape[2]) if layout == "frames" else (t.shape[2], t.shape[1])
-        if frames == 1:
-            fs = bins if bs == 1 else 1
-        if bins == 1:
-            bs = frames if fs == 1 else 1
-        extent = (frames - 1) * fs + (bins - 1) * bs + 1
-        if t.shape[0] == 1:
-            rs = extent
-        if (fs != 1 and bs != 1) or rs < extent:
-            return None
-        return rs, fs, bs
-
     def __call__(self, feats, lengths=None, layout="frames", out=None, return_stats=False):
         """A float32 tensor [..., F, bins] (layout "frames", the Kaldi pass's default) or [..., bins, F] ("bins": its other
         layout and the spectrogram pass's) -> the normalised tensor of the same shape on the handle's device. It works on the
@@ -1568,28 +1624,7 @@ class FeatureNorm(_RowPass):
         import torch
         if layout not in _FBANK_LAYOUTS:
             raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
-        if not self._h:
-            raise ValueError("the handle is closed")
-        if not isinstance(feats, torch.Tensor) or feats.dtype is not torch.float32 or feats.ndim < 2:
-            raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
-        if int(feats.shape[-1 if layout == "frames" else -2]) != self.bins:
-            raise ValueError("feats has %d bins, the handle %d" % (feats.shape[-1 if layout == "frames" else -2], self.bins))
-        dev = torch.device("cuda", self.device)
-        lead, inner = tuple(feats.shape[:-2]), tuple(feats.shape[-2:])
-        rows = 1
-        for d in lead:
-            rows *= int(d)
-        frames = int(inner[0 if layout == "frames" else 1])
-
-        def rows_of(t):
-            """[..., a, b] -> ([rows, a, b] without a copy, strides), or (None, None)"""
-            try:
-                v = t.view((rows,) + inner) if t.ndim != 3 else t
-            except RuntimeError:
-                return None, None
-            st = self._strides(v, layout) if v.numel() else (1, 1, 1)
-            return (v, st) if st else (None, None)
-
+        dev, lead, rows, frames = self._features(feats, layout)
         same = out is feats
         if same and feats.device != dev:
             raise ValueError("in place needs feats on the handle's device")
@@ -1597,33 +1632,24 @@ class FeatureNorm(_RowPass):
             if not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or out.shape != feats.shape or out.device != dev:
                 raise ValueError("out must be a float32 tensor of feats' shape on the handle's device")
         x = feats.to(dev)
-        xv, xs = rows_of(x)
+        xv, xs = _feature_rows(x, rows, layout)
         if xv is None:
             if same:
                 raise ValueError("in place needs a tensor whose rows flatten without a copy and whose frame or bin stride is 1")
-            xv, xs = rows_of(x.contiguous())
+            xv, xs = _feature_rows(x.contiguous(), rows, layout)
         if same:
             result, ov, os_ = feats, xv, xs
         else:
             result = torch.empty(feats.shape, dtype=torch.float32, device=dev) if out is None else out
-            ov, os_ = rows_of(result)
+            ov, os_ = _feature_rows(result, rows, layout)
             if ov is None:
                 raise ValueError("out needs rows that flatten without a copy and a frame or bin stride of 1")
-        d_len = 0
-        if lengths is not None:
-            if not isinstance(lengths, torch.Tensor):
-                lengths = torch.as_tensor(np.asarray(lengths))
-            if lengths.numel() != rows or lengths.dtype.is_floating_point:
-                raise ValueError("lengths holds one integer per row: %d, not %d" % (rows, lengths.numel()))
-            info = torch.iinfo(torch.int32)
-            ln = lengths if lengths.dtype is torch.int32 else lengths.clamp(info.min, info.max).to(torch.int32)
-            ln = ln.to(dev).contiguous().reshape(rows)
-            d_len = ln.data_ptr()
+        ln = self._lengths(lengths, rows, dev)
         stats = torch.empty((rows, 2, self.bins), dtype=torch.float32, device=dev) if return_stats else None
         if rows and frames:
             torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
-            self.norm_device(xv.data_ptr(), xs, rows, frames, d_len, ov.data_ptr(), os_, stats.data_ptr() if return_stats else 0,
-                             sync=True)
+            self.norm_device(xv.data_ptr(), xs, rows, frames, 0 if ln is None else ln.data_ptr(), ov.data_ptr(), os_,
+                             stats.data_ptr() if return_stats else 0, sync=True)
         elif return_stats:
             stats.zero_()
         return (result, stats.reshape(lead + (2, self.bins))) if return_stats else result
@@ -1642,14 +1668,7 @@ def normalize_features(feats, lengths=None, stat="mean", layout="frames", shift=
     """FeatureNorm(bins, stat, ...)(feats, lengths, layout, out, return_stats) with the handle of a (device, parameter set) made
     once and kept: feats a float32 tensor [..., F, bins] (layout "frames") or [..., bins, F] ("bins") on cuda:`device` (default:
     the tensor's own, cuda:0 for a CPU tensor, which is uploaded). shift / scale enter the key by their bytes."""
-    import torch
-    if not isinstance(feats, torch.Tensor) or feats.ndim < 2:
-        raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
-    if layout not in _FBANK_LAYOUTS:
-        raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
-    bins = int(feats.shape[-1 if layout == "frames" else -2])
-    if device is None:
-        device = (feats.device.index or 0) if feats.is_cuda else 0
+    bins, device = _feature_input(feats, layout, device)
     sh, sc = _norm_table(shift, bins, "shift"), _norm_table(scale, bins, "scale")
     if not (stat is None or isinstance(stat, str)):
         raise ValueError("stat is 'none', 'mean', 'mean_var' or 'max', not %r" % (stat,))
@@ -1700,7 +1719,7 @@ def _stack_int(v, name, lo, hi):
     return int(v)
 
 
-class FrameStack(_RowPass):
+class FrameStack(_FeaturePass):
     """float32 features with per-row lengths -> their deltas, spliced context and subsampling in one pass on one MI355X, with
     lengths of their own (include/alacgpu.h: alacgpu_stack_*). Per row over its first n = clamp(lengths, 0, frames)
     frames: d_0 = x, d_k = the delta features of order k <= order with Kaldi's weights (the ramp -window .. window over sum j^2,
@@ -1758,55 +1777,26 @@ class FrameStack(_RowPass):
         out_layout = layout if out_layout is None else out_layout
         if layout not in _FBANK_LAYOUTS or out_layout not in _FBANK_LAYOUTS:
             raise ValueError("layout and out_layout are 'frames' or 'bins', not %r / %r" % (layout, out_layout))
-        if not self._h:
-            raise ValueError("the handle is closed")
-        if not isinstance(feats, torch.Tensor) or feats.dtype is not torch.float32 or feats.ndim < 2:
-            raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
-        if int(feats.shape[-1 if layout == "frames" else -2]) != self.bins:
-            raise ValueError("feats has %d bins, the handle %d" % (feats.shape[-1 if layout == "frames" else -2], self.bins))
-        dev = torch.device("cuda", self.device)
-        lead = tuple(feats.shape[:-2])
-        rows = 1
-        for d in lead:
-            rows *= int(d)
-        frames = int(feats.shape[-2 if layout == "frames" else -1])
+        dev, lead, rows, frames = self._features(feats, layout)
         G = -(-frames // self.stride)
         oshape = lead + ((G, self.columns) if out_layout == "frames" else (self.columns, G))
-
-        def rows_of(t, lay):
-            """[..., a, b] -> ([rows, a, b] without a copy, strides), or (None, None)"""
-            try:
-                v = t.view((rows,) + tuple(t.shape[-2:])) if t.ndim != 3 else t
-            except RuntimeError:
-                return None, None
-            st = FeatureNorm._strides(v, lay) if v.numel() else (1, 1, 1)
-            return (v, st) if st else (None, None)
-
         if out is not None and (not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or tuple(out.shape) != oshape or
                                 out.device != dev):
             raise ValueError("out must be a float32 tensor of shape %r on the handle's device" % (oshape,))
         x = feats.to(dev)
-        xv, xs = rows_of(x, layout)
+        xv, xs = _feature_rows(x, rows, layout)
         if xv is None:
-            xv, xs = rows_of(x.contiguous(), layout)
+            xv, xs = _feature_rows(x.contiguous(), rows, layout)
         y = torch.empty(oshape, dtype=torch.float32, device=dev) if out is None else out
-        yv, ys = rows_of(y, out_layout)
+        yv, ys = _feature_rows(y, rows, out_layout)
         if yv is None:
             raise ValueError("out needs rows that flatten without a copy and a frame or bin stride of 1")
-        d_len = 0
-        if lengths is not None:
-            if not isinstance(lengths, torch.Tensor):
-                lengths = torch.as_tensor(np.asarray(lengths))
-            if lengths.numel() != rows or lengths.dtype.is_floating_point:
-                raise ValueError("lengths holds one integer per row: %d, not %d" % (rows, lengths.numel()))
-            info = torch.iinfo(torch.int32)
-            ln = lengths if lengths.dtype is torch.int32 else lengths.clamp(info.min, info.max).to(torch.int32)
-            ln = ln.to(dev).contiguous().reshape(rows)
-            d_len = ln.data_ptr()
+        ln = self._lengths(lengths, rows, dev)
         out_len = torch.zeros(rows, dtype=torch.int32, device=dev)
         if rows and frames:
             torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
-            self.stack_device(xv.data_ptr(), xs, rows, frames, d_len, yv.data_ptr(), ys, out_len.data_ptr(), sync=True)
+            self.stack_device(xv.data_ptr(), xs, rows, frames, 0 if ln is None else ln.data_ptr(), yv.data_ptr(), ys,
+                              out_len.data_ptr(), sync=True)
         return y, out_len.reshape(lead)
 
 
@@ -1823,14 +1813,7 @@ def stack_frames(feats, lengths=None, order=0, window=2, left=0, right=0, stride
     """FrameStack(bins, order, ...)(feats, lengths, layout, out, out_layout) -> (y, out_lengths) with the handle of a (device,
     parameter set) made once and kept: feats a float32 tensor [..., F, bins] (layout "frames") or [..., bins, F] ("bins") on
     cuda:`device` (default: the tensor's own, cuda:0 for a CPU tensor, which is uploaded)."""
-    import torch
-    if not isinstance(feats, torch.Tensor) or feats.ndim < 2:
-        raise ValueError("feats must be a float32 torch tensor [..., F, bins] or [..., bins, F]")
-    if layout not in _FBANK_LAYOUTS:
-        raise ValueError("layout is 'frames' or 'bins', not %r" % (layout,))
-    bins = int(feats.shape[-1 if layout == "frames" else -2])
-    if device is None:
-        device = (feats.device.index or 0) if feats.is_cuda else 0
+    bins, device = _feature_input(feats, layout, device)
     order = _stack_int(order, "order", 0, 2)
     key = (device, bins, order, _stack_int(window, "window", 1, 8) if order else 0, _stack_int(left, "left", 0, 16),
            _stack_int(right, "right", 0, 16), _stack_int(stride, "stride", 1, 64), np.float32(pad_value).tobytes())

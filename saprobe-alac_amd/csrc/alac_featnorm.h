@@ -3,10 +3,8 @@
  * normalised features with the padding masked, as plain host + device code. k_featnorm.hip builds the gfx950 kernels from this
  * text; tests/host_sim/featnorm_sim.cpp builds the same text with g++ (contraction off) for the CPU suite.
  *
- * Element (r, f, b) of the input is in[r * in_rs + f * in_fs + b * in_bs] (element strides); exactly one of in_fs / in_bs is 1
- * ("frames" layout: the bins of a frame are contiguous; "bins" layout: the frames of a bin are). The output has three strides
- * of its own and may be the input itself (same base, same strides). n_r = clamp(lengths[r], 0, frames), or frames where
- * lengths is NULL. Per row, in this order:
+ * Input and output are addressed as alac_featview.h says: three element strides each, one inner stride 1, n_r valid frames in
+ * row r. The output may be the input itself (same base, same strides). Per row, in this order:
  *
  *   statistic over the valid frames f < n_r
  *     none      s = x
@@ -26,23 +24,21 @@
  * mean and rstd for mean_var, mean and 1.0 for mean, M in [r][0][0] for max, +0.0 elsewhere and in every row with n_r = 0.
  *
  * A TILE is one chunk of one row, one workgroup of 256. stage_tile brings its valid frames into an image (LDS on the device)
- * with loads along the contiguous axis, 16 bytes at a time in the chunks of the ABSOLUTE address space that lie inside a line
- * (as alacwf::stage_tile), element by element at a line's two ends. Lanes then take bins and walk the frames out of the image:
- * sum_tile / max_tile for the partial results of a (row, chunk), finish_* for a row's statistics out of the partials,
- * apply_tile for the output, which goes back into the image and from there, along the output's contiguous axis, to memory
- * (store_tile). All index arithmetic is in 64 bits.
+ * with loads along the contiguous axis (alacfv::lines_in). Lanes then take bins and walk the frames out of the image: sum_tile /
+ * max_tile for the partial results of a (row, chunk), finish_* for a row's statistics out of the partials, apply_tile for the
+ * output, which goes back into the image and from there, along the output's contiguous axis, to memory (store_tile).
  */
 #ifndef ALAC_FEATNORM_H
 #define ALAC_FEATNORM_H
 
-#include "alac_waveform.h"
+#include "alac_featview.h"
 
 #include <cmath>
 #include <cstring>
 
 namespace alacfn {
 
-using alacwf::kThreads;
+using alacfv::kThreads, alacfv::length_of, alacfv::lines_in, alacfv::lines_out;
 
 constexpr uint32_t kNone = 0, kMean = 1, kMeanVar = 2, kMax = 3; /* ALACGPU_NORM_STAT_* */
 constexpr uint32_t kSum = 0, kSquares = 1, kLargest = 2;         /* what a partials launch reduces */
@@ -50,9 +46,6 @@ constexpr uint32_t kMaxBins = 4096;
 constexpr uint32_t kMaxTileFrames = 64;  /* 256 contiguous bytes of a bin in the bins layout */
 constexpr uint32_t kLdsFloats = 12800;   /* 51 200 bytes: three workgroups share a CU's 160 KB at the widest tile */
 constexpr uint32_t kRed = kThreads;      /* the keys of a maximum, behind the image */
-
-/* 16 bytes moved by one instruction */
-typedef float F4 __attribute__((vector_size(16), may_alias));
 
 /* frames of a tile: the largest power of two <= 64 whose image (a line pitch of tile_frames | 1 in the bins layout) and keys fit */
 ALAC_WF_FN uint32_t tile_frames_of(uint32_t bins) {
@@ -79,13 +72,6 @@ struct Params {
     float* partial;     /* [rows][chunks][bins], for max [rows][chunks] */
     float* stats;       /* [rows][2][bins] */
 };
-
-ALAC_WF_FN uint64_t length_of(const Params& p, uint64_t row) {
-    if (!p.lengths) return p.frames;
-    const int32_t n = p.lengths[row];
-    if (n <= 0) return 0u;
-    return (uint64_t)n < p.frames ? (uint64_t)n : p.frames;
-}
 
 /* a float as an integer that orders as the float does, +0.0 above -0.0 */
 ALAC_WF_FN int32_t key_of(float v) {
@@ -116,7 +102,7 @@ ALAC_WF_FN Tile make_tile(const Params& p, uint64_t row, uint64_t chunk) {
     Tile t{};
     t.row = row;
     t.chunk = chunk;
-    t.n = length_of(p, row);
+    t.n = length_of(p.lengths, p.frames, row);
     const uint64_t f0 = chunk * p.tile_frames;
     t.nf = p.frames - f0 < p.tile_frames ? (uint32_t)(p.frames - f0) : p.tile_frames;
     t.nv = t.n > f0 ? (t.n - f0 < t.nf ? (uint32_t)(t.n - f0) : t.nf) : 0u;
@@ -130,48 +116,6 @@ ALAC_WF_FN Tile make_tile(const Params& p, uint64_t row, uint64_t chunk) {
         t.lb = p.tile_frames | 1u;
     }
     return t;
-}
-
-/* nl lines of len contiguous floats, line l at src + l * stride, into image[l * sl + e * se]: work item `tid` of kThreads takes
- * its 16-byte chunks of the absolute address space. Nothing outside the lines is read. */
-ALAC_WF_FN void lines_in(const float* src, uint64_t stride, uint32_t nl, uint32_t len, float* image, uint32_t sl, uint32_t se,
-                         uint32_t tid) {
-    const uint32_t cpl = (len + 3u) / 4u + 1u; /* chunks that cover a line at any offset within its first */
-    const uint32_t total = nl * cpl;
-    for (uint32_t c = tid; c < total; c += kThreads) {
-        const uint32_t l = c / cpl, k = c - l * cpl;
-        const float* s = src + (uint64_t)l * stride;
-        const int32_t e0 = (int32_t)(4u * k) - (int32_t)(((uintptr_t)s >> 2) & 3u);
-        float* d = image + l * sl;
-        if (e0 >= 0 && (uint32_t)e0 + 4u <= len) {
-            const F4 v = *(const F4*)(s + e0);
-            for (uint32_t j = 0; j < 4u; j++) d[((uint32_t)e0 + j) * se] = v[j];
-        } else {
-            for (int32_t j = 0; j < 4; j++)
-                if (e0 + j >= 0 && (uint32_t)(e0 + j) < len) d[(uint32_t)(e0 + j) * se] = s[e0 + j];
-        }
-    }
-}
-
-/* the reverse: image[l * sl + e * se] to line l at dst + l * stride; exactly the lines' elements are written */
-ALAC_WF_FN void lines_out(float* dst, uint64_t stride, uint32_t nl, uint32_t len, const float* image, uint32_t sl, uint32_t se,
-                          uint32_t tid) {
-    const uint32_t cpl = (len + 3u) / 4u + 1u;
-    const uint32_t total = nl * cpl;
-    for (uint32_t c = tid; c < total; c += kThreads) {
-        const uint32_t l = c / cpl, k = c - l * cpl;
-        float* d = dst + (uint64_t)l * stride;
-        const int32_t e0 = (int32_t)(4u * k) - (int32_t)(((uintptr_t)d >> 2) & 3u);
-        const float* s = image + l * sl;
-        if (e0 >= 0 && (uint32_t)e0 + 4u <= len) {
-            F4 v;
-            for (uint32_t j = 0; j < 4u; j++) v[j] = s[((uint32_t)e0 + j) * se];
-            *(F4*)(d + e0) = v;
-        } else {
-            for (int32_t j = 0; j < 4; j++)
-                if (e0 + j >= 0 && (uint32_t)(e0 + j) < len) d[e0 + j] = s[(uint32_t)(e0 + j) * se];
-        }
-    }
 }
 
 /* Phase 1: the tile's nv valid frames into the image. Frames that follow each other without a gap are one line. */
@@ -261,7 +205,7 @@ ALAC_WF_FN void finish_bin(const Params& p, uint64_t row, uint32_t b) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const uint64_t n = length_of(p, row);
+    const uint64_t n = length_of(p.lengths, p.frames, row);
     const uint64_t K = chunks_of(p, n);
     const float* part = p.partial + row * p.chunks * p.bins + b;
     float acc = 0.0f;
@@ -280,7 +224,7 @@ ALAC_WF_FN void finish_bin(const Params& p, uint64_t row, uint32_t b) {
 /* A row's maximum: every work item the largest of the chunks tid, tid + 256, ... into red[tid]; then reduce_keys twice; then
  * put_row_max */
 ALAC_WF_FN void row_max(const Params& p, uint64_t row, int32_t* red, uint32_t tid) {
-    const uint64_t K = chunks_of(p, length_of(p, row));
+    const uint64_t K = chunks_of(p, length_of(p.lengths, p.frames, row));
     const float* part = p.partial + row * p.chunks;
     int32_t k = lowest_key();
     for (uint64_t c = tid; c < K; c += kThreads) {
@@ -290,7 +234,7 @@ ALAC_WF_FN void row_max(const Params& p, uint64_t row, int32_t* red, uint32_t ti
     red[tid] = k;
 }
 ALAC_WF_FN void put_row_max(const Params& p, uint64_t row, const int32_t* red, uint32_t tid) {
-    const uint64_t n = length_of(p, row);
+    const uint64_t n = length_of(p.lengths, p.frames, row);
     float* st = p.stats + row * 2u * p.bins;
     for (uint32_t i = tid; i < 2u * p.bins; i += kThreads) st[i] = (i == 0u && n) ? float_of(red[0]) : 0.0f;
 }
@@ -349,20 +293,6 @@ inline bool config_ok(const Config& c) {
     return true;
 }
 
-/* one tensor's three strides -> 0 refused, 1 frames layout (bin stride 1, frames at least a line apart), 2 bins layout (frame
- * stride 1, bins at least a line apart); the stride of an axis of one element is free. The row stride is at least the row's
- * extent. */
-inline int layout_of(uint64_t rs, uint64_t fs, uint64_t bs, uint64_t rows, uint64_t frames, uint32_t bins) {
-    const uint64_t lim = (uint64_t)1 << 61;
-    if (rs > lim / rows || fs > lim / frames || bs > lim / bins) return 0;
-    int lay = 0;
-    if (bs == 1u && (frames == 1u || fs >= bins)) lay = 1;
-    else if (fs == 1u && (bins == 1u || bs >= frames)) lay = 2;
-    if (!lay) return 0;
-    const uint64_t extent = lay == 1 ? (frames == 1u ? 0u : (frames - 1u) * fs) + bins : (bins == 1u ? 0u : (bins - 1u) * bs) + frames;
-    return rs >= extent ? lay : 0;
-}
-
 /* floats of scratch a pass needs behind the caller's buffers: the partials, and the stats where the caller keeps none */
 inline bool scratch_floats_of(const Config& c, uint64_t rows, uint64_t frames, bool own_stats, uint64_t* floats) {
     const uint32_t tf = tile_frames_of(c.bins);
@@ -384,28 +314,21 @@ inline bool scratch_floats_of(const Config& c, uint64_t rows, uint64_t frames, b
     return true;
 }
 
-/* the arguments of one pass (rows, frames >= 1) but for the scratch block (set_scratch); false for what the entry rejects. The
- * kernels tell the layout by the bin stride: 1 is the frames layout. */
+/* the arguments of one pass (rows, frames >= 1) but for the scratch block (set_scratch); false for what the entry rejects */
 inline bool make_params(const Config& c, const float* in, uint64_t in_rs, uint64_t in_fs, uint64_t in_bs, uint64_t rows,
                         uint64_t frames, const int32_t* lengths, float* out, uint64_t out_rs, uint64_t out_fs, uint64_t out_bs,
                         float* stats, const float* shift, const float* scale, Params* p) {
-    if (!in || !out || ((uintptr_t)in & 3u) || ((uintptr_t)out & 3u) || ((uintptr_t)lengths & 3u) || ((uintptr_t)stats & 3u))
+    if (!in || !out || ((uintptr_t)lengths & 3u) || ((uintptr_t)stats & 3u)) return false;
+    Params q{};
+    if (!alacfv::strides_of(in, in_rs, in_fs, in_bs, rows, frames, c.bins, &q.in_fs, &q.in_bs) ||
+        !alacfv::strides_of(out, out_rs, out_fs, out_bs, rows, frames, c.bins, &q.out_fs, &q.out_bs))
         return false;
-    const int li = layout_of(in_rs, in_fs, in_bs, rows, frames, c.bins);
-    const int lo = layout_of(out_rs, out_fs, out_bs, rows, frames, c.bins);
-    if (!li || !lo) return false;
     uint64_t floats;
     if (!scratch_floats_of(c, rows, frames, stats == nullptr, &floats)) return false;
-    (void)floats;
-    Params q{};
     q.in = in;
     q.in_rs = in_rs;
-    q.in_fs = li == 2 ? 1u : frames == 1u ? c.bins : in_fs; /* the free stride: the other axis' extent */
-    q.in_bs = li == 1 ? 1u : c.bins == 1u ? frames : in_bs;
     q.out = out;
     q.out_rs = out_rs;
-    q.out_fs = lo == 2 ? 1u : frames == 1u ? c.bins : out_fs;
-    q.out_bs = lo == 1 ? 1u : c.bins == 1u ? frames : out_bs;
     q.lengths = lengths;
     q.rows = rows;
     q.frames = frames;

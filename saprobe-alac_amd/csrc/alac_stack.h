@@ -3,9 +3,8 @@
  * context splicing and subsampling in one pass, with lengths of their own, as plain host + device code. k_stack.hip builds the
  * gfx950 kernel from this text; tests/host_sim/stack_sim.cpp builds the same text with g++ (contraction off) for the CPU suite.
  *
- * Input: element (r, f, b) is in[r * in_rs + f * in_fs + b * in_bs] (element strides); one of in_fs / in_bs is 1 and the stride
- * of an axis of one element is free: alac_featnorm.h's addressing. n_r = clamp(lengths[r], 0, frames), or frames where lengths
- * is NULL.
+ * Input and output are addressed as alac_featview.h says: three element strides each, one inner stride 1, n_r valid frames in
+ * row r.
  *
  * Parameters, fixed at create: order 0..2, window 1..8 (read only when order > 0), left and right 0..16, stride 1..64,
  * pad_value any float.
@@ -29,7 +28,7 @@
  * A TILE is tile_out consecutive output frames of one row, one workgroup of 256. It needs the input frames [g0 * stride - left -
  * M_order, (g0 + tile_out - 1) * stride + right + M_order] clamped to [0, n_r - 1]: at most tile_in of them. Where one image of
  * all bins would not fit, the workgroup walks the bins in slabs of tile_bins. Per slab: stage_slab brings the frames into image 0
- * (LDS on the device) with alacfn::lines_in along the contiguous axis, at an odd pitch in the bins layout; delta_slab computes
+ * (LDS on the device) with alacfv::lines_in along the contiguous axis, at an odd pitch in the bins layout; delta_slab computes
  * d_1 and d_2 once each into images 1 and 2 of the same geometry; store_slab writes the output along its contiguous axis out of
  * the images: whole lines of D floats in the frames layout, runs of frames per column in the bins layout, 16 bytes at a time in
  * the absolute 16-byte chunks, elements at the ends. tile_out, tile_bins and the LDS size are functions of the parameters alone
@@ -38,12 +37,13 @@
 #ifndef ALAC_STACK_H
 #define ALAC_STACK_H
 
-#include "alac_featnorm.h"
+#include "alac_featview.h"
+
+#include <cmath>
 
 namespace alacst {
 
-using alacfn::F4;
-using alacwf::kThreads;
+using alacfv::F4, alacfv::kThreads, alacfv::length_of, alacfv::lines_in;
 
 constexpr uint32_t kMaxBins = 4096, kMaxCols = 4096;
 constexpr uint32_t kMaxOrder = 2, kMaxWindow = 8, kMaxContext = 16, kMaxStride = 64;
@@ -82,13 +82,6 @@ struct Params {
     float pad_value;
 };
 
-ALAC_WF_FN uint64_t length_of(const Params& p, uint64_t row) {
-    if (!p.lengths) return p.frames;
-    const int32_t n = p.lengths[row];
-    if (n <= 0) return 0u;
-    return (uint64_t)n < p.frames ? (uint64_t)n : p.frames;
-}
-
 /* what a tile works on */
 struct Tile {
     uint64_t row, n; /* the row's valid input frames */
@@ -109,7 +102,7 @@ struct Tile {
 ALAC_WF_FN Tile make_tile(const Params& p, uint64_t row, uint64_t tile) {
     Tile t{};
     t.row = row;
-    t.n = length_of(p, row);
+    t.n = length_of(p.lengths, p.frames, row);
     t.g0 = tile * p.tile_out;
     const uint64_t m = (t.n + p.stride - 1u) / p.stride;
     t.ng = p.out_frames - t.g0 < p.tile_out ? (uint32_t)(p.out_frames - t.g0) : p.tile_out;
@@ -151,10 +144,10 @@ ALAC_WF_FN void stage_slab(const Params& p, const Tile& t, uint32_t b0, float* i
     const uint32_t nb = slab_bins(p, b0);
     const float* x = p.in + t.row * p.in_rs + t.lo * p.in_fs + (uint64_t)b0 * p.in_bs;
     if (p.in_bs == 1u) {
-        if (p.in_fs == p.bins && nb == p.bins) alacfn::lines_in(x, 0u, 1u, t.nfr * nb, image, 0u, 1u, tid);
-        else alacfn::lines_in(x, p.in_fs, t.nfr, nb, image, t.lf, 1u, tid);
+        if (p.in_fs == p.bins && nb == p.bins) lines_in(x, 0u, 1u, t.nfr * nb, image, 0u, 1u, tid);
+        else lines_in(x, p.in_fs, t.nfr, nb, image, t.lf, 1u, tid);
     } else {
-        alacfn::lines_in(x, p.in_bs, nb, t.nfr, image, t.lb, 1u, tid);
+        lines_in(x, p.in_bs, nb, t.nfr, image, t.lb, 1u, tid);
     }
 }
 
@@ -321,35 +314,24 @@ inline uint32_t make_weights(uint32_t order, uint32_t window, float* w, uint32_t
 
 inline uint64_t out_frames_of(const Config& c, uint64_t frames) { return frames / c.stride + (frames % c.stride ? 1u : 0u); }
 
-/* the elements between a tensor's first and one past its last */
-inline uint64_t extent_of(uint64_t rs, uint64_t fs, uint64_t bs, uint64_t rows, uint64_t frames, uint64_t cols) {
-    return (rows - 1u) * rs + (frames - 1u) * fs + (cols - 1u) * bs + 1u;
-}
-
-/* the arguments of one pass (rows, frames >= 1); false for what the entry rejects. The kernel tells a layout by the bin stride:
- * 1 is the frames layout. */
+/* the arguments of one pass (rows, frames >= 1); false for what the entry rejects */
 inline bool make_params(const Config& c, const Plan& pl, const float* in, uint64_t in_rs, uint64_t in_fs, uint64_t in_bs, uint64_t rows,
                         uint64_t frames, const int32_t* lengths, float* out, uint64_t out_rs, uint64_t out_fs, uint64_t out_bs,
                         int32_t* out_lengths, const float* w, Params* p) {
-    if (!in || !out || ((uintptr_t)in & 3u) || ((uintptr_t)out & 3u) || ((uintptr_t)lengths & 3u) || ((uintptr_t)out_lengths & 3u))
-        return false;
+    if (!in || !out || ((uintptr_t)lengths & 3u) || ((uintptr_t)out_lengths & 3u)) return false;
     if (frames > 0x7fffffffu) return false; /* out_lengths is int32 */
     const uint64_t G = out_frames_of(c, frames);
-    const int li = alacfn::layout_of(in_rs, in_fs, in_bs, rows, frames, c.bins);
-    const int lo = alacfn::layout_of(out_rs, out_fs, out_bs, rows, G, pl.cols);
-    if (!li || !lo) return false;
     Params q{};
+    if (!alacfv::strides_of(in, in_rs, in_fs, in_bs, rows, frames, c.bins, &q.in_fs, &q.in_bs) ||
+        !alacfv::strides_of(out, out_rs, out_fs, out_bs, rows, G, pl.cols, &q.out_fs, &q.out_bs))
+        return false;
     q.in = in;
     q.in_rs = in_rs;
-    q.in_fs = li == 2 ? 1u : frames == 1u ? c.bins : in_fs; /* the free stride: the other axis' extent */
-    q.in_bs = li == 1 ? 1u : c.bins == 1u ? frames : in_bs;
     q.out = out;
     q.out_rs = out_rs;
-    q.out_fs = lo == 2 ? 1u : G == 1u ? pl.cols : out_fs;
-    q.out_bs = lo == 1 ? 1u : pl.cols == 1u ? G : out_bs;
     /* the two tensors apart */
-    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + 4u * extent_of(q.in_rs, q.in_fs, q.in_bs, rows, frames, c.bins);
-    const uintptr_t b0 = (uintptr_t)out, b1 = b0 + 4u * extent_of(q.out_rs, q.out_fs, q.out_bs, rows, G, pl.cols);
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + 4u * alacfv::extent_of(q.in_rs, q.in_fs, q.in_bs, rows, frames, c.bins);
+    const uintptr_t b0 = (uintptr_t)out, b1 = b0 + 4u * alacfv::extent_of(q.out_rs, q.out_fs, q.out_bs, rows, G, pl.cols);
     if (a0 < b1 && b0 < a1) return false;
     q.lengths = lengths;
     q.out_lengths = out_lengths;

@@ -36,10 +36,7 @@ struct NormPlan {
     std::vector<float> scale;  // [bins], or empty
 };
 
-// the three element strides of a tensor: element (r, f, b) at base + r * row + f * frame + b * bin; frame or bin is 1
-struct NormStrides {
-    size_t row, frame, bin;
-};
+using NormStrides = FeatureStrides;
 
 class FeatureNorm {
 public:

@@ -43,10 +43,7 @@ struct StackPlan {
     std::vector<float> w2;  // [4 window + 1], or empty
 };
 
-// the three element strides of a tensor: element (r, f, b) at base + r * row + f * frame + b * bin; frame or bin is 1
-struct StackStrides {
-    size_t row, frame, bin;
-};
+using StackStrides = FeatureStrides;
 
 class FrameStack {
 public:

@@ -1,11 +1,19 @@
-// pass_handle.hpp — what the RAII mirrors of the row passes share (resampler.hpp, mel_spectrogram.hpp, kaldi_features.hpp): how a
-// return code becomes an exception, and the owning pointer of a handle. Header-only; nothing here is part of their interface.
+// pass_handle.hpp — what the RAII mirrors of the row passes share (resampler.hpp, mel_spectrogram.hpp, kaldi_features.hpp,
+// feature_norm.hpp, frame_stack.hpp): how a return code becomes an exception and the owning pointer of a handle (alac::detail:
+// no part of their interface), and the strides of a feature tensor, which the last two take. Header-only.
 #pragma once
 
 #include <memory>
 #include <stdexcept>
 
 #include "../../include/alacgpu.h"
+
+namespace alac {
+// the three element strides of a feature tensor: element (r, f, b) at base + r * row + f * frame + b * bin; frame or bin is 1
+struct FeatureStrides {
+    size_t row, frame, bin;
+};
+}  // namespace alac
 
 namespace alac::detail {
 

@@ -68,6 +68,18 @@ def test_compiles_exactly_when_the_output_is_stale(tmp_path):
     assert not build()
 
 
+def test_the_five_pass_mirrors_compile_in_one_translation_unit(tmp_path):
+    """Each shim of tests/host_sim includes one mirror of host/; a caller includes several, and all of them include
+    pass_handle.hpp, so its guard and theirs are seen only here. Each mirror twice."""
+    mirrors = ("resampler", "mel_spectrogram", "kaldi_features", "feature_norm", "frame_stack")
+    src = str(tmp_path / "mirrors.cpp")
+    host = os.path.join(host_build.ROOT, "saprobe-alac_amd", "host")
+    open(src, "w").write("".join('#include "%s.hpp"\n' % os.path.join(host, m) for m in mirrors * 2) +
+                         "#include <type_traits>\n"
+                         "static_assert(std::is_same_v<alac::NormStrides, alac::StackStrides>, \"one struct\");\n")
+    assert host_build.compile(src, str(tmp_path / "mirrors.o"), host_build.SHIM + ["-c"])
+
+
 def test_dependency_files_of_the_real_tree_name_what_the_sources_include():
     from tests import kaldifft_ref
     from tests.test_chunk_pipeline_host import build_chunk_sim
