@@ -823,6 +823,76 @@ typedef struct alacgpu_stack_info {
 } alacgpu_stack_info;
 int alacgpu_stack_plan(const alacgpu_stack* st, alacgpu_stack_info* info, float* weights_out, size_t weights_cap);
 
+/*
+ * SPECAUGMENT: float32 features [rows][frames][bins] with per-row lengths -> a time warp, frequency masks and time masks drawn
+ * inside each row's own n_r frames, one pass on a handle of its own (k_specaug.hip, alac_specaug.h; the
+ * normalisation pass, the stacking pass and every other are untouched). Input and output are addressed as the normalisation
+ * pass's: element (r, f, b) at d + r * row_stride + f * frame_stride + b * bin_stride (elements), one of the two inner strides 1,
+ * the stride of an axis of one element free; n_r = clamp(d_lengths[r], 0, frames), frames where d_lengths is NULL.
+ *     words     Philox4x32-10 with Random123's constants (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ *               0xBB67AE85), key (seed low, seed high). Row r's identity is id = d_ids ? (uint64)d_ids[r] : row_base + r; its word j
+ *               is output word j % 4 of the block at counter (id low, id high, j / 4, 0). A draw from [0, m) is the high 32 bits
+ *               of word * m. A row consumes P = 2 + 2 freq_masks + 2 time_masks words whatever n_r is: an utterance's
+ *               augmentation depends on (seed, id, n_r) only, never on the batch around it
+ *     warp      words 0 and 1; only where warp (W) > 0 and n_r > 2 W: c = W + draw(n_r - 2 W), w = c - W + 1 + draw(2 W); output
+ *               frames [0, w) are the source frames [0, c) resampled linearly, output frames [w, n_r) the source frames [c, n_r),
+ *               each segment on its own; otherwise c = w = 0 and every element is copied
+ *     resample  output frame t of a segment of a source frames and b output frames: num = (2 t + 1) a - b; num <= 0: i0 = 0, lq = 0;
+ *               else i0 = num / (2 b), lq = ((num % (2 b)) << 23) / (2 b) in uint64; i1 = min(i0 + 1, a - 1). Where lq == 0 or
+ *               i1 == i0, y = x[i0], copied and never multiplied; else y = fmaf((float)lq * 0x1p-23f, x[i1] - x[i0], x[i0]): linear
+ *               interpolation with align_corners false, the position an exact rational, the weight floored to 2^-23
+ *     masks     in output coordinates, behind the warp. Frequency mask i (words 2 + 2 i, 3 + 2 i): fw = draw(freq_width + 1),
+ *               f0 = draw(bins - fw + 1), bins [f0, f0 + fw). Time mask i (the 2 time_masks words behind them): cap =
+ *               min(time_width, (n_r * time_ratio_q16) >> 16), tw = draw(cap + 1), t0 = draw(n_r - tw + 1), frames [t0, t0 + tw):
+ *               never outside [0, n_r). An element under any mask is mask_value
+ *     padding   y = pad_value for f >= n_r; the input there is never read, whatever it holds. Lengths do not change
+ * The integer draws are the same on every build, fmaf is correctly rounded and nothing else rounds but one subtraction.
+ * alacgpu_specaug_create is ALACGPU_E_ARG, before any HIP call, for a NULL config, bins outside [1, 4096], freq_masks above 8,
+ * freq_width above bins, time_masks above 16, time_width above 65535, time_ratio_q16 above 65536 or warp above 256. The handle
+ * owns a stream and an event pair; it is single-caller, like a decoder.
+ */
+typedef struct alacgpu_specaug_config {
+    uint32_t bins;           /* 1 .. 4096 */
+    uint32_t freq_masks;     /* 0 .. 8 */
+    uint32_t freq_width;     /* 0 .. bins: a frequency mask is at most this wide */
+    uint32_t time_masks;     /* 0 .. 16 */
+    uint32_t time_width;     /* 0 .. 65535: a time mask is at most this long */
+    uint32_t time_ratio_q16; /* 0 .. 65536: and at most this share of n_r, in 1 / 65536; 65536: time_width alone caps it */
+    uint32_t warp;           /* 0 .. 256: the warp's centre moves by at most this many frames; 0: no warp */
+    float mask_value;
+    float pad_value;
+} alacgpu_specaug_config;
+typedef struct alacgpu_specaug alacgpu_specaug;
+int alacgpu_specaug_create(int device, const alacgpu_specaug_config* config, alacgpu_specaug** out);
+void alacgpu_specaug_destroy(alacgpu_specaug* sa);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernel (valid after a sync). */
+void* alacgpu_specaug_stream(alacgpu_specaug* sa);
+int alacgpu_specaug_synchronize(alacgpu_specaug* sa);
+int alacgpu_specaug_last_ms(alacgpu_specaug* sa, float* ms);
+/*
+ * rows x frames x bins elements of d_in -> the same elements of d_out, which has strides of its own and either layout. Every
+ * element (r, f < frames, b < bins) of the output is written exactly once and nothing else is touched but d_draws: NULL, or int32
+ * [rows][P] on the device, per row the resolved c, w, then (start, width) per mask in word order. d_lengths: int32 [rows] on the
+ * device, or NULL; d_ids: int64 [rows] on the device, or NULL. rows = 0 or frames = 0 succeeds and touches nothing.
+ * ALACGPU_E_ARG before any HIP call: a NULL handle; with work to do a NULL d_in or d_out, a base that is not aligned to its
+ * element (d_ids: 8 bytes), neither inner stride equal to 1, an inner stride below the other axis' extent, a row stride below the
+ * row's extent, frames above 2^31 - 1, sizes whose products overflow, or an output whose span of addresses meets the input's,
+ * with one exception: d_out == d_in with the same three strides on a handle whose warp is 0 runs in place. Asynchronous on the
+ * handle's stream unless sync != 0: the input must be complete, or ordered on that stream, before the call.
+ */
+int alacgpu_specaug_device(alacgpu_specaug* sa, const float* d_in, size_t in_row_stride, size_t in_frame_stride, size_t in_bin_stride,
+                           size_t rows, size_t frames, const int32_t* d_lengths, uint64_t seed, uint64_t row_base, const int64_t* d_ids,
+                           float* d_out, size_t out_row_stride, size_t out_frame_stride, size_t out_bin_stride, int32_t* d_draws,
+                           int sync);
+/* The plan the handle's kernel uses: the parameters, draws = P, and the tile: tile_out output frames of a row (a function of bins
+ * alone) in lds_bytes <= 25 600 of LDS. */
+typedef struct alacgpu_specaug_info {
+    uint32_t bins, freq_masks, freq_width, time_masks, time_width, time_ratio_q16, warp, draws, tile_out, lds_bytes;
+    float mask_value, pad_value;
+} alacgpu_specaug_info;
+int alacgpu_specaug_plan(const alacgpu_specaug* sa, alacgpu_specaug_info* info);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

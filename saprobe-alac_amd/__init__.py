@@ -37,6 +37,7 @@ __all__ = [
     "KaldiFeatures", "NewKaldiFeatures", "kaldi_fbank", "kaldi_mfcc",
     "NormConfig", "FeatureNorm", "NewFeatureNorm", "normalize_features", "kaldi_frame_counts", "load_features",
     "StackConfig", "StackInfo", "FrameStack", "NewFrameStack", "stack_frames", "add_deltas", "lfr",
+    "SpecAugConfig", "SpecAugInfo", "SpecAugment", "NewSpecAugment", "spec_augment",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -323,6 +324,16 @@ _EXPORTS = {
                                             ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                             ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
     "alacgpu_stack_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    "alacgpu_specaug_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_specaug_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_specaug_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_specaug_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_specaug_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_specaug_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_specaug_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -893,7 +904,7 @@ def NewPacketEncoder(config, device=0):
     return PacketEncoder(config, device)
 
 
-# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures, FeatureNorm, FrameStack): what they share
+# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures, FeatureNorm, FrameStack, SpecAugment): what they share (§15a)
 class _RowPass:
     """The handle of a row pass: _h (NULL once closed), _lib and device, and the entries every such handle has. A subclass names
     its C functions one by one (they are irregular: alacgpu_resampler_last_ms, but alacgpu_resample_out_frames), creates the
@@ -998,7 +1009,7 @@ def _cached(cache, key, make):
     return cache[key]
 
 
-# ---- the passes over feature tensors (FeatureNorm, FrameStack): one strided view with per-row lengths ----
+# ---- the passes over feature tensors (FeatureNorm, FrameStack, SpecAugment): one strided view with per-row lengths (§16) ----
 def _feature_strides(t, layout):
     """A tensor [rows, F, bins] (layout frames) or [rows, bins, F] (bins) -> its (row, frame, bin) strides, or None where
     neither inner stride is 1. The stride of an axis of one element is whatever torch keeps there: it is replaced."""
@@ -1836,8 +1847,169 @@ def lfr(feats, lengths=None, m=7, n=6, layout="frames", **kw):
     return stack_frames(feats, lengths, left=left, right=m - 1 - left, stride=n, layout=layout, **kw)
 
 
+# ---- SpecAugment (new: time warp, frequency and time masks inside each row's own frames, between normalisation and stacking) ----
+class SpecAugConfig(ctypes.Structure):
+    """alacgpu_specaug_config (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("bins", "freq_masks", "freq_width", "time_masks", "time_width", "time_ratio_q16",
+                                               "warp")] + [("mask_value", ctypes.c_float), ("pad_value", ctypes.c_float)]
+
+
+class SpecAugInfo(ctypes.Structure):
+    """alacgpu_specaug_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_uint32) for k in ("bins", "freq_masks", "freq_width", "time_masks", "time_width", "time_ratio_q16", "warp",
+                                               "draws", "tile_out", "lds_bytes")] + [("mask_value", ctypes.c_float),
+                                                                                     ("pad_value", ctypes.c_float)]
+
+
+def _specaug_ratio(time_ratio):
+    """time_ratio in [0, 1] -> round(time_ratio * 65536)"""
+    if isinstance(time_ratio, bool) or not isinstance(time_ratio, (int, float)) or not 0.0 <= time_ratio <= 1.0:
+        raise ValueError("time_ratio is a number in [0, 1], not %r" % (time_ratio,))
+    return int(round(time_ratio * 65536))
+
+
+def _specaug_u64(v, name):
+    if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 1 << 64:
+        raise ValueError("%s is an integer in [0, 2^64), not %r" % (name, v))
+    return int(v)
+
+
+class SpecAugment(_FeaturePass):
+    """float32 features with per-row lengths -> SpecAugment on one MI355X (include/alacgpu.h: alacgpu_specaug_*).
+    Per row over its first n = clamp(lengths, 0, frames) frames: a time warp (warp > 0 and n > 2 warp: a centre c in [warp, n - warp)
+    moves to w in [c - warp + 1, c + warp]; the frames before and behind it are resampled linearly, each segment on its own, as
+    ESPnet's time_warp does with bicubic weights), then freq_masks frequency masks of a width drawn from [0, freq_width] and
+    time_masks time masks of a width drawn from [0, min(time_width, time_ratio * n)], all drawn inside the row's own n frames; an
+    element under any mask is mask_value, every frame from n on pad_value, whatever the input holds there. The random words are
+    Philox4x32-10 keyed by `seed` at a counter made of the row's identity (ids[r], or row_base + r), so an utterance's
+    augmentation depends on (seed, identity, n) only: not on its place in the batch, nor on the rows around it. The draws are
+    integer arithmetic and the warp one subtraction and one fused multiply-add per element, so the bits are the same for both
+    layouts. ValueError, before any HIP call, for bins outside [1, 4096], freq_masks outside [0, 8], freq_width outside [0, bins],
+    time_masks outside [0, 16], time_width outside [0, 65535], time_ratio outside [0, 1] or warp outside [0, 256]. Single-caller,
+    bound to one device and one stream. out_frames(F) is F."""
+
+    _CREATE, _DESTROY = "alacgpu_specaug_create", "alacgpu_specaug_destroy"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_specaug_last_ms", "alacgpu_specaug_synchronize"
+
+    def __init__(self, bins, freq_masks=2, freq_width=27, time_masks=2, time_width=100, time_ratio=1.0, warp=0, mask_value=0.0,
+                 pad_value=0.0, device=0):
+        super().__init__()
+        self.bins = _stack_int(bins, "bins", 1, 4096)
+        self.freq_masks, self.freq_width = _stack_int(freq_masks, "freq_masks", 0, 8), _stack_int(freq_width, "freq_width", 0, self.bins)
+        self.time_masks, self.time_width = _stack_int(time_masks, "time_masks", 0, 16), _stack_int(time_width, "time_width", 0, 65535)
+        self.time_ratio_q16, self.warp = _specaug_ratio(time_ratio), _stack_int(warp, "warp", 0, 256)
+        self.draws = 2 + 2 * self.freq_masks + 2 * self.time_masks
+        self.config = SpecAugConfig(self.bins, self.freq_masks, self.freq_width, self.time_masks, self.time_width, self.time_ratio_q16,
+                                    self.warp, float(mask_value), float(pad_value))
+        self._create(device, ctypes.byref(self.config))
+
+    def out_frames(self, in_frames):
+        """in_frames itself: the pass keeps every frame; 0 on a closed handle."""
+        return int(in_frames) if self._h else 0
+
+    def specaug_device(self, d_in, in_strides, rows, frames, d_lengths, seed, d_out, out_strides, row_base=0, d_ids=0, d_draws=0,
+                       sync=True):
+        """alacgpu_specaug_device: raw device pointers (ints; d_lengths, d_ids and d_draws may be 0), in_strides / out_strides the
+        (row, frame, bin) strides in elements, one of the two inner ones 1 in each. Exactly the rows x frames x bins elements of
+        the output and the rows x draws int32 of d_draws are written; the output may not overlap the input, but on a handle
+        without a warp it may be the input itself with the same strides. Runs on the handle's stream, which does not order
+        against torch's: synchronize the input first."""
+        _check(self._lib.alacgpu_specaug_device(self._h, d_in, *[int(s) for s in in_strides], rows, frames, d_lengths or None,
+                                                _specaug_u64(seed, "seed"), _specaug_u64(row_base, "row_base"), d_ids or None, d_out,
+                                                *[int(s) for s in out_strides], d_draws or None, 1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_specaug_plan -> dict: the parameters, draws (the random words and resolved draws of a row), tile_out (the
+        output frames of a tile, a function of bins alone) and lds_bytes."""
+        info = SpecAugInfo()
+        _check(self._lib.alacgpu_specaug_plan(self._h, ctypes.byref(info)))
+        return {k: (float if k.endswith("_value") else int)(getattr(info, k)) for k, _ in SpecAugInfo._fields_}
+
+    def __call__(self, feats, lengths=None, seed=0, ids=None, row_base=0, layout="frames", out=None, out_layout=None,
+                 return_draws=False):
+        """A float32 tensor [..., F, bins] (layout "frames") or [..., bins, F] ("bins") -> the augmented tensor [..., F, bins]
+        (out_layout "frames") or [..., bins, F] ("bins"; default: layout), new and contiguous or `out`. feats is used on its own
+        strides, views such as feats[..., :-1] included, under FeatureNorm's rule; anything else is made contiguous first.
+        lengths: None (every frame is valid) or one integer per row, the count of its valid frames. seed: the step's, a uint64.
+        ids: None, or one int64 per row, the utterance's identity; without it row r of the flattened leading dimensions is
+        row_base + r. out: a float32 tensor of the result's shape on the device that shares no memory with feats, or, on a handle
+        without a warp and with out_layout the layout, feats itself for in place. return_draws: also the resolved draws, int32
+        [..., draws]: c, w, then (start, width) per mask, frequency masks first: what a caller needs to mask targets alike.
+        ValueError for another dtype, a bins dimension that is not the handle's, lengths or ids of another count."""
+        import torch
+        out_layout = layout if out_layout is None else out_layout
+        if layout not in _FBANK_LAYOUTS or out_layout not in _FBANK_LAYOUTS:
+            raise ValueError("layout and out_layout are 'frames' or 'bins', not %r / %r" % (layout, out_layout))
+        seed, row_base = _specaug_u64(seed, "seed"), _specaug_u64(row_base, "row_base")
+        dev, lead, rows, frames = self._features(feats, layout)
+        oshape = lead + ((frames, self.bins) if out_layout == "frames" else (self.bins, frames))
+        same = out is feats
+        if same and (self.warp or out_layout != layout or feats.device != dev):
+            raise ValueError("in place needs a handle without a warp, one layout and feats on the handle's device")
+        if out is not None and not same and (not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or
+                                             tuple(out.shape) != oshape or out.device != dev):
+            raise ValueError("out must be a float32 tensor of shape %r on the handle's device" % (oshape,))
+        x = feats.to(dev)
+        xv, xs = _feature_rows(x, rows, layout)
+        if xv is None:
+            if same:
+                raise ValueError("in place needs a tensor whose rows flatten without a copy and whose frame or bin stride is 1")
+            xv, xs = _feature_rows(x.contiguous(), rows, layout)
+        if same:
+            y, yv, ys = feats, xv, xs
+        else:
+            y = torch.empty(oshape, dtype=torch.float32, device=dev) if out is None else out
+            yv, ys = _feature_rows(y, rows, out_layout)
+            if yv is None:
+                raise ValueError("out needs rows that flatten without a copy and a frame or bin stride of 1")
+        ln = self._lengths(lengths, rows, dev)
+        idv = None
+        if ids is not None:
+            idv = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+            if idv.numel() != rows or idv.dtype.is_floating_point or idv.dtype is torch.bool:
+                raise ValueError("ids holds one integer per row: %d, not %d" % (rows, idv.numel()))
+            idv = idv.to(dev, torch.int64).contiguous().reshape(rows)
+        draws = torch.zeros((rows, self.draws), dtype=torch.int32, device=dev) if return_draws else None
+        if rows and frames:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            self.specaug_device(xv.data_ptr(), xs, rows, frames, 0 if ln is None else ln.data_ptr(), seed, yv.data_ptr(), ys, row_base,
+                                0 if idv is None else idv.data_ptr(), draws.data_ptr() if return_draws else 0, sync=True)
+        return (y, draws.reshape(lead + (self.draws,))) if return_draws else y
+
+
+def NewSpecAugment(bins, freq_masks=2, freq_width=27, time_masks=2, time_width=100, time_ratio=1.0, warp=0, mask_value=0.0,
+                   pad_value=0.0, device=0):
+    """A SpecAugment (context manager); ValueError where no plan can be built."""
+    return SpecAugment(bins, freq_masks, freq_width, time_masks, time_width, time_ratio, warp, mask_value, pad_value, device)
+
+
+_SPECAUGS = {}  # (device, bins, freq_masks, freq_width, time_masks, time_width, time_ratio_q16, warp, mask_value, pad_value) -> SpecAugment
+_NO_SEED = object()
+
+
+def spec_augment(feats, lengths=None, seed=_NO_SEED, ids=None, row_base=0, freq_masks=2, freq_width=27, time_masks=2, time_width=100,
+                 time_ratio=1.0, warp=0, mask_value=0.0, pad_value=0.0, layout="frames", out=None, out_layout=None, return_draws=False,
+                 device=None):
+    """SpecAugment(bins, freq_masks, ...)(feats, lengths, seed, ids, row_base, layout, out, out_layout, return_draws) with the
+    handle of a (device, parameter set) made once and kept: feats a float32 tensor [..., F, bins] (layout "frames") or [..., bins,
+    F] ("bins") on cuda:`device` (default: the tensor's own, cuda:0 for a CPU tensor, which is uploaded). seed is required: a
+    default would give every training step the same masks."""
+    if seed is _NO_SEED:
+        raise ValueError("spec_augment needs a seed: the step's, so that no two steps draw the same masks")
+    bins, device = _feature_input(feats, layout, device)
+    bins = _stack_int(bins, "bins", 1, 4096)
+    key = (device, bins, _stack_int(freq_masks, "freq_masks", 0, 8), _stack_int(freq_width, "freq_width", 0, bins),
+           _stack_int(time_masks, "time_masks", 0, 16), _stack_int(time_width, "time_width", 0, 65535), _specaug_ratio(time_ratio),
+           _stack_int(warp, "warp", 0, 256), np.float32(mask_value).tobytes(), np.float32(pad_value).tobytes())
+    sa = _cached(_SPECAUGS, key, lambda: SpecAugment(bins, freq_masks, freq_width, time_masks, time_width, time_ratio, warp, mask_value,
+                                                     pad_value, device))
+    return sa(feats, lengths, seed, ids, row_base, layout, out, out_layout, return_draws)
+
+
 def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="fbank", norm="mean", channel=0, transform="direct",
-                  device=0, deltas=0, delta_window=2, context=(0, 0), subsample=1, **kaldi_kwargs):
+                  device=0, deltas=0, delta_window=2, context=(0, 0), subsample=1, augment=None, **kaldi_kwargs):
     """Files to normalised features in one call: load_clips(sources, frame_offsets, num_frames, sample_rate=sample_rate) -> the
     channel `channel` -> kaldi_fbank (kind "fbank") or kaldi_mfcc ("mfcc") with kaldi_kwargs (torchaudio's names; frames layout)
     -> kaldi_frame_counts of load_clips' lengths -> FeatureNorm(stat=norm: "mean", "mean_var" or None, which only masks).
@@ -1845,11 +2017,20 @@ def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="f
     themselves, the frames behind them are 0. Nothing but that composition; its two limits are kaldi_frame_counts'.
     With deltas (0..2, delta_window frames each side), context (left, right) or subsample other than their defaults, stack_frames
     runs behind the normalisation, which is Kaldi's order: feats is [B, ceil(F / subsample), (left + right + 1) * (deltas + 1) * D]
-    and frame_lengths its out_lengths. With the defaults that pass is not run."""
+    and frame_lengths its out_lengths. With the defaults that pass is not run.
+    augment: None, or a dict of spec_augment's keywords that must hold `seed` (and may hold ids, row_base, the mask and warp
+    parameters, mask_value): SpecAugment runs between the normalisation and the stacking, so its masks fall on the
+    features' own bins and frames, and behind norm "mean" a mask_value of 0 is the row's mean. With None nothing runs."""
     try:
         left, right = context
     except (TypeError, ValueError):
         raise ValueError("context is (left, right), not %r" % (context,))
+    if augment is not None:
+        if not isinstance(augment, dict) or "seed" not in augment:
+            raise ValueError("augment is a dict of spec_augment's keywords that holds 'seed'")
+        for k in ("feats", "lengths", "layout", "out", "out_layout", "return_draws", "device", "pad_value"):
+            if k in augment:
+                raise ValueError("%s is not a key of augment" % k)
     stacked = (_stack_int(deltas, "deltas", 0, 2), _stack_int(left, "context left", 0, 16), _stack_int(right, "context right", 0, 16),
                _stack_int(subsample, "subsample", 1, 64)) != (0, 0, 0, 1)
     if kind not in ("fbank", "mfcc"):
@@ -1868,6 +2049,8 @@ def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="f
     h = int(rate * kaldi_kwargs.get("frame_shift", 10.0) * 0.001)
     counts = kaldi_frame_counts(lengths, W, h, kaldi_kwargs.get("snip_edges", True))
     feats = normalize_features(feats, counts, stat=norm, out=feats, device=device)
+    if augment is not None:
+        feats = spec_augment(feats, counts, device=device, **augment)
     if stacked:
         feats, counts = stack_frames(feats, counts, order=deltas, window=delta_window, left=left, right=right, stride=subsample,
                                      device=device)

@@ -1,7 +1,7 @@
 /*
  * alac_featview.h — what a pass over a feature tensor needs and nothing of any one pass: a float32 tensor [rows][frames][bins]
- * given by three element strides, with per-row lengths, as plain host + device code (alac_featnorm.h and alac_stack.h stand
- * on it).
+ * given by three element strides, with per-row lengths, as plain host + device code (alac_featnorm.h, alac_stack.h and
+ * alac_specaug.h stand on it).
  *
  * Element (r, f, b) is base[r * rs + f * fs + b * bs] (element strides); exactly one of fs / bs is 1 ("frames" layout: the bins
  * of a frame are contiguous; "bins" layout: the frames of a bin are). The stride of an axis of one element is free: the caller's

@@ -1,9 +1,9 @@
 /*
  * alac_host.h — what the host code of libalacgpu.so shares (alacgpu.hip: the decoder's and the waveform pass's entries;
- * k_enc.hip: the encoder's; k_resample.hip, k_mel.hip, k_melfft.hip, k_fbank.hip, k_fbankfft.hip, k_featnorm.hip and
- * k_stack.hip: the row passes'): the error text behind alacgpu_last_error, the HIP-error macro, the grow-only buffers, the
- * pinned-pointer test, the configuration check, and the skeleton of a row pass: PassHandle and launch_tiles. Host only and
- * private to the library: no kernel header includes it, and nothing in it is exported.
+ * k_enc.hip: the encoder's; k_resample.hip, k_mel.hip, k_melfft.hip, k_fbank.hip, k_fbankfft.hip, k_featnorm.hip,
+ * k_stack.hip and k_specaug.hip: the row passes'): the error text behind alacgpu_last_error, the HIP-error macro, the grow-only
+ * buffers, the pinned-pointer test, the configuration check, and the skeleton of a row pass: PassHandle and launch_tiles. Host
+ * only and private to the library: no kernel header includes it, and nothing in it is exported.
  */
 #ifndef ALAC_HOST_H
 #define ALAC_HOST_H
