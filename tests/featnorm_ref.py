@@ -151,6 +151,10 @@ def view_like(buf, lead, shape, strides):
 
 # ---- the cases -----------------------------------------------------------------------------------------------------------
 BINS = (1, 23, 80, 129)
+# Above 192 bins the kernels run other code: 193 is the first count with tile_frames 32, 257 the first with two finishing blocks
+# (the second holds one bin), 513 and 1025 are spectrograms of n_fft 1024 and 2048, 4096 is the limit (tile_frames 2, SpecAugment's
+# tile_out 1)
+WIDE_BINS = (193, 257, 513, 1025, 4096)
 
 
 def frames_of(tf):

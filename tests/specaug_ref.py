@@ -36,6 +36,7 @@ U = 2.0 ** -24
 IMAGE_FLOATS = 6016  # alacsa::kImageFloats
 M64 = (1 << 64) - 1
 BINS = fr.BINS
+WIDE_BINS = fr.WIDE_BINS
 clamp_lengths, same_bits, lay_out, outside, view_like, features = (fr.clamp_lengths, fr.same_bits, fr.lay_out, fr.outside, fr.view_like,
                                                                    fr.features)
 

@@ -22,6 +22,7 @@ LDS_FLOATS = 6400  # alacst::kLdsFloats
 PARAMS = ((0, 2, 0, 0, 1), (1, 1, 0, 0, 1), (1, 2, 0, 0, 1), (2, 2, 0, 0, 1), (2, 3, 1, 1, 1), (0, 2, 3, 3, 6), (0, 2, 0, 4, 3),
           (0, 2, 5, 0, 2), (2, 2, 3, 3, 6), (1, 8, 16, 16, 64))
 BINS = fr.BINS
+WIDE_BINS = fr.WIDE_BINS
 clamp_lengths, lengths_of, same_bits, lay_out, outside, view_like, features = (
     fr.clamp_lengths, fr.lengths_of, fr.same_bits, fr.lay_out, fr.outside, fr.view_like, fr.features)
 

@@ -3,10 +3,11 @@
 of k_featnorm.hip run, against tests/featnorm_ref.py's numpy restatement bit for bit and against float64 within bounds computed
 from the data.
 
-* every mode of fr.MODES at the bins 1, 23, 80, 129, the frames 1, tile_frames - 1, tile_frames, tile_frames + 1 and 2 *
-  tile_frames + 3, six rows with the lengths 0, 1, a middle value, frames, -5 and frames + 7, in both layouts, which give the
-  same bits;
-* the means and variances against float64 within fr.mean_bound / fr.var_bound (DESIGN.md §16), no free tolerance;
+* every mode of fr.MODES at the bins 1, 23, 80, 129 and at the wide bins 193, 257, 513, 1025, 4096 (fr.WIDE_BINS: tile_frames 32,
+  32, 16, 8 and 2), the frames 1, tile_frames - 1, tile_frames, tile_frames + 1 and 2 * tile_frames + 3, six rows with the lengths
+  0, 1, a middle value, frames, -5 and frames + 7, in both layouts, which give the same bits; nothing is cut at the wide bins;
+* the means and variances against float64 within fr.mean_bound / fr.var_bound, no free tolerance, at the same
+  bins;
 * rows and lines padded apart, every base offset, in place, one layout in and the other out; NaN and Inf in the padding and in
   the gaps; canaries around and between everything that is written;
 * the affine step and the clamp against the plain numpy expressions; what is refused, by the host build, by the library before
@@ -49,9 +50,11 @@ def test_plan_of_every_bin_count(sim):
 
 
 # ---- 2. bit for bit against the numpy restatement, both layouts ----------------------------------------------------------
-@pytest.mark.parametrize("bins", fr.BINS)
+@pytest.mark.parametrize("bins", fr.BINS + fr.WIDE_BINS)
 @pytest.mark.parametrize("mode", list(fr.MODES))
 def test_bits_against_the_reference(sim, mode, bins):
+    """The yardstick of tests/test_gpu_featnorm.py: the host build's output and stats [rows][2][bins] are numpy's, at the wide bins
+    too, where the device runs other tiles and more than one finishing block"""
     tf = fr.tile_frames_of(bins)
     args = fr.mode_args(mode, bins)
     rng = np.random.default_rng(1000 + bins)
@@ -77,7 +80,7 @@ def test_bits_against_the_reference(sim, mode, bins):
 
 
 # ---- 3. against float64 --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bins", fr.BINS)
+@pytest.mark.parametrize("bins", fr.BINS + fr.WIDE_BINS)
 def test_mean_and_variance_within_the_float64_bounds(sim, bins):
     """|m - m64| <= gamma(tile_frames + K) sum|x| / n and the variance's analogue (fr.var_bound), per row and bin, from the data"""
     tf = fr.tile_frames_of(bins)

@@ -6,6 +6,9 @@
   and the affine; for mean_var the mean bit for bit, rstd within 2 float32 ulp (the device's sqrtf is specified to 1 ulp, the
   division rounds once more), and the output bit for bit numpy's (x - mean) * rstd over the device's own stats;
 * gaps between rows and lines, base offsets, one layout in and the other out, in place, NaN / Inf in padding and gaps, canaries;
+* both of these at the wide bins 193, 257, 513, 1025 and 4096 as well (fr.WIDE_BINS), where tile_frames is 32, 32, 16, 8 and 2
+  and the finishing kernel runs 1, 2, 3, 5 and 16 workgroups per row; the statistics of 257 and 4096 bins on their own; the
+  max-clamp of a 513-bin spectrogram view through normalize_features;
 * whisper_post and amplitude_to_DB's clamp against the torch ops, on the strided view logmel[..., :-1];
 * load_features over three synthesised .m4a files of two sample rates, one shorter than the clip, against the pass applied to
   kaldi_fbank of each clip cut to its length;
@@ -111,11 +114,13 @@ def check_against_host(sim, x, lengths, args, y, stats, what):
 
 
 # ---- 1. the CPU suite's cases against the host build ---------------------------------------------------------------------
-@pytest.mark.parametrize("bins", fr.BINS)
+@pytest.mark.parametrize("bins", fr.BINS + fr.WIDE_BINS)
 @pytest.mark.parametrize("mode", list(fr.MODES))
 def test_the_host_cases_on_the_device(torch, pkg, sim, mode, bins):
     tf = fr.tile_frames_of(bins)
     args = fr.mode_args(mode, bins)
+    with new_norm(pkg, bins, **args) as h:
+        assert h.plan()["tile_frames"] == tf and (tf == 64) == (bins <= 192)
     rng = np.random.default_rng(1000 + bins)
     for k, frames in enumerate(fr.frames_of(tf)):
         if frames < 1:
@@ -130,7 +135,7 @@ def test_the_host_cases_on_the_device(torch, pkg, sim, mode, bins):
         assert fr.same_bits(got["frames"][0], got["bins"][0]) and fr.same_bits(got["frames"][1], got["bins"][1]), "the layouts differ"
 
 
-@pytest.mark.parametrize("bins", fr.BINS)
+@pytest.mark.parametrize("bins", fr.BINS + fr.WIDE_BINS)
 @pytest.mark.parametrize("mode", ["mean_var", "whisper", "mean_affine"])
 def test_gaps_offsets_poisoned_padding_and_in_place(torch, pkg, sim, mode, bins):
     tf = fr.tile_frames_of(bins)
@@ -152,7 +157,67 @@ def test_gaps_offsets_poisoned_padding_and_in_place(torch, pkg, sim, mode, bins)
         check_against_host(sim, x, lengths, args, y, stats, "%s in place" % in_layout)
 
 
+@pytest.mark.parametrize("bins", [257, 4096])
+@pytest.mark.parametrize("mode", ["mean_var", "max"])
+def test_statistics_of_more_than_one_finishing_block(torch, pkg, sim, mode, bins):
+    """The returned stats [rows][2][bins] where alac_featnorm_finish runs ceil(bins / 256) > 1 workgroups per row for the sums (at
+    257 bins the second holds one bin) and one per row, which writes all 2 bins values, for the maximum: the host build calls
+    finish_bin per bin and knows no blocks, so this is the only observer of row = b / blocks and bin = (b - row * blocks) * 256 +
+    tid. mean_var: the mean bit for bit, rstd within the 2 ulp of this file (the device's sqrtf and one division), rows without a
+    frame +0.0; max: M in [r][0][0] bit for bit and every other value +0.0."""
+    args = fr.mode_args(mode, bins)
+    with new_norm(pkg, bins, **args) as h:
+        pl = h.plan()
+    tf, blocks = pl["tile_frames"], -(-pl["bins"] // 256)
+    assert tf == fr.tile_frames_of(bins) and blocks >= 2
+    frames = 2 * tf + 3
+    x = fr.features(np.random.default_rng(7000 + bins), ROWS, frames, bins)
+    lengths = fr.lengths_of(frames)
+    valid = np.array(fr.clamp_lengths(lengths, ROWS, frames)) > 0
+    want, want_stats = fr.host_values(sim, x, lengths, "frames", **args)
+    assert want_stats[valid].any(axis=(1, 2)).all() and not want_stats[~valid].view(np.uint32).any()
+    for layout in ("frames", "bins"):
+        y, stats = device_run(torch, pkg, x, lengths, layout, layout, args, row_gap=3, inner_gap=1, lead=1)
+        assert stats.shape == (ROWS, 2, bins)
+        if mode == "max":
+            assert fr.same_bits(stats, want_stats) and fr.same_bits(y, want)
+            assert fr.same_bits(stats[valid, 0, 0], np.array([fr.largest(x[r, :n]) for r, n in
+                                                              enumerate(fr.clamp_lengths(lengths, ROWS, frames)) if n], F32))
+            rest = stats.reshape(ROWS, -1)[:, 1:]
+            assert rest.shape[1] == 2 * bins - 1 and not rest.view(np.uint32).any(), "a value behind the maximum is not +0.0"
+        else:
+            assert fr.same_bits(stats[:, 0], want_stats[:, 0]), "mean"
+            assert not stats[~valid].view(np.uint32).any()
+            assert (ulps(stats[valid, 1], want_stats[valid, 1]) <= 2).all(), "rstd"
+            assert (stats[valid, 1] > 0).all()
+            check_against_host(sim, x, lengths, args, y, stats, "%s, %d bins, %s" % (mode, bins, layout))
+
+
 # ---- 2. against the torch ops --------------------------------------------------------------------------------------------
+def test_max_clamp_of_a_513_bin_spectrogram_view(torch, pkg, sim):
+    """normalize_features on a spectrogram of n_fft 1024 in the bins layout: the view spec[..., :-1] of a [2, 513, F] tensor (bin
+    stride F, F - 1 frames at frame stride 1), stat max, against the host build of the same view, output and statistics; the
+    largest value of row 1 lies in the frame that the view drops"""
+    bins = 513
+    tf = fr.tile_frames_of(bins)
+    F = 2 * tf + 4
+    rng = np.random.default_rng(513)
+    x = rng.uniform(-10.0, 1.5, (2, bins, F)).astype(F32)
+    x[1, 300, F - 1] = 9.0
+    spec = to_dev(torch, x)
+    view = spec[..., :-1]
+    assert view.stride() == (bins * F, F, 1) and tuple(view.shape) == (2, bins, F - 1)
+    before = spec.clone()
+    lengths = [F - 1, tf + 1]
+    logical = np.ascontiguousarray(x[..., :-1].transpose(0, 2, 1))  # [rows, frames, bins]
+    want, want_stats = fr.host_values(sim, logical, lengths, "bins", stat="max", range_=8.0, pad=-1.0)
+    got, stats = pkg.normalize_features(view, lengths, stat="max", layout="bins", range=8.0, pad_value=-1.0, return_stats=True)
+    assert tuple(got.shape) == (2, bins, F - 1) and got.is_contiguous() and torch.equal(spec, before)
+    assert fr.same_bits(got.cpu().numpy().transpose(0, 2, 1), want)
+    assert fr.same_bits(stats.cpu().numpy(), want_stats) and float(stats[1, 0, 0]) < 9.0
+    assert not fr.same_bits(want, logical), "the clamp changed nothing"
+
+
 def test_whisper_post_and_the_db_clamp(torch, pkg):
     """whisper_post(logmel) == FeatureNorm(max, range 8, shift -4, scale 0.25) on the view logmel[..., :-1] (bin stride F, F - 1
     frames), bit for bit; and amplitude_to_DB's clamp at top_db 80 on dB values"""

@@ -5,11 +5,13 @@ and draws:
 
 * the parameter sets of sa.PARAMS at the bins 1, 23, 80, 129 and the frames 1, tile_out, tile_out + 1, 3 tile_out + 5, five rows
   with the lengths 0, 1, 2 W + 1, frames and frames + 9, both layouts in and both out, with gaps between rows and lines, odd base
-  offsets, NaN / Inf in padding and gaps, canaries around the output and the draws;
+  offsets, NaN / Inf in padding and gaps, canaries around the output and the draws; the same at the wide bins 193, 257, 513, 1025
+  and 4096 (sa.WIDE_BINS), where tile_out is 31, 23, 11, 5 and 1 and there are more bins than work items;
 * in place without a warp; a strided view; ids against row_base; spec_augment against the handle, and the cache;
 * load_features with augment over three synthesised .m4a files against the pass applied to load_features without it, and
   augment=None against the chain as it was, byte for byte;
-* the lifecycle of the handle, the C++ mirror.
+* the lifecycle of the handle, the C++ mirror;
+* two rows more than 2^32 elements apart, in and out, and in place.
 
 No test provokes a fault: every refusal happens on the host, and every buffer has the size the entry asks for."""
 import ctypes
@@ -25,6 +27,7 @@ F32 = np.float32
 CANARY = F32(-12345.5)
 SEED = 0x1234_5678_9ABC_DEF1
 CASES = [(name, bins) for name in sa.PARAMS for bins in sa.BINS]
+CASES += [(name, bins) for bins in sa.WIDE_BINS for name in sa.PARAMS]  # tile_out 31, 23, 11, 5 and 1
 IDS = ["%s-%d" % c for c in CASES]
 
 
@@ -271,3 +274,55 @@ def test_lifecycle_and_the_cpp_mirror(torch, pkg, sim):
     assert (info.mask_value, info.pad_value, info.warp) == (2.5, -1.0, 2)
     assert sa.same_bits(d_y.cpu().numpy(), want) and np.array_equal(d_draws.cpu().numpy(), want_draws)
     assert run(good + (70 * 23, 22, 1)) == -6 and b"stride" in S.specaug_shim_last_error()
+
+
+# ---- 5. far rows ---------------------------------------------------------------------------------------------------------
+def test_rows_more_than_4_gi_elements_apart(torch, pkg, sim):
+    """Two rows whose row stride is 2^32 + 12 345 elements, in the input and in the output, each in one allocation of 16 GiB that
+    is touched only around the rows: a row offset narrowed to 32 bits would read and write row 1 at element 12 345, which holds
+    canaries. The warp reads two source frames per output frame through the row's offset. Then masks only, in place on the input"""
+    bins = 23
+    ps, masks = sa.for_bins(sa.PARAMS["all"], bins), sa.for_bins(sa.PARAMS["masks"], bins)
+    rs, guard = (1 << 32) + 12345, 4096
+    with new_specaug(pkg, ps, bins, -7.0, -2.0) as h:
+        frames = h.plan()["tile_out"] + 1
+    ext = frames * bins
+    try:
+        big_in = torch.empty(rs + ext + guard, dtype=torch.float32, device="cuda:0")
+        big_out = torch.empty(rs + ext + guard, dtype=torch.float32, device="cuda:0")
+    except RuntimeError as e:
+        pytest.skip("no two allocations of %.1f GiB: %s" % ((rs + ext + guard) * 4 / 2.0 ** 30, str(e).splitlines()[0]))
+    x = sa.features(np.random.default_rng(4), 2, frames, bins)
+    lengths = [frames - 3, frames]
+    for big in (big_in, big_out):
+        big[:12345 + ext + guard] = float(CANARY)
+        big[rs - guard:rs + ext + guard] = float(CANARY)
+    big_in[:ext] = to_dev(torch, x[0].reshape(-1))
+    big_in[rs:rs + ext] = to_dev(torch, x[1].reshape(-1))
+    rows_in = torch.as_strided(big_in, (2, frames, bins), (rs, bins, 1))
+    rows_out = torch.as_strided(big_out, (2, frames, bins), (rs, bins, 1))
+
+    def rows_of(big):
+        return np.stack([big[:ext].cpu().numpy(), big[rs:rs + ext].cpu().numpy()]).reshape(2, frames, bins)
+
+    def guards_intact(big):
+        return all(bool((big[a:b] == float(CANARY)).all()) for a, b in ((ext, 12345 + ext + guard), (rs - guard, rs),
+                                                                        (rs + ext, rs + ext + guard)))
+
+    with new_specaug(pkg, ps, bins, -7.0, -2.0) as h:
+        out, draws = h(rows_in, lengths, SEED, row_base=5, out=rows_out, return_draws=True)
+    assert out is rows_out
+    want, want_draws = sa.host_values(sim, x, lengths, ps, SEED, row_base=5, mask_value=-7.0, pad_value=-2.0)
+    assert (want_draws[:, 1] > 0).all(), "both rows are warped"
+    assert sa.same_bits(rows_of(big_out), want) and np.array_equal(draws.cpu().numpy(), want_draws)
+    assert guards_intact(big_out), "an element outside the two rows was written"
+    assert sa.same_bits(rows_of(big_in), x) and guards_intact(big_in), "the input changed"
+    # masks only, in place on the input view
+    with new_specaug(pkg, masks, bins, -7.0, -2.0) as h:
+        out, draws = h(rows_in, lengths, SEED, row_base=5, out=rows_in, return_draws=True)
+    assert out is rows_in
+    want, want_draws = sa.host_values(sim, x, lengths, masks, SEED, row_base=5, mask_value=-7.0, pad_value=-2.0)
+    assert sa.same_bits(rows_of(big_in), want) and np.array_equal(draws.cpu().numpy(), want_draws) and not sa.same_bits(want, x)
+    assert guards_intact(big_in), "an element outside the two rows was written"
+    del big_in, big_out, rows_in, rows_out, out
+    torch.cuda.empty_cache()

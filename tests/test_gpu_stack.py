@@ -4,7 +4,8 @@ logarithm in this pass and fmaf is correctly rounded on both sides, so every com
 
 * the CPU suite's cases (sr.PARAMS at the bins 1, 23, 80, 129 and the slab case, five frame counts around tile_in, six rows with
   the lengths 0, 1, a middle value, frames, -5 and frames + 7, both layouts in and both out) with gaps between rows and lines,
-  base offsets, NaN / Inf in padding and gaps, canaries around the output and the out lengths;
+  base offsets, NaN / Inf in padding and gaps, canaries around the output and the out lengths; the same at the wide bins 193, 257,
+  513, 1025 and 4096 (sr.WIDE_BINS) with every parameter set that create takes there;
 * strided views through FrameStack's __call__; lfr, add_deltas and stack_frames against FrameStack; the cache;
 * load_features with deltas, and with context and subsampling, over three synthesised .m4a files against the pass applied to each
   clip cut to its own frame count; with the defaults against normalize_features of the same chain;
@@ -26,6 +27,7 @@ ROWS = 6
 CANARY = F32(-12345.5)
 SLABS = (2, 8, 0, 0, 1)
 CASES = [(ps, bins) for ps in sr.PARAMS for bins in sr.BINS if sr.accepted(ps, bins)] + [(SLABS, 700)]
+CASES += [(ps, bins) for bins in sr.WIDE_BINS for ps in sr.PARAMS if sr.accepted(ps, bins)]  # at 4096 bins the plain copy alone
 IDS = ["%s-%d" % (sr.param_id(ps), bins) for ps, bins in CASES]
 
 

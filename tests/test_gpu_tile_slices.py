@@ -1,24 +1,31 @@
-"""The second launch of the seven tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
+"""The second launch of the twelve tile passes that go in slices of 2^22 workgroups: alac_resample_rows (k_resample.hip),
 alac_clips_gather (k_clips.hip), alac_wave_convert (k_wave.hip), alac_wave_pack (k_wavepack.hip), alac_mel_rows (k_mel.hip),
-alac_melfft_rows (k_melfft.hip) and alac_fbank_rows (k_fbank.hip). Each launch gets the slice's
+alac_melfft_rows (k_melfft.hip), alac_fbank_rows (k_fbank.hip), alac_featnorm_partials, alac_featnorm_finish and
+alac_featnorm_apply (k_featnorm.hip), alac_stack (k_stack.hip) and alac_specaug (k_specaug.hip). Each launch gets the slice's
 first tile as first_tile; only a batch of more than 2^22 tiles has a second slice, and a launch that lost its first_tile would
 corrupt such batches alone, silently.
 
-Every test runs N = 2^22 + 4 099 items of one tile each, so the second launch starts at first_tile = 2^22 and has 4 099
+Every test but one runs N = 2^22 + 4 099 items of one tile each, so the second launch starts at first_tile = 2^22 and has 4 099
 workgroups. The items' content cycles with period 7 (the clips' with 35), and 2^22 = 2 mod 7 (9 mod 35): a slice that
 started at item 0 again, or that read its inputs from the batch's start, would not continue the cycle. The expectation is that
 of the 7 (35) items, from the host build or the numpy restatement, repeated; it is compared on the device, and the sentinels in
-front of and behind the tensor must be intact. The largest test holds about 150 MB of device memory.
+front of and behind the tensor must be intact. The feature passes read lengths[row] and ids[row] and write stats[row],
+out_lengths[row] and draws[row] beside their output: those arrays cycle too and are held to the same comparison, with sentinels of
+their own. The tests hold between 150 and 550 MB of device memory; the one that slices the finishing launch alone (two
+workgroups per row of 257 bins) holds about 11 GB and skips where that is not to be had.
 
 No test provokes a fault: every pass gets buffers of the sizes its entry asks for."""
 import numpy as np
 import pytest
 
 from tests import clip_ref as cr
+from tests import featnorm_ref as nr
 from tests import kaldi_ref as kr
 from tests import mel_ref as mr
 from tests import melfft_ref as fr
 from tests import resample_ref as rr
+from tests import specaug_ref as sa
+from tests import stack_ref as sr
 from tests import wave_ref as wr
 from tests import wavepack_ref as pr
 
@@ -272,3 +279,182 @@ def test_second_launch_of_alac_fbank_rows(torch, pkg):
         kf.features_device(x.data_ptr(), T, N, T, buf.data_ptr() + 4 * LEAD, cols, cols, sync=True)
     assert_cycle(torch, buf[LEAD:LEAD + N * cols], np.ascontiguousarray(want7).view(np.int32), "rows")
     assert_guards(buf, N * cols, fill)
+
+
+# ---- the feature passes: per-row side arrays beside the output -----------------------------------------------------------
+FILL = -0x21524111  # the sentinel of the feature passes' tensors, as int32; 0xDEADBEEF as bits
+
+
+def assert_classes(rows7, shift, empty):
+    """rows7: each class's whole expectation (output and per-row results) as bytes. The seven are pairwise distinct, but for the
+    classes in `empty`: rows without a valid frame (a length of 0 and a negative one, which the cycle must hold both) come out as
+    padding and zeros whatever they held, so those agree with each other and with nothing else. And class k differs from class
+    k + shift, so a slice that began `shift` items late in the cycle would differ in every row."""
+    assert len(rows7) == 7
+    for i in range(7):
+        for j in range(i + 1, 7):
+            assert (rows7[i] == rows7[j]) == (i in empty and j in empty), "classes %d and %d" % (i, j)
+        assert rows7[i] != rows7[(i + shift) % 7], "class %d and the one %d on" % (i, shift)
+
+
+def featnorm_slices(torch, pkg, rows, bins, frames, lengths7, empty, sliced, **mode):
+    """`rows` rows of [frames, bins] whose content and length are those of class row % 7 through one normalisation pass with the
+    statistics requested; output and statistics against the host build's 7 rows as cycles, sentinels around both.
+    sliced(chunks, blocks) -> the workgroups per row of each launch that is to go in two slices, read from the handle's plan: they
+    agree, so those launches' second slices begin at the same row."""
+    sim = nr.build_featnorm_sim()
+    x7 = nr.features(np.random.default_rng(70 + bins), 7, frames, bins)
+    want7, stats7 = nr.host_values(sim, x7, lengths7, "frames", **mode)
+    per_row = frames * bins
+    try:
+        x = cycled(torch, x7.reshape(7, per_row), rows)
+        d_len = cycled(torch, np.asarray(lengths7, np.int32)[:, None], rows).flatten()
+        out = sentinel_buffer(torch, rows * per_row, FILL, torch.int32)
+        stats = sentinel_buffer(torch, rows * 2 * bins, FILL, torch.int32)
+    except RuntimeError as e:
+        pytest.skip("no %.1f GiB in four allocations for %d rows of %d bins: %s" % (rows * (2 * per_row + 2 * bins) * 4 / 2.0 ** 30, rows,
+                                                                                   bins, str(e).splitlines()[0]))
+    torch.cuda.synchronize()
+    with pkg.NewFeatureNorm(bins, mode["stat"], None, None, 1e-20, mode.get("range_"), mode["pad"]) as h:
+        pl = h.plan()
+        per = set(sliced(-(-frames // pl["tile_frames"]), -(-pl["bins"] // 256)))
+        assert len(per) == 1, "the launches under test do not share their tiles"
+        per = per.pop()
+        assert rows * per > SLICE and SLICE % per == 0, "the launches under test have no second slice"
+        assert_classes([want7[k].tobytes() + stats7[k].tobytes() for k in range(7)], (SLICE // per) % 7, empty)
+        h.norm_device(x.data_ptr(), (per_row, bins, 1), rows, frames, d_len.data_ptr(), out.data_ptr() + 4 * LEAD, (per_row, bins, 1),
+                      stats.data_ptr() + 4 * LEAD, sync=True)
+    assert_cycle(torch, out[LEAD:LEAD + rows * per_row], want7.view(np.int32), "output")
+    assert_guards(out, rows * per_row, FILL)
+    assert_cycle(torch, stats[LEAD:LEAD + rows * 2 * bins], stats7.view(np.int32), "stats")
+    assert_guards(stats, rows * 2 * bins, FILL)
+
+
+def test_second_launch_of_the_featnorm_sums(torch, pkg):
+    """stat mean_var over N rows of 2 frames x 3 bins: chunks = 1 and one finishing block per row, so alac_featnorm_partials (twice),
+    alac_featnorm_finish (twice) and alac_featnorm_apply all have tile = row and a second launch at first_tile = 2^22. Row r has the
+    content and the length of class r % 7; the lengths are 2, 1, 0, -4, 5, 2, 1: classes 2 and 3 hold no valid frame.
+
+    A launch that ignored first_tile would leave partial[], stats[] or the output of the rows from 2^22 on as they were (the
+    sentinel, or the scratch block's old content); one that narrowed (row * chunks + chunk) * bins or row * 2 * bins would write
+    them elsewhere; one that read lengths[], the partials or the statistics from the batch's start would give row 2^22 + j the
+    mean, rstd or length of row j, whose class j % 7 is not (2^22 + j) % 7."""
+    featnorm_slices(torch, pkg, N, 3, 2, [2, 1, 0, -4, 5, 2, 1], (2, 3), lambda chunks, blocks: (chunks, blocks, chunks),
+                    stat="mean_var", pad=-2.0)
+
+
+def test_second_launch_of_the_featnorm_maximum(torch, pkg):
+    """The same with stat max, range 1: the kLargest branch of alac_featnorm_partials (partial[row * chunks + chunk]), the
+    one-workgroup-per-row branch of alac_featnorm_finish, which writes all 2 x bins statistics of its row, and the clamp of
+    alac_featnorm_apply, which reads stats[row][0][0]."""
+    featnorm_slices(torch, pkg, N, 3, 2, [2, 1, 0, -4, 5, 2, 1], (2, 3), lambda chunks, blocks: (chunks, 1, chunks),
+                    stat="max", range_=1.0, pad=-2.0)
+
+
+def test_second_launch_of_alac_featnorm_finish_with_two_blocks_per_row(torch, pkg):
+    """R = 2^21 + 2 053 rows of 1 frame x 257 bins, stat mean_var: the finishing launches have two workgroups per row, 2 R > 2^22 in
+    all, and are the only ones that go in two slices here. The second starts at first_tile = 2^22 = row 2^21 (= 1 mod 7), block 0,
+    behind row 2^21 - 1's block 1, which holds bin 256 alone. With one frame the mean is the value itself, so stats[r][0] is row
+    r's input and stats[r][1] the floor's rstd; the lengths are 1, 1, 7, 0, 1, -2, 1: classes 3 and 5 hold no valid frame.
+
+    A launch that took b for the row, or lost first_tile, would write the means of the rows from 2^21 on to other rows or not at
+    all. About 2 GB each for input, output and the handle's partial sums and 4 GB for the statistics; skipped where the test's own
+    four tensors cannot be allocated."""
+    R = (1 << 21) + 2053
+    featnorm_slices(torch, pkg, R, 257, 1, [1, 1, 7, 0, 1, -2, 1], (3, 5), lambda chunks, blocks: (blocks,), stat="mean_var", pad=-2.0)
+
+
+def test_second_launch_of_alac_stack(torch, pkg):
+    """N rows of 3 frames x 2 bins, order 1 at window 1, one frame of left context, stride 1: 3 output frames of 8 columns, one tile
+    per row, so tile = row and the second launch has first_tile = 2^22. Row r has the content and the length of class r % 7; the
+    lengths are 3, 1, 0, -4, 5, 2, 3, and the out lengths are requested.
+
+    A launch that ignored first_tile would leave the output and out_lengths[] of the rows from 2^22 on unwritten (the sentinel);
+    one that read the input or lengths[] from the batch's start would give row 2^22 + j the deltas or the length of row j,
+    whose class j % 7 is not (2^22 + j) % 7."""
+    sim = sr.build_stack_sim()
+    ps, bins, frames = (1, 1, 1, 0, 1), 2, 3
+    lengths7 = [3, 1, 0, -4, 5, 2, 3]
+    x7 = sr.features(np.random.default_rng(71), 7, frames, bins)
+    want7, len7 = sr.host_values(sim, x7, lengths7, ps, pad=-2.0)
+    G, D = want7.shape[1:]
+    x = cycled(torch, x7.reshape(7, frames * bins), N)
+    d_len = cycled(torch, np.asarray(lengths7, np.int32)[:, None], N).flatten()
+    out = sentinel_buffer(torch, N * G * D, FILL, torch.int32)
+    olen = sentinel_buffer(torch, N, FILL, torch.int32)
+    torch.cuda.synchronize()
+    with pkg.NewFrameStack(bins, *ps, -2.0) as h:
+        pl = h.plan()
+        per = -(-h.out_frames(frames) // pl["tile_out"])  # the slabs of tile_bins bins are a loop inside the workgroup
+        assert (G, D) == (h.out_frames(frames), pl["columns"]) == (3, 8) and per == 1 and N * per > SLICE
+        assert_classes([want7[k].tobytes() + len7[k].tobytes() for k in range(7)], SLICE % 7, (2, 3))
+        h.stack_device(x.data_ptr(), (frames * bins, bins, 1), N, frames, d_len.data_ptr(), out.data_ptr() + 4 * LEAD, (G * D, D, 1),
+                       olen.data_ptr() + 4 * LEAD, sync=True)
+    assert_cycle(torch, out[LEAD:LEAD + N * G * D], want7.view(np.int32), "output")
+    assert_guards(out, N * G * D, FILL)
+    assert_cycle(torch, olen[LEAD:LEAD + N], len7.view(np.int32), "out lengths")
+    assert_guards(olen, N, FILL)
+
+
+def test_second_launch_of_alac_specaug(torch, pkg):
+    """N rows of 4 frames x 2 bins, one frequency mask of at most 1 bin, one time mask of at most 2 frames, a warp of 1: tile_out
+    64, so tile = row and the second launch has first_tile = 2^22. Row r has the content and the length of class r % 7; the
+    lengths are -3, 0, 1, 2, 3, 4, 13, so rows 4, 5 and 6 of a cycle are warped and the others are not.
+
+    Pass 1: ids[r] = 1000 + r % 7 on the device, so the draws cycle too; output and draws against the host build's 7 rows. A
+    launch that ignored first_tile would leave the output and draws[] of the rows from 2^22 on unwritten; one that read the
+    input, lengths[] or ids[] from the batch's start would give row 2^22 + j the draws and frames of row j.
+
+    Pass 2: no ids and row_base = 2^32 - 2^22 - 1, so row 2^22 has the identity 2^32 - 1 and row 2^22 + 1 the identity 2^32: the
+    counter's low word wraps into its high word one row into the second slice. The draws and the output of the rows 0, 2^22 - 1,
+    2^22, 2^22 + 1 and N - 1 against specaug_ref.draws_of and the host build run with those identities as ids: a row number
+    narrowed to 32 bits, or a low word that did not carry, would draw other masks."""
+    sim = sa.build_specaug_sim()
+    ps, bins, frames, seed = (1, 1, 1, 2, 65536, 1), 2, 4, 25
+    lengths7 = [-3, 0, 1, 2, 3, 4, 13]
+    ids7 = [1000 + k for k in range(7)]
+    x7 = sa.features(np.random.default_rng(72), 7, frames, bins)
+    want7, draws7 = sa.host_values(sim, x7, lengths7, ps, seed, ids=ids7, mask_value=-7.0, pad_value=-2.0)
+    P = draws7.shape[1]
+    assert [bool(d[1]) for d in draws7] == [False, False, False, False, True, True, True], "which classes are warped"
+    per_row = frames * bins
+    x = cycled(torch, x7.reshape(7, per_row), N)
+    d_len = cycled(torch, np.asarray(lengths7, np.int32)[:, None], N).flatten()
+    d_ids = 1000 + torch.arange(N, dtype=torch.int64, device="cuda:0") % 7
+    out = sentinel_buffer(torch, N * per_row, FILL, torch.int32)
+    draws = sentinel_buffer(torch, N * P, FILL, torch.int32)
+    torch.cuda.synchronize()
+    with pkg.NewSpecAugment(bins, ps[0], ps[1], ps[2], ps[3], ps[4] / 65536.0, ps[5], -7.0, -2.0) as h:
+        pl = h.plan()
+        per = -(-frames // pl["tile_out"])
+        assert pl["draws"] == P == 6 and per == 1 and N * per > SLICE
+        assert_classes([want7[k].tobytes() + draws7[k].tobytes() for k in range(7)], SLICE % 7, ())
+        run = lambda row_base, ids: h.specaug_device(x.data_ptr(), (per_row, bins, 1), N, frames, d_len.data_ptr(), seed,
+                                                     out.data_ptr() + 4 * LEAD, (per_row, bins, 1), row_base, ids,
+                                                     draws.data_ptr() + 4 * LEAD, sync=True)
+        run(0, d_ids.data_ptr())
+        assert_cycle(torch, out[LEAD:LEAD + N * per_row], want7.view(np.int32), "output")
+        assert_guards(out, N * per_row, FILL)
+        assert_cycle(torch, draws[LEAD:LEAD + N * P], draws7, "draws")
+        assert_guards(draws, N * P, FILL)
+        out.fill_(FILL)
+        draws.fill_(FILL)
+        torch.cuda.synchronize()
+        base = (1 << 32) - SLICE - 1
+        run(base, 0)
+    assert_guards(out, N * per_row, FILL)
+    assert_guards(draws, N * P, FILL)
+    spots = [0, SLICE - 1, SLICE, SLICE + 1, N - 1]
+    idents = [base + r for r in spots]
+    assert idents[2] == (1 << 32) - 1 and idents[3] == 1 << 32
+    cls = [r % 7 for r in spots]
+    want, want_draws = sa.host_values(sim, x7[cls], [lengths7[k] for k in cls], ps, seed, ids=idents, mask_value=-7.0, pad_value=-2.0)
+    for j, r in enumerate(spots):
+        n = min(max(lengths7[cls[j]], 0), frames)
+        assert want_draws[j].tolist() == sa.draws_of(ps, bins, n, seed, idents[j])
+        got_draws = draws[LEAD + r * P:LEAD + (r + 1) * P].cpu().numpy()
+        assert np.array_equal(got_draws, want_draws[j]), "row %d (identity %d): draws %s, not %s" % (r, idents[j], got_draws, want_draws[j])
+        got = out[LEAD + r * per_row:LEAD + (r + 1) * per_row].cpu().numpy()
+        assert np.array_equal(got, want[j].reshape(-1).view(np.int32)), "row %d (identity %d): output" % (r, idents[j])
+    assert not bool((out[LEAD:LEAD + N * per_row] == FILL).any()) and not bool((draws[LEAD:LEAD + N * P] == FILL).any()), "a row was left unwritten"
+    assert len({tuple(d) for d in want_draws.tolist()}) > 1

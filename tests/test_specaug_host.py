@@ -6,7 +6,9 @@ computed from the data.
 * Philox4x32-10's two known answers, from the host build and from numpy;
 * the parameter sets of sa.PARAMS (nothing, masks only, a warp only, everything, the maxima) at the bins 1, 23, 80, 129, the frames
   1, 2, tile_out - 1, tile_out, tile_out + 1 and 3 tile_out + 5, seven rows with the lengths -3, 0, 1, 2 W, 2 W + 1, frames and
-  frames + 9, both layouts in and both out; the maxima also at 530 frames, where a warp of 256 takes effect;
+  frames + 9, both layouts in and both out; the maxima also at 530 frames, where a warp of 256 takes effect; the same at the wide
+  bins 193, 257, 513, 1025 and 4096 (sa.WIDE_BINS), where the masked bins fill up to 128 words and the tile shrinks to one
+  frame;
 * rows and lines padded apart, every base offset, NaN and Inf in all padding and gaps, canaries around the output and the draws;
 * the properties: nothing in, the input's bits out; a row alone is the row in its batch; every draw in its range; every width
   occurs; the padding is never read; a row of at most 2 W frames is not warped;
@@ -26,6 +28,7 @@ F32 = np.float32
 CANARY = F32(-12345.5)
 SEED = 0x1234_5678_9ABC_DEF1
 CASES = [(name, bins) for name in sa.PARAMS for bins in sa.BINS]
+CASES += [(name, bins) for bins in sa.WIDE_BINS for name in sa.PARAMS]  # tile_out 31, 23, 11, 5 and 1; nothing is cut there
 IDS = ["%s-%d" % c for c in CASES]
 KW = dict(mask_value=-7.0, pad_value=-3.5)
 
@@ -223,7 +226,7 @@ def test_warp_against_float64_interpolation(sim):
     import torch
     rng = np.random.default_rng(7)
     worst = 0.0
-    for bins, frames, W in ((23, 200, 5), (80, 130, 40), (1, 600, 256), (129, 91, 1)):
+    for bins, frames, W in ((23, 200, 5), (80, 130, 40), (1, 600, 256), (129, 91, 1), (513, 40, 5), (4096, 13, 2)):
         ps = (0, 0, 0, 0, 65536, W)
         rows = 8
         x = rng.normal(0.0, 1.0, (rows, frames, bins)).astype(F32)

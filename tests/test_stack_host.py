@@ -7,7 +7,8 @@ apply_lfr, splice-feats and subsample-feats by index lists) and against float64 
   3 of the plan's own input span, six rows with the lengths 0, 1, a middle value, frames, -5 and frames + 7, both layouts in and
   both out, which give the same bits; a row alone gives what it gives in the batch. (1, 8, 16, 16, 64) has 66 columns per bin: at
   80 and 129 bins it is more than 4096 columns, which create refuses, and that refusal is what is checked there. One more set,
-  order 2 at window 8 over 700 bins, is the one whose bins go through the tile in slabs;
+  order 2 at window 8 over 700 bins, is the one whose bins go through the tile in slabs; and at the wide bins 193, 257, 513, 1025
+  and 4096 (sr.WIDE_BINS) every set that create takes there, with nothing cut: at 4096 bins the plain copy alone remains;
 * rows and lines padded apart, every base offset, NaN and Inf in all padding and gaps, canaries around and between everything
   written;
 * the plan, the weight tables, what is refused (by the host build, by the library before any HIP call, by the Python class and by
@@ -27,7 +28,10 @@ ROWS = 6
 CANARY = F32(-12345.5)
 SLABS = (2, 8, 0, 0, 1)  # at 700 bins: tile_bins 44
 CASES = [(ps, bins) for ps in sr.PARAMS for bins in sr.BINS] + [(SLABS, 700)]
+# the wide bins: every parameter set that create takes there (at most 4096 columns); at 4096 bins that is the plain copy alone
+WIDE = [(ps, bins) for bins in sr.WIDE_BINS for ps in sr.PARAMS if sr.accepted(ps, bins)]
 IDS = ["%s-%d" % (sr.param_id(ps), bins) for ps, bins in CASES]
+WIDE_IDS = ["%s-%d" % (sr.param_id(ps), bins) for ps, bins in WIDE]
 
 
 @pytest.fixture(scope="module")
@@ -39,7 +43,7 @@ def sim():
 def test_plan_of_every_case_and_of_lfr_at_every_bin_count(sim):
     """tile_out in [1, 64], the largest whose images fit; tile_in its input span; the LDS within 25 600 bytes; all bins in one slab
     wherever one output frame's images fit"""
-    cases = [c for c in CASES if sr.accepted(*c)] + [((0, 2, 3, 3, 6), bins) for bins in range(1, 301)]
+    cases = [c for c in CASES if sr.accepted(*c)] + WIDE + [((0, 2, 3, 3, 6), bins) for bins in range(1, 301)]
     cases += [((2, 8, 16, 16, 1), 41), ((2, 8, 0, 0, 1), 1365), ((0, 1, 0, 0, 64), 4096), ((1, 8, 0, 0, 1), 2048)]
     for ps, bins in cases:
         order, window, left, right, stride = ps
@@ -76,8 +80,10 @@ def test_weight_tables_are_exact(sim):
 
 
 # ---- 2. bit for bit against the numpy restatement, both layouts in and out -----------------------------------------------
-@pytest.mark.parametrize("ps,bins", CASES, ids=IDS)
+@pytest.mark.parametrize("ps,bins", CASES + WIDE, ids=IDS + WIDE_IDS)
 def test_bits_against_the_reference(sim, ps, bins):
+    """The yardstick of tests/test_gpu_stack.py: the host build's output and out lengths are numpy's, at the wide bins too, with the
+    plan's own frame counts, both layouts in and out and the same six lengths; nothing is cut there"""
     if not sr.accepted(ps, bins):
         assert sr.columns_of(ps, bins) > 4096 and sr.sim_plan(sim, ps, bins)[0] == -2
         x, y = np.zeros(bins, F32), np.full(sr.columns_of(ps, bins), CANARY, F32)
@@ -165,12 +171,13 @@ def within_the_bound(y, v, ps, other64=None):
     return float((err[lim > 0] / lim[lim > 0]).max()) if (lim > 0).any() else 0.0
 
 
-@pytest.mark.parametrize("bins", sr.BINS)
+@pytest.mark.parametrize("bins", sr.BINS + sr.WIDE_BINS[:-1])
 def test_deltas_against_kaldi_conv1d_and_float64(sim, bins):
+    """The bound is the same at every bin count. 4096 bins are left out: no parameter set with deltas has at most 4096 columns there"""
     import torch
     rng = np.random.default_rng(2000 + bins)
     worst = 0.0
-    for ps in [p for p in sr.PARAMS if p[0] > 0 and sr.accepted(p, bins)] + [(2, 8, 0, 0, 1), (1, 4, 0, 0, 1)]:
+    for ps in [p for p in sr.PARAMS + ((2, 8, 0, 0, 1), (1, 4, 0, 0, 1)) if p[0] > 0 and sr.accepted(p, bins)]:
         order, window = ps[:2]
         frames = sr.plan_of(ps, bins)["tile_in"] + 1
         x = sr.features(rng, ROWS, frames, bins)
