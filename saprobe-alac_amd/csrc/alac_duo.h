@@ -14,7 +14,7 @@
  *                        shift-byte merge, PCM packing and the LDS stager: many short independent chains.
  *
  * The two waves of a workgroup hold the SAME 64 packets (lane = packet in both). Residuals go A -> B through a
- * double-buffered LDS queue of DUO_CHUNK steps x 64 lanes; one s_barrier per chunk is the only synchronisation.
+ * double-buffered LDS queue of DUO_CHUNK steps (16; 32 in k_dec16l.hip) x 64 lanes; one s_barrier per chunk is the only synchronisation.
  * Iteration c: A writes R[c & 1], B reads R[(c-1) & 1]; the barrier at the end of the iteration publishes the
  * chunk. U of a pair still goes through the HBM hand-off tile (B stores it in the U phase and loads it in the V
  * phase): V's first bit is known only when U is fully parsed. Status and frame count come from A (it sees the
@@ -39,7 +39,13 @@ namespace alac {
 #ifndef ALAC_WRAP_COUNTDOWN
 #define ALAC_WRAP_COUNTDOWN 0
 #endif
-constexpr uint32_t DUO_CHUNK = 16;     /* steps per queue buffer (a multiple of 8) */
+/* ALAC_DUO_CHUNK, set per translation unit in the same way: steps per queue buffer. 16 everywhere but in k_dec16l.hip, whose
+ * waves meet half as often (32: 32 steps per rendezvous in the U phase, 16 where a writer wave takes half of each buffer). */
+#ifndef ALAC_DUO_CHUNK
+#define ALAC_DUO_CHUNK 16
+#endif
+constexpr uint32_t DUO_CHUNK = ALAC_DUO_CHUNK; /* steps per queue buffer (a multiple of 16: CH below is whole top-up periods) */
+static_assert(DUO_CHUNK % 16u == 0u && DUO_CHUNK <= 32u, "a writer's half chunk is whole groups of 8 steps and fits a stager row");
 constexpr int DUO_UN8_MAX = 12;        /* longest predictor whose steady-state groups are 8 steps (else 4) */
 enum { ROLE_A = 0, ROLE_B = 1, ROLE_BOTH = 2, ROLE_C = 3 };
 
@@ -155,7 +161,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     auto qval = [&](uint32_t nd) -> int32_t { return QND ? (int32_t)nd : gol_unfold(nd); };
     auto golomb_chunk = [&](uint32_t c) {
         const uint32_t buf = c & 1u;
-        if ((c + 1u) * CH <= n_it) { /* CH is 8 or 16: whole top-up periods */
+        if ((c + 1u) * CH <= n_it) { /* CH is 8, 16 or 32: whole top-up periods */
 #pragma nounroll
             for (uint32_t g = 0; g < CH; g += GOL_TICK) {
                 s.rd.tick(wv, s.pos);

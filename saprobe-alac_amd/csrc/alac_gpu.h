@@ -2,7 +2,7 @@
  * alac_gpu.h — what the kernel translation units of libalacgpu.so share: the gfx950 forms of the building-block
  * macros of alac_regular.h, the wave policies (GpuWave: LDS stager, bitstream rings, residual queue, DPP reductions;
  * GpuWaveMem: residuals from memory), the launch plan (alac_plan.h), the sort's workspace, and the kernels' declarations. The library is built from
- * several translation units (k_sort, k_scan, k_dec16q, k_dec16g, k_dec24q, k_dec32q, k_decw24, k_decw32, k_split, alacgpu)
+ * several translation units (k_sort, k_scan, k_dec16q, k_dec16l, k_dec16g, k_dec24q, k_dec32q, k_decw24, k_decw32, k_split, alacgpu)
  * so that the kernels compile in parallel; nothing crosses between them on the device side.
  */
 #ifndef ALAC_GPU_H
@@ -204,7 +204,7 @@ static __shared__ unsigned long long s_optr[kWave];                             
 static __shared__ __attribute__((aligned(16))) uint32_t s_ring[kRingSlots * kWave];     /* bitstream rings */
 /* residual queue of the wave pair (alac_duo.h), A -> B, double-buffered chunks. Rows per buffer: a chunk of residuals
  * A -> B; where another wave writes the PCM (alac_duo.h: EMIT_A) half a chunk of residuals and half a chunk of samples
- * B -> writer */
+ * B -> writer. 8 KB; 16 KB in k_dec16l.hip (ALAC_DUO_CHUNK 32) */
 constexpr uint32_t kQ = alac::DUO_CHUNK;
 static __shared__ int32_t s_rq[2 * kQ * kWave];
 
@@ -539,6 +539,8 @@ static_assert(mode_is_fit4_without_the_others(1u) && mode_is_fit4_without_the_ot
                   mode_is_fit4_within_four(256u) && mode_is_fit4_within_four(304u),
               "decode_mode would leave batches of up to 4 x CUs wave slots to a launch that is not made for them");
 constexpr uint32_t kQuadLdsFit4 = 34816u; /* static + dynamic LDS of a "fit 4" launch: 4 x 34 KB <= 160 KB < 5 x 34 KB */
+/* (16-bit: the "fit 4" launch of batches that fill the device is alac_decode_16l's, k_dec16l.hip: the same workgroups with
+ * queue buffers of 32 steps. Its queue takes 8 KB of what is pad in alac_decode_16q's launch: 34 072 B static, 744 B of pad.) */
 
 /* arguments of the pair kernels (k_decode_body.inc), passed as one struct */
 struct PairArgs {
@@ -568,6 +570,7 @@ struct PairArgs {
 /* the wave pair over the regular packets, one kernel per class (sample width x channel width) */
 ALAC_DECLARE_DECODE(alac_decode_16q) ALAC_DECLARE_DECODE(alac_decode_16g) ALAC_DECLARE_DECODE(alac_decode_24q) ALAC_DECLARE_DECODE(alac_decode_32q)
 ALAC_DECLARE_DECODE(alac_decode_w24) ALAC_DECLARE_DECODE(alac_decode_w32)
+ALAC_DECLARE_DECODE(alac_decode_16l) /* alac_decode_16q with queue buffers of 32 steps (k_dec16l.hip) */
 #undef ALAC_DECLARE_DECODE
 __global__ void alac_chan_predict(alac::DevCfg cfg, const uint8_t* __restrict__ blob, uint64_t blob_bytes, const uint64_t* __restrict__ offsets,
                                   const uint32_t* __restrict__ sizes, const uint32_t* __restrict__ perm, const Plan* __restrict__ plan,

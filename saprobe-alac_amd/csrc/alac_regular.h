@@ -241,6 +241,11 @@ ALAC_DEV uint32_t classify_regular(const DevCfg& cfg, const uint8_t* pkt, uint32
  * a block that reaches past the packet's last byte takes tail1(): aligned dwords that hold at least one packet byte
  * are fetched (they cannot leave the blob's pages), the neighbour's bytes in them are cleared, and dwords wholly
  * behind the packet are zeros without a fetch — the reference's zero pad (bitbuffer.go:33), as far out as anyone looks. */
+/* ALAC_RING_START_AHEAD, set per translation unit (as ALAC_LDS_ROWS is): 1 = start() asks for its three blocks at once. On in
+ * k_dec16l.hip; every other unit keeps the block-by-block prefill and with it the code it had. */
+#ifndef ALAC_RING_START_AHEAD
+#define ALAC_RING_START_AHEAD 0
+#endif
 template <class W>
 struct RingRd {
     const uint32_t* base; /* packet start rounded down to a dword */
@@ -307,11 +312,29 @@ struct RingRd {
         const uint32_t ni = posb >> 5;
         fill = ni & ~7u;
         pend = false;
+#if ALAC_RING_START_AHEAD
+        /* the three blocks are asked for before the first one is committed: one trip to memory at the start of a channel
+         * (the predictor and writer waves stand idle meanwhile) instead of three dependent ones; 24 registers, here only */
+        uint32_t blk[3][8];
+#pragma unroll
+        for (uint32_t b = 0; b < 3u; ++b) {
+            load8(fill + 8u * b);
+            blk[b][0] = p0, blk[b][1] = p1, blk[b][2] = p2, blk[b][3] = p3;
+            blk[b][4] = p4, blk[b][5] = p5, blk[b][6] = p6, blk[b][7] = p7;
+        }
+#pragma unroll
+        for (uint32_t b = 0; b < 3u; ++b) {
+            p0 = blk[b][0], p1 = blk[b][1], p2 = blk[b][2], p3 = blk[b][3];
+            p4 = blk[b][4], p5 = blk[b][5], p6 = blk[b][6], p7 = blk[b][7];
+            commit(wv);
+        }
+#else
 #pragma nounroll
         for (int b = 0; b < 3; ++b) {
             load8(fill);
             commit(wv);
         }
+#endif
         reseek(wv, posb);
     }
     ALAC_DEV void reseek(W& wv, uint32_t posb) {

@@ -14,6 +14,8 @@
  *                  more than two channels also every channel's residuals, into the channel's row
  *   alac_decode_{16,24,32}q   regular packets: entropy, predictor, writer and spare wave per 64 same-key packets
  *                  (alac_duo.h), residuals and samples through an LDS queue; PCM staged in LDS, written in 128-B lines
+ *   alac_decode_16l   alac_decode_16q with queue buffers of 32 steps (half as many rendezvous of a workgroup's waves): the
+ *                  "fit 4" launch of 16-bit batches that fill the device (long_chunks)
  *   alac_decode_16g, alac_decode_w{24,32}   the gated twin (16-bit batches between the rounds) and the wide keys: a PAIR
  *                  of wavefronts (entropy; predictor + PCM) per 64 same-key packets (one kernel and compilation unit per
  *                  class: sample width x chanBits)
@@ -154,6 +156,7 @@ struct Kernels {
     bool lean;                       /* alac::lean_config: else alac_scan is the whole-packet decoder of every packet */
     bool one_or_two;                 /* channels: with `lean`, the regular packets have kernels of their own; more: the split pipeline */
     PairKernel quad;                 /* narrow regular keys: the four-wave kernel */
+    PairKernel quad_long;            /* ... and its form with queue buffers of 32 steps (16-bit only: k_dec16l.hip; long_chunks) */
     PairKernel gated;                /* ... and its gated twin of wave pairs (16-bit only) */
     PairKernel wide;                 /* wide keys: wave pairs (24- and 32-bit only) */
     decltype(&alac_interleave) interleave;
@@ -166,6 +169,7 @@ Kernels choose_kernels(const alac::DevCfg& c) {
     k.lean = alac::lean_config(c); /* pb and kb only: aligned16 has no say */
     k.one_or_two = c.num_channels <= 2;
     k.quad = c.bit_depth == 16 ? ALAC_PAIR_KERNEL(alac_decode_16q) : c.bit_depth == 32 ? ALAC_PAIR_KERNEL(alac_decode_32q) : ALAC_PAIR_KERNEL(alac_decode_24q); /* 24: 20 and 24 */
+    k.quad_long = c.bit_depth == 16 ? ALAC_PAIR_KERNEL(alac_decode_16l) : PairKernel{nullptr, ""};
     k.gated = c.bit_depth == 16 ? ALAC_PAIR_KERNEL(alac_decode_16g) : PairKernel{nullptr, ""};
     /* the wide keys (chanBits > 23: 24- and 32-bit streams without their usual shift bytes): wave pairs */
     k.wide = c.bit_depth == 32 ? ALAC_PAIR_KERNEL(alac_decode_w32) : c.bit_depth == 24 ? ALAC_PAIR_KERNEL(alac_decode_w24) : PairKernel{nullptr, ""};
@@ -213,6 +217,8 @@ struct alacgpu_decoder {
     char ahead_err[512];
     size_t last_n;                                           /* the last device decode: packets, packets per wave slot, PairArgs::cap */
     uint32_t last_ppw, last_cap, last_fit5;
+    bool last_long;                                          /* ... and whether its "fit 4" launch was the long-chunk kernel's (long_chunks) */
+    bool long_ok;                                            /* ALACGPU_CHUNK=16 (experiments): never */
     uint32_t fit_force;                                      /* PairArgs::fit_force (ALACGPU_FIT) */
     DevBuf wave_ws;                                          /* alacgpu_waveform_device: the scan's scratch */
     hipEvent_t ev_w0, ev_w1;                                 /* around the kernels of the last waveform pass */
@@ -419,6 +425,21 @@ void scan(const Launch& L) {
                        (uint64_t)row_stride_of(dec->cfg.frame_length));
 }
 
+/* Whether the "fit 4" launch of a batch of n packets is the long-chunk kernel's (k_dec16l.hip: queue buffers of 32 steps,
+ * half as many rendezvous of a workgroup's waves) — decided from what host and device both know, n and ppw, so that
+ * alacgpu_last_dispatch can name the kernel that ran. Batches that fill the device: full wave slots, at least one per CU.
+ * Below that a workgroup has its CU to itself and the keys with long predictors run predictor waves on several lanes per
+ * packet (k_decode_body.inc: lanes_ok, up to n_cu + n_cu / 8 narrow slots), a form the long-chunk unit leaves out; so a
+ * batch of that size takes it only where no key would get such waves (lanes_min above 16). Above 4 x CUs slots (`beyond4` in
+ * regular_packets) nothing changes: the "fit 5" and the gated launches live on the 26 KB of the short queue, and the rounds of
+ * four that such a batch may still run (5 to 7.5 slots per CU, or many irregular packets) stay alac_decode_16q's beside them. */
+bool long_chunks(const alacgpu_decoder* dec, size_t n, uint32_t ppw) {
+    const size_t slots = (n + ppw - 1) / ppw;
+    const uint32_t n_cu = dec->n_cu;
+    return dec->kernels.quad_long.fn && dec->long_ok && ppw == kWave && slots >= n_cu && slots <= (size_t)4 * n_cu &&
+           (slots > n_cu + n_cu / 8u || dec->lanes_min > 16u);
+}
+
 /* one of the up to three launches for the narrow regular wave slots (regular_packets) */
 void narrow_launch(const Launch& L, const PairArgs& a, uint32_t slots, uint32_t mode) {
     alacgpu_decoder* dec = L.dec;
@@ -429,10 +450,12 @@ void narrow_launch(const Launch& L, const PairArgs& a, uint32_t slots, uint32_t 
         return;
     }
     if (mode == kModeFit5 && !a.fit5) return;
-    const uint32_t stat = kernel_attr(k.quad.fn).static_lds;
+    /* (the long-chunk kernel's static LDS is all but the whole footprint of four per CU: its pad is what is left of it) */
+    const PairKernel& pk = (mode == kModeFit4 && dec->last_long) ? k.quad_long : k.quad;
+    const uint32_t stat = kernel_attr(pk.fn).static_lds;
     PairArgs q = a;
     q.fit = mode;
-    hipLaunchKernelGGL(k.quad.fn, dim3(slots), dim3(4 * kWave), (mode == kModeFit4 && stat < kQuadLdsFit4) ? kQuadLdsFit4 - stat : 0u,
+    hipLaunchKernelGGL(pk.fn, dim3(slots), dim3(4 * kWave), (mode == kModeFit4 && stat < kQuadLdsFit4) ? kQuadLdsFit4 - stat : 0u,
                        dec->stream, q);
 }
 
@@ -474,6 +497,7 @@ void regular_packets(const Launch& L) {
     if (a.cap <= 4u) a.cap = 0u;
     dec->last_cap = a.cap;
     dec->last_fit5 = a.fit5;
+    dec->last_long = long_chunks(dec, n, ppw);
     const uint32_t guess = decode_mode((uint32_t)((n + ppw - 1) / ppw), n_cu, a.cap, dec->fit_force, dec->cfg.num_channels == 1, a.fit5 != 0u);
     narrow_launch(L, a, slots, guess);
     if (k.wide.fn) hipLaunchKernelGGL(k.wide.fn, dim3(slots), dim3(2 * kWave), 0, dec->stream, a);
@@ -538,6 +562,7 @@ int launch(alacgpu_decoder* dec, const uint8_t* d_blob, uint64_t blob_bytes, con
     dec->last_n = n;
     dec->last_ppw = ppw;
     dec->last_cap = dec->last_fit5 = 0;
+    dec->last_long = false;
     const Kernels& k = dec->kernels;
     Launch L{dec, dec->dev_cfg, d_blob, blob_bytes, d_offsets, n, d_out, out_stride, d_frames, d_status, ppw, max_waves(dec, n, ppw),
              dec->stream, false, 0u};
@@ -693,12 +718,15 @@ void configure(alacgpu_decoder* d, const alacgpu_config* cfg) {
     d->ahead_err[0] = 0;
     d->last_n = 0;
     d->last_ppw = d->last_cap = d->last_fit5 = 0;
+    d->last_long = false;
     d->wave_timed = false;
     d->clips_timed = false;
     d->lanes_min = 4;
     d->fit_force = 0;
     if (const char* e = getenv("ALACGPU_FIT")) d->fit_force = (uint32_t)atoi(e); /* experiments: 4 / 5 workgroups per CU for every batch */
     if (const char* e = getenv("ALACGPU_LANES_MIN")) d->lanes_min = (uint32_t)std::max(1, atoi(e)); /* experiments; 17: never */
+    d->long_ok = true;
+    if (const char* e = getenv("ALACGPU_CHUNK")) d->long_ok = atoi(e) != 16; /* experiments (A/B): 16 keeps every batch on alac_decode_16q */
     d->side = 2;
     if (const char* e = getenv("ALACGPU_SIDE")) d->side = atoi(e); /* experiments, tests */
     d->chunk_bytes = (size_t)192 << 20;
@@ -1198,11 +1226,12 @@ int alacgpu_last_dispatch(alacgpu_decoder* d, alacgpu_dispatch* out) {
     const char* narrow = "";
     if (lean && out->narrow_slots) {
         const uint32_t mode = decode_mode(out->narrow_slots, d->n_cu, d->last_cap, d->fit_force, d->cfg.num_channels == 1, d->last_fit5 != 0u);
-        narrow = mode == kModeGated ? k.gated.name : k.quad.name;
+        const bool lng = mode == kModeFit4 && d->last_long;
+        narrow = mode == kModeGated ? k.gated.name : lng ? k.quad_long.name : k.quad.name;
         out->gated = mode == kModeGated ? 1u : 0u;
         out->workgroups_per_cu = mode == kModeGated ? pair_quota(out->narrow_slots, d->n_cu, d->last_cap) : mode;
         /* predictor waves on several lanes per packet (k_decode_body.inc: lanes_ok) */
-        if (!out->gated && out->narrow_slots <= d->n_cu + d->n_cu / 8u && d->lanes_min <= 16u) out->lanes_per_packet = d->last_ppw <= 32u ? 4u : 2u;
+        if (!out->gated && !lng && out->narrow_slots <= d->n_cu + d->n_cu / 8u && d->lanes_min <= 16u) out->lanes_per_packet = d->last_ppw <= 32u ? 4u : 2u;
     }
     snprintf(out->narrow_kernel, sizeof(out->narrow_kernel), "%s", narrow);
     snprintf(out->wide_kernel, sizeof(out->wide_kernel), "%s", (lean && out->wide_slots) ? k.wide.name : "");

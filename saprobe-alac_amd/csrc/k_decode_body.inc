@@ -8,6 +8,8 @@
  *
  *   ALAC_DECODE_GATED 0   one workgroup per item, placed by the hardware dispatcher, as many rounds as it takes. 34.5 KB
  *       of LDS per workgroup caps a CU at four, and up to 4 x CUs items the dispatcher spreads them exactly evenly.
+ *       (16-bit: two such kernels, k_dec16q.hip and k_dec16l.hip with longer queue buffers; the host launches one of them in
+ *       this shape, alacgpu.hip: long_chunks.)
  *   ALAC_DECODE_GATED 1   (16-bit only: its registers and 26 KB of LDS let six PAIRS share a CU) for item counts
  *       between the multiples of 4 x CUs, where the first kind would run a last, nearly empty round. As many
  *       workgroups as the device holds are launched; a workgroup asks its CU's gate for admission, the admitted ones
@@ -261,7 +263,10 @@ __global__ void __launch_bounds__(ALAC_DECODE_ROLES * kWave, ALAC_DECODE_WAVES) 
     __syncthreads();
     role ^= s_swap;
 #endif
-#if ALAC_DECODE_ROLES == 4
+#if ALAC_DECODE_ROLES == 4 && defined(ALAC_DECODE_NO_LANES)
+    /* (k_dec16l.hip: one predictor wave per workgroup; the constant takes duo_phase_lanes out of the kernel) */
+    pair_item(ka, first + bid, threadIdx.x & (kWave - 1u), (uint32_t)__builtin_amdgcn_readfirstlane((int)role), false);
+#elif ALAC_DECODE_ROLES == 4
     /* Two predictor waves for the long keys only while (nearly) every workgroup has a CU to itself (nine wave slots per eight CUs
      * (a partly filled slot per key comes on top of packets / 64): there the step of such a workgroup
      * shrinks with its longest wave (4 096 packets: 2.17 -> 1.56 ms; 16 384: 2.19 -> 2.09). On a fuller device the waves
