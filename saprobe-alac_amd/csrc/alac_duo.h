@@ -159,6 +159,39 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
     uint32_t ns_live = s.err == 0 ? ns : 0u;
     if (DO_A) gol_head(s, c31kb); /* the head of the channel's first step (gol_step) */
     auto qval = [&](uint32_t nd) -> int32_t { return QND ? (int32_t)nd : gol_unfold(nd); };
+#if ALAC_LEAN_PACKET_END
+    /* form: how the steps stand to the packets' ends (alac_regular.h: GOL_FORM_*; the main loop below chooses it) */
+    auto golomb_chunk = [&](uint32_t c, auto form) {
+        constexpr int FORM = decltype(form)::value;
+        const uint32_t buf = c & 1u;
+        if (FORM == GOL_FORM_FAR || (c + 1u) * CH <= n_it) { /* CH is 8, 16 or 32: whole top-up periods */
+#pragma nounroll
+            for (uint32_t g = 0; g < CH; g += GOL_TICK) {
+                s.rd.tick(wv, s.pos);
+                s.near = gol_near_rest(s, c * CH + g, ns_live); /* (FAR and END: no packet-end term) */
+#pragma nounroll
+                for (uint32_t h = g; h < g + GOL_TICK; h += 4u) {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4u; ++j)
+                        wv.rq_write(buf, h + j, qval(gol_step<true, FORM>(wv, bits, s, size, kb, wb, c31kb, chan_bits, c * CH + h + j, ns, ns_live)));
+                }
+            }
+            return;
+        }
+        if constexpr (FORM != GOL_FORM_FAR) { /* (a chunk that is not whole is the channel's last) */
+#pragma nounroll
+            for (uint32_t j = 0; j < CH; ++j) {
+                const uint32_t i = c * CH + j;
+                if (i >= n_it) break;
+                if ((i & (GOL_TICK - 1u)) == 0) {
+                    s.rd.tick(wv, s.pos);
+                    s.near = gol_near_rest(s, i, ns_live);
+                }
+                wv.rq_write(buf, j, qval(gol_step<true, FORM>(wv, bits, s, size, kb, wb, c31kb, chan_bits, i, ns, ns_live)));
+            }
+        }
+    };
+#else
     auto golomb_chunk = [&](uint32_t c) {
         const uint32_t buf = c & 1u;
         if ((c + 1u) * CH <= n_it) { /* CH is 8, 16 or 32: whole top-up periods */
@@ -186,6 +219,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
             wv.rq_write(buf, j, qval(gol_step<true>(wv, bits, s, size, kb, wb, c31kb, chan_bits, i, ns, ns_live)));
         }
     };
+#endif
     /* PCM of frame i from its last channel's sample o (unmix / shift merge / packing / stager).
      * u: the U sample of frame i (pairs), sw: window on the frame's shift values (24/32-bit) */
     /* FP_OK / fp: 16-bit pairs in chunks that every lane keeps whole or not at all: the writer pushes a group's dwords at
@@ -659,6 +693,60 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
      * c-2 from the samples B queued in iteration c-1); the barrier publishes the buffers written in the iteration */
     const uint32_t nch = (n_it + CH - 1u) / CH;
     const uint32_t iters = nch + (EMIT_A ? 2u : 1u);
+#if ALAC_LEAN_PACKET_END
+    /* (the iteration of the loop below, with the form of the entropy role's steps) */
+    auto iteration = [&](uint32_t c, auto form) {
+        if (DO_A) {
+            if (EMIT_A && !EC && c >= 2u) fetch_chunk(c - 2u);
+            if (c < nch) golomb_chunk(c, form);
+        }
+        if (DO_B) {
+            if (c >= 1u && c <= nch) predict_chunk(c - 1u);
+        }
+        if (DO_A && EMIT_A && !EC) {
+            if (c >= 2u) emit_chunk(c - 2u);
+        }
+        if (DO_C && C16) {
+            if (c >= 2u) emit_chunk16(c - 2u);
+            if (c >= 1u && c <= nch) fetch_u16(c - 1u);
+        } else if (DO_C && EMIT_A) {
+            if (c >= 2u) {
+#pragma unroll
+                for (uint32_t j = 0; j < CH; ++j) {
+                    u_v[j] = u_n[j];
+                    sw_v[j] = sw_n[j];
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < CH / 4u; ++q) {
+                    g_v[q][0] = g_n[q][0];
+                    g_v[q][1] = g_n[q][1];
+                    g_v[q][2] = g_n[q][2];
+                }
+            }
+            if (c >= 1u && c <= nch) fetch_mem_ahead(c - 1u);
+            if (c >= 2u) {
+                fetch_chunk(c - 2u);
+                emit_chunk(c - 2u);
+            }
+        }
+        wv.duo_sync();
+    };
+    /* The entropy role's iterations come in two loops. FAR while every lane that still decodes stays clear of its packet's
+     * end for a whole chunk more, whatever its steps turn out to be (gol_far: the wave is uniform here): the plain step with
+     * no packet-end term anywhere. Then END to the channel's last chunk: positions only grow, so there is no way back. The
+     * stretch is a couple of hundred steps of 8 192, two instructions more each, where every lane used to take golomb_slow
+     * in each of the last 40-odd steps with the predictor and writer waves at the barrier meanwhile. TWO LOOPS, not a choice
+     * per group of 8 steps inside one: with both forms of the group in one loop the compiler shuffles two dozen registers
+     * around every group, which cost the whole kernel 3.6 % (profiles/r09_packet_ends/). */
+    uint32_t c_far = 0;
+    if (DO_A) {
+        for (; (c_far + 1u) * CH <= n_it; ++c_far) {
+            if (wv.any(c_far * CH < ns_live && !gol_far(s, CH))) break;
+            iteration(c_far, std::integral_constant<int, GOL_FORM_FAR>{});
+        }
+    }
+    for (uint32_t c = c_far; c < iters; ++c) iteration(c, std::integral_constant<int, GOL_FORM_END>{});
+#else
     for (uint32_t c = 0; c < iters; ++c) {
         if (DO_A) {
             if (EMIT_A && !EC && c >= 2u) fetch_chunk(c - 2u);
@@ -695,6 +783,7 @@ ALAC_DEV void duo_phase(W& wv, const DevCfg& cfg, const B& bits, RegLane<W>& s, 
         }
         wv.duo_sync();
     }
+#endif
     if (DO_EMIT && LAST) wv.st_tail(pk_acc, pk_n); /* bytes of the last, incomplete dword */
     if (!LAST) wv.duo_sync_mem();                  /* the U tile is complete before anyone loads from it */
 }

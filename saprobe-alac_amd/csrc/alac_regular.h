@@ -246,6 +246,19 @@ ALAC_DEV uint32_t classify_regular(const DevCfg& cfg, const uint8_t* pkt, uint32
 #ifndef ALAC_RING_START_AHEAD
 #define ALAC_RING_START_AHEAD 0
 #endif
+/* ALAC_LEAN_ENDS, set per translation unit in the same way: what the entropy role does at a packet's ends, one bit per part
+ * (DESIGN.md 3.3). 0: every unit but k_dec16l.hip, which keep the code they had.
+ *   1  packet end: chunks with a lane within reach of its packet's end run the END form of the step (gol_step: the plain
+ *      step plus the exact overrun test) instead of sending every such lane through golomb_slow, all others the FAR form
+ *      (the plain step, and no packet-end term in `near` at all);
+ *   2  sample end: the exact term i + GOL_TICK > ns_live instead of an over-reach of one group (gol_near_samples);
+ *   4  tail blocks: all eight fetches of a block that reaches past the packet are issued before the first is masked. */
+#ifndef ALAC_LEAN_ENDS
+#define ALAC_LEAN_ENDS 0
+#endif
+#define ALAC_LEAN_PACKET_END ((ALAC_LEAN_ENDS & 1) != 0)
+#define ALAC_LEAN_SAMPLE_END ((ALAC_LEAN_ENDS & 2) != 0)
+#define ALAC_LEAN_TAIL_BLOCKS ((ALAC_LEAN_ENDS & 4) != 0)
 template <class W>
 struct RingRd {
     const uint32_t* base; /* packet start rounded down to a dword */
@@ -279,12 +292,73 @@ struct RingRd {
         const uint32_t nb = end_b > lo ? umin(end_b - lo, 4u) : 0u;
         return v & (nb >= 4u ? 0xffffffffu : ((1u << (8u * nb)) - 1u));
     }
+#if ALAC_LEAN_TAIL_BLOCKS
+    /* tail1() in two halves, so that a block's eight fetches can be on their way before the first one is looked at: the
+     * same addresses and the same masks */
+    ALAC_DEV uint32_t tail_fetch(uint32_t idx) const {
+        const uint32_t last = end_b ? (end_b - 1u) >> 2 : 0u;
+        return base[umin(idx, last)];
+    }
+    ALAC_DEV uint32_t tail_mask(uint32_t idx) const {
+        const uint32_t lo = idx * 4u;
+        const uint32_t nb = end_b > lo ? umin(end_b - lo, 4u) : 0u;
+        return nb >= 4u ? 0xffffffffu : ((1u << (8u * nb)) - 1u);
+    }
+    ALAC_DEV void fetch8(uint32_t at) { /* the block's dwords as memory holds them: whole blocks are done with that */
+        if (at + 8u <= full) {
+            ALAC_LOAD4(base + at, p0, p1, p2, p3);
+            ALAC_LOAD4(base + at + 4u, p4, p5, p6, p7);
+        } else {
+            p0 = tail_fetch(at);
+            p1 = tail_fetch(at + 1u);
+            p2 = tail_fetch(at + 2u);
+            p3 = tail_fetch(at + 3u);
+            p4 = tail_fetch(at + 4u);
+            p5 = tail_fetch(at + 5u);
+            p6 = tail_fetch(at + 6u);
+            p7 = tail_fetch(at + 7u);
+        }
+    }
+    ALAC_DEV void mask8(uint32_t at) { /* a block that reaches past the packet keeps what is packet data */
+        if (at + 8u > full) {
+            p0 &= tail_mask(at);
+            p1 &= tail_mask(at + 1u);
+            p2 &= tail_mask(at + 2u);
+            p3 &= tail_mask(at + 3u);
+            p4 &= tail_mask(at + 4u);
+            p5 &= tail_mask(at + 5u);
+            p6 &= tail_mask(at + 6u);
+            p7 &= tail_mask(at + 7u);
+        }
+    }
+#endif
     ALAC_DEV void load8(uint32_t at) {
         /* two 16-byte loads, 4-byte aligned. The dwords stay RAW (little-endian) in p0..p7: touching them here
          * would make the wave wait for the loads on the spot; commit() swaps them eight steps later. */
         if (at + 8u <= full) {
             ALAC_LOAD4(base + at, p0, p1, p2, p3);
             ALAC_LOAD4(base + at + 4u, p4, p5, p6, p7);
+#if ALAC_LEAN_TAIL_BLOCKS
+        } else { /* the last blocks of the packet, and everything behind it: eight fetches, ONE wait, then the masks (masking
+                    each dword as it is asked for made eight dependent trips to memory of it) */
+            p0 = tail_fetch(at);
+            p1 = tail_fetch(at + 1u);
+            p2 = tail_fetch(at + 2u);
+            p3 = tail_fetch(at + 3u);
+            p4 = tail_fetch(at + 4u);
+            p5 = tail_fetch(at + 5u);
+            p6 = tail_fetch(at + 6u);
+            p7 = tail_fetch(at + 7u);
+            p0 &= tail_mask(at);
+            p1 &= tail_mask(at + 1u);
+            p2 &= tail_mask(at + 2u);
+            p3 &= tail_mask(at + 3u);
+            p4 &= tail_mask(at + 4u);
+            p5 &= tail_mask(at + 5u);
+            p6 &= tail_mask(at + 6u);
+            p7 &= tail_mask(at + 7u);
+        }
+#else
         } else { /* the last blocks of the packet, and everything behind it */
             p0 = tail1(at);
             p1 = tail1(at + 1u);
@@ -295,6 +369,7 @@ struct RingRd {
             p6 = tail1(at + 6u);
             p7 = tail1(at + 7u);
         }
+#endif
     }
     ALAC_DEV void commit(W& wv) {
         const uint32_t slot = fill & (RING - 1u);
@@ -318,7 +393,11 @@ struct RingRd {
         uint32_t blk[3][8];
 #pragma unroll
         for (uint32_t b = 0; b < 3u; ++b) {
+#if ALAC_LEAN_TAIL_BLOCKS
+            fetch8(fill + 8u * b); /* tail blocks too are only asked for here (short packets: all three may be) */
+#else
             load8(fill + 8u * b);
+#endif
             blk[b][0] = p0, blk[b][1] = p1, blk[b][2] = p2, blk[b][3] = p3;
             blk[b][4] = p4, blk[b][5] = p5, blk[b][6] = p6, blk[b][7] = p7;
         }
@@ -326,6 +405,9 @@ struct RingRd {
         for (uint32_t b = 0; b < 3u; ++b) {
             p0 = blk[b][0], p1 = blk[b][1], p2 = blk[b][2], p3 = blk[b][3];
             p4 = blk[b][4], p5 = blk[b][5], p6 = blk[b][6], p7 = blk[b][7];
+#if ALAC_LEAN_TAIL_BLOCKS
+            mask8(fill); /* (commit moves fill on) */
+#endif
             commit(wv);
         }
 #else
@@ -411,17 +493,50 @@ struct RegLane {
  * channel's last sample is among the next eight when i + 8 >= ns_live */
 constexpr uint32_t GOL_TICK = 8;  /* steps per ring top-up */
 constexpr uint32_t GOL_REACH = 41u * GOL_TICK; /* bits a lane can move between two looks at `near` */
+/* the sample-end term from step i of a group on (the groups start at multiples of GOL_TICK). ALAC_LEAN_SAMPLE_END: nonzero
+ * exactly when the group holds a step i >= ns_live, which golomb_slow parks the lane in; a group that the lane's last sample
+ * closes runs plain: of what golomb.go does differently for the last sample, only the zero run's start is left (:223), and
+ * every such start goes to golomb_slow through the plain step's zs flag, where i + 1 < ns is tested. Otherwise one group
+ * more (the term as it was). */
+ALAC_DEV uint32_t gol_near_samples(uint32_t i, uint32_t ns_live) {
+#if ALAC_LEAN_SAMPLE_END
+    return ALAC_SUBSAT((i | (GOL_TICK - 1u)) + 1u, ns_live);
+#else
+    return ALAC_SUBSAT(i + GOL_TICK + 1u, ns_live);
+#endif
+}
 template <class W>
 ALAC_DEV uint32_t gol_near(const RegLane<W>& s, uint32_t i, uint32_t ns_live) {
-    return ALAC_SUBSAT(s.pos + (GOL_REACH + 1u), s.max_pos) | ALAC_SUBSAT(i + GOL_TICK + 1u, ns_live) | s.zmode;
+    return ALAC_SUBSAT(s.pos + (GOL_REACH + 1u), s.max_pos) | gol_near_samples(i, ns_live) | s.zmode;
 }
+/* The forms of a step (gol_step, golomb_slow). NEAR: `near` holds the packet-end term, looked at every GOL_TICK steps (the
+ * form every caller had, and the only one without ALAC_LEAN_PACKET_END). With it the caller knows more:
+ * FAR: no lane comes within reach of its packet's end before the caller looks again (gol_far), so `near` holds no
+ *      packet-end term, neither at a top-up (gol_near_rest) nor behind the slow path;
+ * END: some lane may: the plain step plus the one test the reach stood for, golomb.go:168 on the step's own starting position,
+ *      pos >= max_pos (the stored position is biased and minus one: pos + 2 > max_pos, one add and one saturating subtract
+ *      OR-ed into `rare`). A lane that fails it redoes the step in golomb_slow, which reports the overrun where it always
+ *      did; a code that merely reaches past the last bit reads the zero pad, as the reference does. The inline escape path
+ *      asks for GOL_ESC_REACH bits of packet behind the position (getStreamBits' bounds: 9 + 32 bits and the byte behind). */
+enum { GOL_FORM_NEAR = 0, GOL_FORM_FAR = 1, GOL_FORM_END = 2 };
+#if ALAC_LEAN_PACKET_END
+constexpr uint32_t GOL_ESC_REACH = 64;
+/* bits a step can move at most, the slow path included: an escape code (9 + chanBits <= 42) and a zero-run code (<= 25) */
+constexpr uint32_t GOL_STEP_MAX = 72;
+/* true where the lane stays clear of its packet's end for `steps` more steps (the caller runs them in the FAR form) */
+template <class W>
+ALAC_DEV bool gol_far(const RegLane<W>& s, uint32_t steps) { return ALAC_SUBSAT(s.pos + (GOL_STEP_MAX * steps + 1u), s.max_pos) == 0u; }
+#endif
+/* `near` without the packet-end term (the FAR and END forms) */
+template <class W>
+ALAC_DEV uint32_t gol_near_rest(const RegLane<W>& s, uint32_t i, uint32_t ns_live) { return gol_near_samples(i, ns_live) | s.zmode; }
 
 /* The rare part of DynDecomp (golomb.go:167-247) for one lane: the lane's last samples and everything behind them,
  * overrun, an escape code, the start of a zero run and the code behind one. Redoes the sample from its start with the
  * stateless reader; returns n + zmode (what the plain step would have queued: the predictor wave folds the sign,
  * golomb.go:206-209). Works on local copies and writes the lane state back once (stores into the state from several
  * exits make the compiler keep it in scratch memory). ns_live: the lane's sample count, 0 once it has failed. */
-template <class W, class B>
+template <class W, class B, int FORM = GOL_FORM_NEAR>
 ALAC_DEV uint32_t golomb_slow(W& wv, const B& bits, RegLane<W>& s, uint32_t size, uint32_t kb, uint32_t wb,
                               uint32_t chan_bits, uint32_t i, uint32_t ns, uint32_t& ns_live) {
     if (i >= ns_live) { /* nothing left to decode: park the lane (it looks like one inside an endless zero run) */
@@ -469,7 +584,14 @@ ALAC_DEV uint32_t golomb_slow(W& wv, const B& bits, RegLane<W>& s, uint32_t size
                 int32_t k32 = (int32_t)clz32(mean) - 24 + (int32_t)((mean + 16u) >> 6);
                 if (k32 < 0) k32 = 0;
                 const uint32_t kz = (uint32_t)k32;
+#if ALAC_LEAN_PACKET_END
+                /* the same mask from kb (wb is 2^kb - 1, all ones from kb = 32 on, and kz <= 8), so that wb does not hold a
+                 * register through the entropy loop for this line's sake: with a second form of every group the kernel
+                 * would need one more than it has */
+                const uint32_t mz = (1u << umin(kz, kb)) - 1u;
+#else
                 const uint32_t mz = ((1u << kz) - 1u) & wb;
+#endif
                 if ((pos >> 3) > size) { /* dynGet's read32bit, golomb.go:115 */
                     err = ST_MALFORMED;
                 } else {
@@ -498,7 +620,7 @@ ALAC_DEV uint32_t golomb_slow(W& wv, const B& bits, RegLane<W>& s, uint32_t size
         s.zmode = zmode;
         s.zq = zrem - 1u;
         /* the steps up to the next top-up: at most seven (gol_near) */
-        s.near = ALAC_SUBSAT(pos + bias + GOL_REACH, s.max_pos) | ALAC_SUBSAT(i + GOL_TICK + 1u, ns_live) | zmode;
+        s.near = (FORM != GOL_FORM_NEAR ? 0u : ALAC_SUBSAT(pos + bias + GOL_REACH, s.max_pos)) | gol_near_samples(i, ns_live) | zmode;
         return ndq;
     }
     s.err = err;
@@ -539,9 +661,11 @@ ALAC_DEV void gol_head(RegLane<W>& s, uint32_t c31kb) {
  * keeps in order (the build runs with the pre-RA scheduler off, csrc/Makefile); the same code runs in tests/host_sim.
  * Returns n + zmode (0 inside a run).
  */
-template <bool ESC, class W, class B>
+/* FORM: GOL_FORM_* (above) */
+template <bool ESC, int FORM = GOL_FORM_NEAR, class W, class B>
 ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, uint32_t kb, uint32_t wb, uint32_t c31kb,
                            uint32_t chan_bits, uint32_t i, uint32_t ns, uint32_t& ns_live) {
+    static_assert(FORM == GOL_FORM_NEAR || ALAC_LEAN_PACKET_END, "the other forms come with the switch");
     const uint32_t o_pos = s.pos, o_mean = s.mean, o_zq = s.zq;
     RingRd<W>& rd = s.rd;
     const uint32_t o_wa = rd.wa, o_wb = rd.wb; /* stream dwords o_pos >> 5 and the next (o_pos: minus one) */
@@ -580,7 +704,10 @@ ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, u
         const uint32_t zs = ALAC_SUBSAT(128u, mean2);
         uint32_t x = mean2 >> 9;
         sh2 = ~pos2;
-        const uint32_t fl = esc | nhi | zs;
+        uint32_t fl = esc | nhi | zs;
+#if ALAC_LEAN_PACKET_END
+        if (FORM == GOL_FORM_END) fl |= ALAC_SUBSAT(o_pos + 2u, s.max_pos); /* the step started at or behind the packet's last bit */
+#endif
         t92 = ALAC_MULHI(mean2, s.pbs);
         x += 3u;
         norun2 = (uint32_t)((int32_t)zq2 >> 31);
@@ -609,7 +736,12 @@ ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, u
              * (golomb.go:216-218). Everything else, and a zero run behind either (mean * 4 < 512), takes golomb_slow from
              * the lane's old state. */
             bool done = false;
-            if (ESC && s.near == 0u) {
+#if ALAC_LEAN_PACKET_END
+            const bool inside = s.near == 0u && (FORM != GOL_FORM_END || ALAC_SUBSAT(o_pos + (GOL_ESC_REACH + 1u), s.max_pos) == 0u);
+#else
+            const bool inside = s.near == 0u;
+#endif
+            if (ESC && inside) {
                 if (esc != 0u && chan_bits <= 32u && chan_bits != 0u) {
                     const uint64_t hi = (((uint64_t)o_wa) << 32) | o_wb;
                     const uint32_t o_wc = wv.ring_read(((o_pos >> 5) + 2u) & (RingRd<W>::RING - 1u));
@@ -634,7 +766,7 @@ ALAC_DEV uint32_t gol_step(W& wv, const B& bits, RegLane<W>& s, uint32_t size, u
                 s.pos = o_pos;
                 s.mean = o_mean;
                 s.zq = o_zq;
-                ndq = golomb_slow(wv, bits, s, size, kb, wb, chan_bits, i, ns, ns_live);
+                ndq = golomb_slow<W, B, FORM>(wv, bits, s, size, kb, wb, chan_bits, i, ns, ns_live);
             }
             rd.reseek(wv, s.pos); /* the window afresh */
             gol_head(s, c31kb);   /* and the head of the lane's next step */

@@ -18,6 +18,11 @@
 #define ALAC_DUO_CHUNK 32
 /* the bitstream ring's three blocks at a channel's start in one trip to memory (alac_regular.h: RingRd::start) */
 #define ALAC_RING_START_AHEAD 1
+/* the entropy wave off the slow path at a packet's ends (alac_regular.h: ALAC_LEAN_ENDS; all three parts. A build with
+ * EXTRA=-DALAC_LEAN_ENDS=<bits> has some of them, for A/Bs) */
+#ifndef ALAC_LEAN_ENDS
+#define ALAC_LEAN_ENDS 7
+#endif
 #include "alac_gpu.h"
 
 #define ALAC_DECODE_KERNEL alac_decode_16l
