@@ -282,12 +282,18 @@ inline float round_once(double v) {
     return r == 0.0f ? 0.0f : r; /* +0.0f, never -0.0f */
 }
 
-/* floats of LDS a tile of tf frames needs; the places of its parts */
-inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t* a_floats, uint32_t* e_off, uint32_t* c_off) {
+/* floats of the first LDS region of a tile of tf frames: the staged inputs with their offset within a chunk, or the output tile
+ * in their place, rounded up to 4. Both transforms' lds_need begin with it. */
+inline uint64_t stage_floats(const Plan& pl, uint32_t tf) {
     uint64_t a = pl.hop <= pl.W ? (uint64_t)(tf - 1u) * pl.hop + pl.W + 3u : (uint64_t)tf * pl.W;
     const uint64_t o = (uint64_t)(pl.n_mels + (pl.num_ceps == 0u && pl.cfg.use_energy ? 1u : 0u)) * tf;
     if (o > a) a = o;
-    a = (a + 3u) & ~(uint64_t)3u;
+    return (a + 3u) & ~(uint64_t)3u;
+}
+
+/* floats of LDS a tile of tf frames needs; the places of its parts */
+inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t* a_floats, uint32_t* e_off, uint32_t* c_off) {
+    const uint64_t a = stage_floats(pl, tf);
     uint64_t at = a + (uint64_t)tf * pl.KP;
     if (a_floats) *a_floats = (uint32_t)a;
     if (e_off) *e_off = (uint32_t)at;
@@ -297,8 +303,28 @@ inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t* a_floats, uint32
     return at;
 }
 
-/* false: no plan for these arguments (alacgpu.h lists them) */
-inline bool make_plan(const Config& c, Plan* out) {
+/* The plan is built in steps, each a plain function over Config / Plan, so that the FFT transform's plan (alac_fbankfft.h) takes
+ * the ones it shares (config_ok, set_dims, mel_banks, dct_lifter) and leaves the direct transform's own (make_basis, fit_tile). */
+
+/* the DFT size of a configuration: 0 where frame_length is outside [1, 2048] */
+inline uint32_t n_fft_of(const Config& c) {
+    if (c.frame_length < 1u || c.frame_length > kMaxFft) return 0u;
+    uint32_t N = c.frame_length;
+    if (c.round_to_power_of_two)
+        for (N = 1u; N < c.frame_length; N *= 2u) {}
+    return N;
+}
+
+/* the filterbank's band in Hz: high_freq <= 0 counts from Nyquist. false: not 0 <= low < high <= Nyquist, high > 0 */
+inline bool band_of(const Config& c, double* low, double* high) {
+    const double nyquist = 0.5 * (double)c.sample_rate;
+    *low = c.low_freq;
+    *high = c.high_freq <= 0.0 ? c.high_freq + nyquist : c.high_freq;
+    return *low >= 0.0 && *low < nyquist && *high > 0.0 && *high <= nyquist && *low < *high;
+}
+
+/* false: no plan for these arguments, whatever the transform (alacgpu.h lists them) */
+inline bool config_ok(const Config& c) {
     if (c.frame_length < 1u || c.frame_length > kMaxFft || c.frame_shift < 1u || !c.sample_rate) return false;
     if (c.round_to_power_of_two > 1u || c.snip_edges > 1u || c.remove_dc_offset > 1u || c.window_type > kWinBlackman ||
         c.use_log_fbank > 1u || c.use_energy > 1u || c.raw_energy > 1u || c.htk_compat > 1u || c.use_power > 1u || c.log_energy > 1u ||
@@ -311,34 +337,35 @@ inline bool make_plan(const Config& c, Plan* out) {
     if (c.scale == 0.0 || c.energy_floor < 0.0) return false;
     const float scale2 = (float)(c.scale * c.scale);
     if (!std::isfinite(scale2) || !(scale2 > 0.0f)) return false;
-    const double nyquist = 0.5 * (double)c.sample_rate;
-    const double low = c.low_freq, high = c.high_freq <= 0.0 ? c.high_freq + nyquist : c.high_freq;
-    if (!(low >= 0.0 && low < nyquist && high > 0.0 && high <= nyquist && low < high)) return false;
+    double low, high;
+    return band_of(c, &low, &high);
+}
 
-    Plan pl;
+/* the dimensions and constants of a fresh plan for a configuration that config_ok accepts */
+inline void set_dims(const Config& c, Plan& pl) {
     pl.cfg = c;
     const uint32_t W = pl.W = c.frame_length;
-    uint32_t N = W;
-    if (c.round_to_power_of_two)
-        for (N = 1u; N < W; N *= 2u) {}
-    pl.N = N;
+    pl.N = n_fft_of(c);
     pl.hop = c.frame_shift;
-    const uint32_t K = pl.K = N / 2u + 1u;
+    const uint32_t K = pl.K = pl.N / 2u + 1u;
     pl.KP = K | 1u;
     pl.BP = (K + 1u) / 2u;
-    const uint32_t M = pl.n_mels = c.num_mel_bins;
+    pl.n_mels = c.num_mel_bins;
     pl.num_ceps = c.num_ceps;
-    pl.cols = c.num_ceps ? c.num_ceps : M + c.use_energy;
+    pl.cols = c.num_ceps ? c.num_ceps : pl.n_mels + c.use_energy;
     pl.fs = pl.hop < W ? pl.hop : W;
     pl.pad = c.snip_edges ? 0 : (int64_t)(W / 2u) - (int64_t)(pl.hop / 2u);
     pl.eps = 1.1920928955078125e-07f; /* 2^-23 */
     pl.log_eps = (float)std::log((double)pl.eps);
     pl.log_efloor = c.energy_floor > 0.0 ? (float)std::log(c.energy_floor) : 0.0f;
     pl.inv_w = (float)(1.0 / (double)W);
-    pl.scale2 = scale2;
-    pl.mel_off = 0u;
+    pl.scale2 = (float)(c.scale * c.scale);
+}
 
-    /* the folded basis */
+/* the folded basis and bt: the direct transform's own */
+inline void make_basis(Plan& pl) {
+    const Config& c = pl.cfg;
+    const uint32_t W = pl.W, N = pl.N, K = pl.K;
     const double pi = 3.14159265358979323846;
     const std::vector<double> win = window_of(c.window_type, W, c.blackman_coeff);
     const double pre = c.preemphasis;
@@ -365,69 +392,75 @@ inline bool make_plan(const Config& c, Plan* out) {
                 pl.bt[((size_t)n * pl.BP + k / 2u) * 4u + 2u * (k & 1u) + part] = v;
             }
         }
+}
 
-    /* get_mel_banks */
-    {
-        const double m_low = mel_of(low), m_high = mel_of(high), delta = (m_high - m_low) / (double)(M + 1u);
-        const uint32_t nb = N / 2u; /* bins with a weight */
-        const double width = (double)c.sample_rate / (double)N;
-        std::vector<float> fb((size_t)M * K, 0.0f);
-        pl.first.assign(M, 0);
-        std::vector<uint32_t> run(M, 0u);
-        for (uint32_t m = 0; m < M; m++) {
-            const double left = m_low + (double)m * delta, centre = m_low + (double)(m + 1u) * delta;
-            const double right = m_low + (double)(m + 2u) * delta;
-            int64_t f = -1, l = -1;
-            for (uint32_t k = 0; k < nb; k++) {
-                const double mk = mel_of(width * (double)k);
-                const double up = (mk - left) / (centre - left), down = (right - mk) / (right - centre);
-                double v = up < down ? up : down;
-                if (!(v > 0.0)) v = 0.0;
-                const float v32 = (float)v;
-                fb[(size_t)m * K + k] = v32;
-                if (v32 != 0.0f) {
-                    if (f < 0) f = k;
-                    l = k;
-                }
-            }
-            if (f >= 0) {
-                for (int64_t k = f; k <= l; k++)
-                    if (fb[(size_t)m * K + k] == 0.0f) return false; /* not one run */
-                pl.first[m] = (int32_t)f;
-                run[m] = (uint32_t)(l - f + 1);
-            }
-            if (run[m] > pl.taps) pl.taps = run[m];
-        }
-        if (!pl.taps) pl.taps = 1u;
-        pl.fbw.assign((size_t)M * pl.taps, 0.0f);
-        for (uint32_t m = 0; m < M; m++) {
-            if ((uint32_t)pl.first[m] + pl.taps > K) pl.first[m] = (int32_t)(K - pl.taps);
-            for (uint32_t q = 0; q < pl.taps; q++) pl.fbw[(size_t)m * pl.taps + q] = fb[(size_t)m * K + (uint32_t)pl.first[m] + q];
+/* get_mel_banks: first, taps and fbw. false: a filter that is not one run of weights */
+inline bool mel_banks(Plan& pl) {
+    const uint32_t M = pl.n_mels, N = pl.N, K = pl.K;
+    double low, high;
+    band_of(pl.cfg, &low, &high);
+    const double m_low = mel_of(low), m_high = mel_of(high), delta = (m_high - m_low) / (double)(M + 1u);
+    const uint32_t nb = N / 2u; /* bins with a weight */
+    const double width = (double)pl.cfg.sample_rate / (double)N;
+    std::vector<float> fb((size_t)M * K, 0.0f);
+    for (uint32_t m = 0; m < M; m++) {
+        const double left = m_low + (double)m * delta, centre = m_low + (double)(m + 1u) * delta;
+        const double right = m_low + (double)(m + 2u) * delta;
+        for (uint32_t k = 0; k < nb; k++) {
+            const double mk = mel_of(width * (double)k);
+            const double up = (mk - left) / (centre - left), down = (right - mk) / (right - centre);
+            double v = up < down ? up : down;
+            if (!(v > 0.0)) v = 0.0;
+            fb[(size_t)m * K + k] = (float)v;
         }
     }
+    return alacmel::compact_filters(fb, M, K, &pl.first, &pl.taps, &pl.fbw);
+}
 
-    /* the DCT and the lifter */
-    if (c.num_ceps) {
-        pl.dct.assign((size_t)c.num_ceps * M, 0.0f);
-        pl.lifter.assign(c.num_ceps, 1.0f);
-        /* row 0: sqrt(1 / M); times sqrt(2) where C0 itself leaves in the last column (htk_compat without use_energy) */
-        const float row0 = round_once(std::sqrt(((c.htk_compat && !c.use_energy) ? 2.0 : 1.0) / (double)M));
-        for (uint32_t q = 0; q < c.num_ceps; q++) {
-            for (uint32_t m = 0; m < M; m++)
-                pl.dct[(size_t)q * M + m] = q ? round_once(std::sqrt(2.0 / (double)M) * std::cos(pi * ((double)m + 0.5) * (double)q / (double)M))
-                                              : row0;
-            if (c.cepstral_lifter != 0.0)
-                pl.lifter[q] = (float)(1.0 + 0.5 * c.cepstral_lifter * std::sin(pi * (double)q / c.cepstral_lifter));
-        }
+/* the DCT and the lifter of MFCC; nothing for fbank */
+inline void dct_lifter(Plan& pl) {
+    const Config& c = pl.cfg;
+    const uint32_t M = pl.n_mels;
+    if (!c.num_ceps) return;
+    const double pi = 3.14159265358979323846;
+    pl.dct.assign((size_t)c.num_ceps * M, 0.0f);
+    pl.lifter.assign(c.num_ceps, 1.0f);
+    /* row 0: sqrt(1 / M); times sqrt(2) where C0 itself leaves in the last column (htk_compat without use_energy) */
+    const float row0 = round_once(std::sqrt(((c.htk_compat && !c.use_energy) ? 2.0 : 1.0) / (double)M));
+    for (uint32_t q = 0; q < c.num_ceps; q++) {
+        for (uint32_t m = 0; m < M; m++)
+            pl.dct[(size_t)q * M + m] = q ? round_once(std::sqrt(2.0 / (double)M) * std::cos(pi * ((double)m + 0.5) * (double)q / (double)M))
+                                          : row0;
+        if (c.cepstral_lifter != 0.0)
+            pl.lifter[q] = (float)(1.0 + 0.5 * c.cepstral_lifter * std::sin(pi * (double)q / c.cepstral_lifter));
     }
+}
 
+/* where the mel tile begins in the first LDS region: behind a leading energy column of fbank */
+inline uint32_t mel_off_of(const Config& c, uint32_t tf) { return (!c.num_ceps && c.use_energy && !c.htk_compat) ? tf : 0u; }
+
+/* the direct transform's fit: tile_frames halved from 64 until the tile fits the LDS budget, and the places of its parts.
+ * false: four frames do not fit */
+inline bool fit_tile(Plan& pl) {
     uint32_t tf = kMaxTile;
     while (tf > kMinTile && lds_need(pl, tf, nullptr, nullptr, nullptr) > kLdsFloats) tf /= 2u;
     const uint64_t need = lds_need(pl, tf, &pl.a_floats, &pl.e_off, &pl.c_off);
     if (need > kLdsFloats) return false;
     pl.tile_frames = tf;
     pl.lds_floats = (uint32_t)need;
-    pl.mel_off = (!c.num_ceps && c.use_energy && !c.htk_compat) ? tf : 0u;
+    pl.mel_off = mel_off_of(pl.cfg, tf);
+    return true;
+}
+
+/* false: no plan for these arguments (alacgpu.h lists them) */
+inline bool make_plan(const Config& c, Plan* out) {
+    if (!config_ok(c)) return false;
+    Plan pl;
+    set_dims(c, pl);
+    make_basis(pl);
+    if (!mel_banks(pl)) return false;
+    dct_lifter(pl);
+    if (!fit_tile(pl)) return false;
     *out = std::move(pl);
     return true;
 }

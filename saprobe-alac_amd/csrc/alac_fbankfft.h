@@ -29,8 +29,9 @@
  * for bit. Frames share nothing: a NaN or an infinity stays in the frames that read it. A constant frame has v = +0.0f exactly
  * wherever s and the quotient are exact, and so +0.0f in every mel column, as Kaldi has.
  *
- * The tables: ws[N]; the twiddle table and pos[M] of alacmelfft::make_passes(N); fbw, first, dct, lifter as in alac_fbank.h, built
- * by the same steps. There is no folded basis.
+ * The tables: ws[N], built here; the twiddle table and pos[M], which alacmelfft::make_passes(N) builds; fbw and first, which
+ * alacfb::mel_banks builds, and dct and lifter, which alacfb::dct_lifter builds: the very functions alacfb::make_plan calls, so
+ * these four are the direct plan's by construction. There is no folded basis: alacfb::make_basis is not called.
  *
  * A TILE is alac_fbank.h's: tile_frames frames of one row, one workgroup of 256. LDS, in floats:
  *   [staged inputs, later the output tile: a_floats] [power tile: tile_frames * KP, rounded up to 4] [energies: tile_frames, with
@@ -187,11 +188,8 @@ struct Plan {
 inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t batch, uint32_t* a_floats, uint32_t* p_floats, uint32_t* e_off,
                          uint32_t* c_off, uint32_t* s_off, uint32_t* b_off) {
     const alacfb::Plan& b = pl.base;
-    uint64_t a = b.hop <= b.W ? (uint64_t)(tf - 1u) * b.hop + b.W + 3u : (uint64_t)tf * b.W;
-    const uint64_t o = (uint64_t)(b.n_mels + (b.num_ceps == 0u && b.cfg.use_energy ? 1u : 0u)) * tf;
-    if (o > a) a = o;
-    a = (a + 3u) & ~(uint64_t)3u;
-    const uint64_t pt = ((uint64_t)tf * b.KP + 3u) & ~(uint64_t)3u;
+    const uint64_t a = alacfb::stage_floats(b, tf);
+    const uint64_t pt = ((uint64_t)tf * b.KP + 3u) & ~(uint64_t)3u; /* rounded up to 4, which the direct plan's is not */
     uint64_t at = a + pt;
     if (a_floats) *a_floats = (uint32_t)a;
     if (p_floats) *p_floats = (uint32_t)pt;
@@ -205,117 +203,25 @@ inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t batch, uint32_t* 
     return at + (uint64_t)2u * batch * pl.fft.pitch;
 }
 
-/* the DFT size of a configuration: 0 where frame_length is outside [1, 2048] */
-inline uint32_t n_fft_of(const Config& c) {
-    if (c.frame_length < 1u || c.frame_length > alacmel::kMaxFft) return 0u;
-    uint32_t N = c.frame_length;
-    if (c.round_to_power_of_two)
-        for (N = 1u; N < c.frame_length; N *= 2u) {}
-    return N;
-}
+using alacfb::n_fft_of; /* the DFT size of a configuration: k_fbank.hip asks for it under this name */
 
-/* false: no plan: what alacfb::make_plan refuses for its arguments (the same checks, in the same order), an N that size_ok
- * refuses, or four frames with one in the transform buffer that do not fit the LDS budget */
+/* false: no plan: a configuration that alacfb::config_ok refuses, an N that size_ok refuses, a filter that is not one run, or
+ * four frames with one in the transform buffer that do not fit the LDS budget. The checks, the dimensions, the filterbank, the
+ * DCT and the lifter are alac_fbank.h's steps, the ones alacfb::make_plan runs; ws, c32, the passes and the fit are this
+ * transform's own. It never passes through the direct transform's basis or fit: base.basis and base.bt stay empty. */
 inline bool make_plan(const Config& c, Plan* out) {
-    if (c.frame_length < 1u || c.frame_length > alacmel::kMaxFft || c.frame_shift < 1u || !c.sample_rate) return false;
-    if (c.round_to_power_of_two > 1u || c.snip_edges > 1u || c.remove_dc_offset > 1u || c.window_type > alacfb::kWinBlackman ||
-        c.use_log_fbank > 1u || c.use_energy > 1u || c.raw_energy > 1u || c.htk_compat > 1u || c.use_power > 1u || c.log_energy > 1u ||
-        c.layout > alacfb::kLayoutBins)
-        return false;
-    if (c.dither != 0.0 || c.vtln_warp != 1.0 || !c.use_power || (c.use_energy && !c.raw_energy)) return false;
-    if (c.num_mel_bins < 1u || c.num_mel_bins > alacmel::kMaxMels || c.num_ceps > c.num_mel_bins) return false;
-    for (double v : {c.preemphasis, c.blackman_coeff, c.low_freq, c.high_freq, c.energy_floor, c.scale, c.cepstral_lifter})
-        if (!std::isfinite(v)) return false;
-    if (c.scale == 0.0 || c.energy_floor < 0.0) return false;
-    const float scale2 = (float)(c.scale * c.scale);
-    if (!std::isfinite(scale2) || !(scale2 > 0.0f)) return false;
-    const double nyquist = 0.5 * (double)c.sample_rate;
-    const double low = c.low_freq, high = c.high_freq <= 0.0 ? c.high_freq + nyquist : c.high_freq;
-    if (!(low >= 0.0 && low < nyquist && high > 0.0 && high <= nyquist && low < high)) return false;
-    const uint32_t N = n_fft_of(c);
-    if (!alacmelfft::size_ok(N)) return false;
-
+    if (!alacfb::config_ok(c) || !alacmelfft::size_ok(n_fft_of(c))) return false;
     Plan plan;
     alacfb::Plan& pl = plan.base;
-    pl.cfg = c;
-    const uint32_t W = pl.W = c.frame_length;
-    pl.N = N;
-    pl.hop = c.frame_shift;
-    const uint32_t K = pl.K = N / 2u + 1u;
-    pl.KP = K | 1u;
-    pl.BP = (K + 1u) / 2u;
-    const uint32_t M = pl.n_mels = c.num_mel_bins;
-    pl.num_ceps = c.num_ceps;
-    pl.cols = c.num_ceps ? c.num_ceps : M + c.use_energy;
-    pl.fs = pl.hop < W ? pl.hop : W;
-    pl.pad = c.snip_edges ? 0 : (int64_t)(W / 2u) - (int64_t)(pl.hop / 2u);
-    pl.eps = 1.1920928955078125e-07f; /* 2^-23 */
-    pl.log_eps = (float)std::log((double)pl.eps);
-    pl.log_efloor = c.energy_floor > 0.0 ? (float)std::log(c.energy_floor) : 0.0f;
-    pl.inv_w = (float)(1.0 / (double)W);
-    pl.scale2 = scale2;
+    alacfb::set_dims(c, pl);
 
     /* the window times the scale, rounded once */
-    const std::vector<double> win = alacfb::window_of(c.window_type, W, c.blackman_coeff);
-    plan.ws.assign(N, 0.0f);
-    for (uint32_t n = 0; n < W; n++) plan.ws[n] = alacfb::round_once(c.scale * win[n]);
+    const std::vector<double> win = alacfb::window_of(c.window_type, pl.W, c.blackman_coeff);
+    plan.ws.assign(pl.N, 0.0f);
+    for (uint32_t n = 0; n < pl.W; n++) plan.ws[n] = alacfb::round_once(c.scale * win[n]);
     plan.c32 = (float)c.preemphasis;
-    if (!alacmelfft::make_passes(N, &plan.fft)) return false;
-
-    /* get_mel_banks, as alacfb::make_plan */
-    const double pi = 3.14159265358979323846;
-    {
-        const double m_low = alacfb::mel_of(low), m_high = alacfb::mel_of(high), delta = (m_high - m_low) / (double)(M + 1u);
-        const uint32_t nb = N / 2u; /* bins with a weight */
-        const double width = (double)c.sample_rate / (double)N;
-        std::vector<float> fb((size_t)M * K, 0.0f);
-        pl.first.assign(M, 0);
-        std::vector<uint32_t> run(M, 0u);
-        for (uint32_t m = 0; m < M; m++) {
-            const double left = m_low + (double)m * delta, centre = m_low + (double)(m + 1u) * delta;
-            const double right = m_low + (double)(m + 2u) * delta;
-            int64_t f = -1, l = -1;
-            for (uint32_t k = 0; k < nb; k++) {
-                const double mk = alacfb::mel_of(width * (double)k);
-                const double up = (mk - left) / (centre - left), down = (right - mk) / (right - centre);
-                double v = up < down ? up : down;
-                if (!(v > 0.0)) v = 0.0;
-                const float v32 = (float)v;
-                fb[(size_t)m * K + k] = v32;
-                if (v32 != 0.0f) {
-                    if (f < 0) f = k;
-                    l = k;
-                }
-            }
-            if (f >= 0) {
-                for (int64_t k = f; k <= l; k++)
-                    if (fb[(size_t)m * K + k] == 0.0f) return false; /* not one run */
-                pl.first[m] = (int32_t)f;
-                run[m] = (uint32_t)(l - f + 1);
-            }
-            if (run[m] > pl.taps) pl.taps = run[m];
-        }
-        if (!pl.taps) pl.taps = 1u;
-        pl.fbw.assign((size_t)M * pl.taps, 0.0f);
-        for (uint32_t m = 0; m < M; m++) {
-            if ((uint32_t)pl.first[m] + pl.taps > K) pl.first[m] = (int32_t)(K - pl.taps);
-            for (uint32_t q = 0; q < pl.taps; q++) pl.fbw[(size_t)m * pl.taps + q] = fb[(size_t)m * K + (uint32_t)pl.first[m] + q];
-        }
-    }
-
-    /* the DCT and the lifter, as alacfb::make_plan */
-    if (c.num_ceps) {
-        pl.dct.assign((size_t)c.num_ceps * M, 0.0f);
-        pl.lifter.assign(c.num_ceps, 1.0f);
-        const float row0 = alacfb::round_once(std::sqrt(((c.htk_compat && !c.use_energy) ? 2.0 : 1.0) / (double)M));
-        for (uint32_t q = 0; q < c.num_ceps; q++) {
-            for (uint32_t m = 0; m < M; m++)
-                pl.dct[(size_t)q * M + m] =
-                    q ? alacfb::round_once(std::sqrt(2.0 / (double)M) * std::cos(pi * ((double)m + 0.5) * (double)q / (double)M)) : row0;
-            if (c.cepstral_lifter != 0.0)
-                pl.lifter[q] = (float)(1.0 + 0.5 * c.cepstral_lifter * std::sin(pi * (double)q / c.cepstral_lifter));
-        }
-    }
+    if (!alacmelfft::make_passes(pl.N, &plan.fft) || !alacfb::mel_banks(pl)) return false;
+    alacfb::dct_lifter(pl);
 
     uint32_t tf = kMaxTile;
     while (tf > kMinTile && lds_need(plan, tf, tf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) > kLdsFloats) tf /= 2u;
@@ -325,7 +231,7 @@ inline bool make_plan(const Config& c, Plan* out) {
     if (need > kLdsFloats) return false;
     pl.tile_frames = tf;
     pl.lds_floats = (uint32_t)need;
-    pl.mel_off = (!c.num_ceps && c.use_energy && !c.htk_compat) ? tf : 0u;
+    pl.mel_off = alacfb::mel_off_of(c, tf);
     plan.batch = batch;
     plan.parts = kThreads / tf;
     for (plan.log_parts = 0u; (1u << plan.log_parts) < plan.parts; plan.log_parts++) {}
@@ -341,25 +247,8 @@ inline bool make_params(const Plan& pl, const float* in, uint64_t in_stride, uin
     if (!alacfb::make_params(pl.base, in, in_stride, rows, in_frames, out, out_row_stride, out_inner_stride, nullptr, fbw, first, dct,
                              lifter, &q.fb))
         return false;
-    const alacmelfft::Plan& f = pl.fft;
     q.fft.m = q.fb.m;
-    q.fft.w32 = ws;
-    q.fft.tw = tw;
-    q.fft.pos = pos;
-    q.fft.M = f.M;
-    q.fft.pitch = f.pitch;
-    q.fft.batch = pl.batch;
-    q.fft.p_floats = pl.p_floats;
-    q.fft.n_pass = f.n_pass;
-    q.fft.split = f.split;
-    q.fft.inv_M = alacmelfft::inv_of(f.M);
-    q.fft.inv_M1 = alacmelfft::inv_of(f.M + 1u);
-    q.fft.s3 = f.tw[1];
-    q.fft.c1 = f.tw[2];
-    q.fft.s1 = f.tw[3];
-    q.fft.c2 = f.tw[4];
-    q.fft.s2 = f.tw[5];
-    for (uint32_t s = 0; s < alacmelfft::kMaxPasses; s++) q.fft.pass[s] = f.pass[s];
+    alacmelfft::fill_params(pl.fft, pl.batch, pl.p_floats, ws, tw, pos, &q.fft);
     q.N = pl.base.N;
     q.parts = pl.parts;
     q.log_parts = pl.log_parts;

@@ -322,6 +322,45 @@ inline double mel_to_hz(double m, uint32_t scale) {
     return (200.0 / 3.0) * m;
 }
 
+/* the periodic Hann window of W samples within N, in double: 0.5 - 0.5 cos(2 pi j / W) at offset (N - W) / 2 ([1.0] for W = 1),
+ * 0 elsewhere */
+inline std::vector<double> hann_window(uint32_t N, uint32_t W) {
+    const double pi = 3.14159265358979323846;
+    std::vector<double> w(N, 0.0);
+    const uint32_t off = (N - W) / 2u;
+    for (uint32_t j = 0; j < W; j++) w[off + j] = W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W);
+    return w;
+}
+
+/* The dense filterbank fb [M][K] the way the device reads it: first[m] = filter m's first bin with a weight, taps = the longest
+ * run of weights (at least 1), fbw [M][taps] = the weights from first[m] on, first[m] moved down where that would pass K. false:
+ * a filter whose weights are not one run. The Kaldi plan's filterbank (alac_fbank.h) goes through here as well. */
+inline bool compact_filters(const std::vector<float>& fb, uint32_t M, uint32_t K, std::vector<int32_t>* first, uint32_t* taps,
+                            std::vector<float>* fbw) {
+    first->assign(M, 0);
+    *taps = 1u;
+    for (uint32_t m = 0; m < M; m++) {
+        const float* w = &fb[(size_t)m * K];
+        int64_t f = -1, l = -1;
+        for (uint32_t k = 0; k < K; k++)
+            if (w[k] != 0.0f) {
+                if (f < 0) f = k;
+                l = k;
+            }
+        if (f < 0) continue;
+        for (int64_t k = f; k <= l; k++)
+            if (w[k] == 0.0f) return false; /* not one run */
+        (*first)[m] = (int32_t)f;
+        if ((uint32_t)(l - f + 1) > *taps) *taps = (uint32_t)(l - f + 1);
+    }
+    fbw->assign((size_t)M * *taps, 0.0f);
+    for (uint32_t m = 0; m < M; m++) {
+        if ((uint32_t)(*first)[m] + *taps > K) (*first)[m] = (int32_t)(K - *taps);
+        for (uint32_t q = 0; q < *taps; q++) (*fbw)[(size_t)m * *taps + q] = fb[(size_t)m * K + (uint32_t)(*first)[m] + q];
+    }
+    return true;
+}
+
 /* floats of LDS a tile of tf frames needs: the staged inputs with their offset within a chunk, or the output tile in their
  * place, and the power tile */
 inline uint64_t lds_need(const Plan& pl, uint32_t tf, uint32_t* a_floats) {
@@ -363,9 +402,7 @@ inline bool make_plan(const Config& c, Plan* out, bool with_basis = true) {
     pl.log_floor = c.log == kLogNone ? 0.0f : (float)((c.log == kLogDb ? 10.0 : 1.0) * lf);
 
     const double pi = 3.14159265358979323846;
-    std::vector<double> w(N, 0.0);
-    const uint32_t off = (N - W) / 2u;
-    for (uint32_t j = 0; j < W; j++) w[off + j] = W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W);
+    const std::vector<double> w = hann_window(N, W);
     if (with_basis) {
         pl.basis.assign((size_t)2 * K * N, 0.0f);
         pl.bt.assign((size_t)N * pl.BP * 4u, 0.0f);
@@ -397,38 +434,18 @@ inline bool make_plan(const Config& c, Plan* out, bool with_basis = true) {
         for (uint32_t i = 0; i + 1u < M + 2u; i++)
             if (!(pts[i + 1u] > pts[i])) return false;
         std::vector<float> fb((size_t)M * K);
-        pl.first.assign(M, 0);
-        std::vector<uint32_t> run(M, 0u);
         for (uint32_t m = 0; m < M; m++) {
             const double d0 = pts[m + 1u] - pts[m], d1 = pts[m + 2u] - pts[m + 1u];
             const double enorm = c.norm ? 2.0 / (pts[m + 2u] - pts[m]) : 1.0;
-            int64_t f = -1, l = -1;
             for (uint32_t k = 0; k < K; k++) {
                 const double down = (freqs[k] - pts[m]) / d0, up = (pts[m + 2u] - freqs[k]) / d1;
                 double v = down < up ? down : up;
                 if (!(v > 0.0)) v = 0.0;
                 if (c.norm) v *= enorm;
-                const float v32 = (float)v;
-                fb[(size_t)m * K + k] = v32;
-                if (v32 != 0.0f) {
-                    if (f < 0) f = k;
-                    l = k;
-                }
+                fb[(size_t)m * K + k] = (float)v;
             }
-            if (f >= 0) {
-                for (int64_t k = f; k <= l; k++)
-                    if (fb[(size_t)m * K + k] == 0.0f) return false; /* not one run */
-                pl.first[m] = (int32_t)f;
-                run[m] = (uint32_t)(l - f + 1);
-            }
-            if (run[m] > pl.taps) pl.taps = run[m];
         }
-        if (!pl.taps) pl.taps = 1u;
-        pl.fbw.assign((size_t)M * pl.taps, 0.0f);
-        for (uint32_t m = 0; m < M; m++) {
-            if ((uint32_t)pl.first[m] + pl.taps > K) pl.first[m] = (int32_t)(K - pl.taps);
-            for (uint32_t q = 0; q < pl.taps; q++) pl.fbw[(size_t)m * pl.taps + q] = fb[(size_t)m * K + (uint32_t)pl.first[m] + q];
-        }
+        if (!compact_filters(fb, M, K, &pl.first, &pl.taps, &pl.fbw)) return false;
     }
 
     uint32_t tf = kMaxTile;

@@ -6,8 +6,9 @@
  *
  * The definition. N = n_fft even in [2, 2048], M = N / 2 = 2^a 3^b 5^c; any other N is no plan.
  *
- *   window   w32[n] = float(w[n]), w the direct pass's window in double: periodic Hann of W at offset (N - W) / 2 ([1.0] for W =
- *            1), +0.0f elsewhere.  v[n] = w32[n] * x~[n], one float32 product; x~ is what stage_tile / sample_at deliver.
+ *   window   w32[n] = float(w[n]), w the direct pass's window in double (alacmel::hann_window, the one both plans call):
+ *            periodic Hann of W at offset (N - W) / 2 ([1.0] for W = 1), +0.0f elsewhere.  v[n] = w32[n] * x~[n], one float32
+ *            product; x~ is what stage_tile / sample_at deliver.
  *   pack     z[m] = v[2 m] + i v[2 m + 1], m < M: a real transform of N through a complex one of M, one frame at a time.
  *   passes   radices r_0 .. r_{P-1} (the 5s, then the 3s, then the 4s, then a 2), L_s = r_0 .. r_{s-1}. Decimation in time, in
  *            place: z[m] is put at pos(m), pos over [r_0 .. r_s](n) = (n mod r_s) L_s + pos over [r_0 .. r_{s-1}](n / r_s), so
@@ -35,7 +36,9 @@
  * in the frames that contain it.
  *
  * The tables. twiddle = [8 roots: -0.5, s3, c1, s1, c2, s2, 0, 0] [pass 0: L (r - 1) complex] .. [pass P - 1] [t[0 .. M]: M + 1
- * complex], floats; window = w32[N]; pos[M] (uint32) is derived from the radices and not reported.
+ * complex], floats; window = w32[N]; pos[M] (uint32) is derived from the radices and not reported. make_passes builds the
+ * twiddle table and pos, make_plan the window; fbw and first are alacmel::make_plan's, which this plan runs without its basis.
+ * fill_params hands them to the device, for this pass and for alac_fbankfft.h's.
  *
  * A TILE is alac_mel.h's: tile_frames frames of one row, one workgroup of 256, staged by stage_tile. Its frames are transformed
  * `batch` at a time (batch = tile_frames except at the largest N, where the buffer of a whole tile does not fit): pack (window
@@ -345,12 +348,11 @@ inline bool make_plan(const alacmel::Config& c, Plan* out) {
     if (!size_ok(c.n_fft)) return false;
     Plan pl;
     if (!alacmel::make_plan(c, &pl.base, false)) return false;
-    const uint32_t N = pl.base.N, W = pl.base.W;
-    const double pi = 3.14159265358979323846;
+    const uint32_t N = pl.base.N;
 
-    pl.w32.assign(N, 0.0f);
-    const uint32_t off = (N - W) / 2u;
-    for (uint32_t j = 0; j < W; j++) pl.w32[off + j] = (float)(W == 1u ? 1.0 : 0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)W));
+    const std::vector<double> w = alacmel::hann_window(N, pl.base.W);
+    pl.w32.resize(N);
+    for (uint32_t n = 0; n < N; n++) pl.w32[n] = (float)w[n];
 
     if (!make_passes(N, &pl)) return false;
     uint32_t tf = kMaxTile;
@@ -366,6 +368,30 @@ inline bool make_plan(const alacmel::Config& c, Plan* out) {
     return true;
 }
 
+/* Everything of *q behind Params::m: the three device tables (a window [N], the twiddle table, pos) and what make_passes left in
+ * pl, with the batch and the power tile's size that the caller's fit arrived at. alac_fbankfft.h's make_params calls it as well,
+ * with its own window and fit. */
+inline void fill_params(const Plan& pl, uint32_t batch, uint32_t p_floats, const float* w32, const float* tw, const uint32_t* pos,
+                        Params* q) {
+    q->w32 = w32;
+    q->tw = tw;
+    q->pos = pos;
+    q->M = pl.M;
+    q->pitch = pl.pitch;
+    q->batch = batch;
+    q->p_floats = p_floats;
+    q->n_pass = pl.n_pass;
+    q->split = pl.split;
+    q->inv_M = inv_of(pl.M);
+    q->inv_M1 = inv_of(pl.M + 1u);
+    q->s3 = pl.tw[1];
+    q->c1 = pl.tw[2];
+    q->s1 = pl.tw[3];
+    q->c2 = pl.tw[4];
+    q->s2 = pl.tw[5];
+    for (uint32_t s = 0; s < kMaxPasses; s++) q->pass[s] = pl.pass[s];
+}
+
 /* the arguments of one pass with frames to write; false for what the entry rejects (alacmel::make_params) */
 inline bool make_params(const Plan& pl, const float* in, uint64_t in_stride, uint64_t rows, uint64_t in_frames, float* out,
                         uint64_t out_row_stride, uint64_t out_bin_stride, const float* w32, const float* tw, const uint32_t* pos,
@@ -373,23 +399,7 @@ inline bool make_params(const Plan& pl, const float* in, uint64_t in_stride, uin
     Params q{};
     if (!alacmel::make_params(pl.base, in, in_stride, rows, in_frames, out, out_row_stride, out_bin_stride, nullptr, fbw, first, &q.m))
         return false;
-    q.w32 = w32;
-    q.tw = tw;
-    q.pos = pos;
-    q.M = pl.M;
-    q.pitch = pl.pitch;
-    q.batch = pl.batch;
-    q.p_floats = pl.p_floats;
-    q.n_pass = pl.n_pass;
-    q.split = pl.split;
-    q.inv_M = inv_of(pl.M);
-    q.inv_M1 = inv_of(pl.M + 1u);
-    q.s3 = pl.tw[1];
-    q.c1 = pl.tw[2];
-    q.s1 = pl.tw[3];
-    q.c2 = pl.tw[4];
-    q.s2 = pl.tw[5];
-    for (uint32_t s = 0; s < kMaxPasses; s++) q.pass[s] = pl.pass[s];
+    fill_params(pl, pl.batch, pl.p_floats, w32, tw, pos, &q);
     *p = q;
     return true;
 }
