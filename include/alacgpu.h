@@ -893,6 +893,83 @@ typedef struct alacgpu_specaug_info {
 } alacgpu_specaug_info;
 int alacgpu_specaug_plan(const alacgpu_specaug* sa, alacgpu_specaug_info* info);
 
+/*
+ * WAVEFORM AUGMENTATION: float32 waveforms [rows][samples] with per-row lengths -> a random gain, noise from a bank at a random
+ * SNR, dither, clamp and padding, one pass on a handle of its own between the clips and the features (k_waveaug.hip,
+ * alac_waveaug.h; SpecAugment and every other pass are untouched). Row r is d_in + r * in_row_stride (elements),
+ * n_r = clamp(d_lengths[r], 0, samples), samples where d_lengths is NULL. The bank is noise_rows clips at d_noise + k *
+ * noise_row_stride of m_k = clamp(d_noise_lengths[k], 0, noise_samples) samples; a NULL bank or noise_rows = 0 is no noise.
+ *     tables    snr_amp[i] = (float)10^(-(snr_lo_q8 + i) / 5120), gain_amp[i] = (float)10^((gain_lo_q8 + i) / 5120): computed in
+ *               double at create, rounded once, uploaded; the device never calls pow
+ *     words     Philox4x32-10 as SpecAugment's, key (seed low, seed high), id = d_ids ? (uint64)d_ids[r] : row_base + r. The fourth
+ *               counter word is a stream number: SpecAugment's is 0, this pass's row draws are stream 2 (word j is output word
+ *               j % 4 of the block at (id low, id high, j / 4, 2)) and its dither is stream 3 (sample t: the block at (id low,
+ *               id high, t, 3)), so one (seed, ids) serves both passes
+ *     draws     five words per row whatever n_r and the bank are: applied = noise_rows > 0 && draw(65536) < noise_prob_q16;
+ *               k = draw(noise_rows); o = draw(m_k), and m_k = 0 clears applied; snr_i = draw(snr_hi_q8 - snr_lo_q8 + 1); gain_i =
+ *               draw(gain_hi_q8 - gain_lo_q8 + 1); draw(m) is the high 32 bits of word * m. The noise under sample t is
+ *               z_t = noise[k][(o + t) mod m_k]: the clip loops. d_draws: applied, k, o, snr_lo_q8 + snr_i, gain_lo_q8 + gain_i
+ *     energies  Ex = sum x_t^2, En = sum z_t^2 over t < n_r only, in one order that depends on n_r alone: chunks of `tile`
+ *               samples on the row's own index; in a chunk, lane l of 256 chains acc = fmaf(v, v, acc) from +0.0f over the samples
+ *               of index = l mod 256 in increasing order; acc[l] += acc[l + s] for s = 128 .. 1; the chunks in order from +0.0f
+ *     scalars   a = gain_amp[gain_i]; b = (sqrtf(Ex / En) * snr_amp[snr_i]) * a where applied, Ex > 0, En > 0 and both finite,
+ *               else 0. d_stats: Ex, En (0 without noise), a, b
+ *     output    t < n_r: v = a * x_t; b != 0: v = fmaf(b, z_t, v); dither != 0: v = fmaf(dither, g_t, v); clamp: v = v < -1 ? -1 :
+ *               v > 1 ? 1 : v (a NaN stays one). t >= n_r: pad_value. Nothing at t >= n_r or behind m_k is read; a row with
+ *               b == 0 never reads the bank. With a == 1, b == 0, no dither and no clamp a sample is 1.0f * x_t: its own bits,
+ *               but a signalling NaN comes out quiet
+ *     dither    the block's eight 16-bit halves h0 .. h7 (the low half of word 0 first): s = (h0 + h1 + h2 + h3) - (h4 + h5 + h6
+ *               + h7), g = (float)s * 0x1.3988e2p-16f (the float nearest 1 / sqrt((2^32 - 1) * 2 / 3)): an Irwin-Hall(8) stand-in
+ *               for a Gaussian of zero mean and unit variance, cut at +-4.9 sigma, bit-exact everywhere
+ * alacgpu_waveaug_create is ALACGPU_E_ARG, before any HIP call, for a NULL config, a range outside [-16384, 16384], out of
+ * order or more than 16384 (64 dB: 16 385 table entries) wide, noise_prob_q16 above 65536, a dither that is negative or not
+ * finite, or clamp above 1. The handle owns a stream, an event pair, the two tables and a grow-only block for the partial sums;
+ * it is single-caller, like a decoder.
+ */
+typedef struct alacgpu_waveaug_config {
+    int32_t snr_lo_q8, snr_hi_q8;   /* -16384 .. 16384, lo <= hi <= lo + 16384: the SNR in 1 / 256 dB */
+    int32_t gain_lo_q8, gain_hi_q8; /* likewise; 0, 0: no gain */
+    uint32_t noise_prob_q16;        /* 0 .. 65536: the share of rows that get noise */
+    float dither;                   /* >= 0; 0: none, and no random word is computed per sample */
+    uint32_t clamp;                 /* 0 / 1: saturate to [-1, 1] */
+    float pad_value;
+} alacgpu_waveaug_config;
+typedef struct alacgpu_waveaug alacgpu_waveaug;
+int alacgpu_waveaug_create(int device, const alacgpu_waveaug_config* config, alacgpu_waveaug** out);
+void alacgpu_waveaug_destroy(alacgpu_waveaug* wa);
+/* The handle's hipStream_t as an opaque pointer, a wait for everything on it, and the duration of the last pass in
+ * milliseconds: HIP events around its kernels (valid after a sync). */
+void* alacgpu_waveaug_stream(alacgpu_waveaug* wa);
+int alacgpu_waveaug_synchronize(alacgpu_waveaug* wa);
+int alacgpu_waveaug_last_ms(alacgpu_waveaug* wa, float* ms);
+/*
+ * rows x samples elements of d_in -> the same elements of d_out, which has a row stride of its own and may be d_in itself with
+ * the same stride (in place). Every element (r, t < samples) of the output is written exactly once and nothing else is touched
+ * but d_draws (NULL, or int32 [rows][5] on the device) and d_stats (NULL, or float [rows][4] on the device). d_lengths, d_noise,
+ * d_noise_lengths, d_ids (int64 [rows]): on the device, or NULL. rows = 0 or samples = 0 succeeds and touches nothing. Without a
+ * bank and without d_stats one kernel runs; otherwise three. ALACGPU_E_ARG before any HIP call: a NULL handle; with work to do a
+ * NULL d_in or d_out, a base that is not aligned to its element (d_ids: 8 bytes), a row stride below the row's samples, samples,
+ * noise_samples or noise_rows above 2^31 - 1, sizes whose products overflow, an output whose span of addresses meets the
+ * input's other than exactly in place, or a bank whose span meets the output's. Asynchronous on the handle's stream unless
+ * sync != 0: the input must be complete, or ordered on that stream, before the call.
+ */
+int alacgpu_waveaug_device(alacgpu_waveaug* wa, const float* d_in, size_t in_row_stride, size_t rows, size_t samples,
+                           const int32_t* d_lengths, const float* d_noise, size_t noise_row_stride, size_t noise_rows,
+                           size_t noise_samples, const int32_t* d_noise_lengths, uint64_t seed, uint64_t row_base, const int64_t* d_ids,
+                           float* d_out, size_t out_row_stride, int32_t* d_draws, float* d_stats, int sync);
+/* The plan the handle's kernels use: the parameters, tile (the samples of a chunk), draws = 5, the LDS of a workgroup, the
+ * scratch block as it stands (address and bytes: they change only when a pass needs more), and (where the pointers are not NULL
+ * and the capacities, counted in entries, suffice) the two tables. */
+typedef struct alacgpu_waveaug_info {
+    int32_t snr_lo_q8, snr_hi_q8, gain_lo_q8, gain_hi_q8;
+    uint32_t noise_prob_q16, clamp, tile, draws, snr_entries, gain_entries, lds_bytes;
+    float dither, pad_value;
+    uint32_t reserved;
+    uint64_t scratch_bytes, scratch_address;
+} alacgpu_waveaug_info;
+int alacgpu_waveaug_plan(const alacgpu_waveaug* wa, alacgpu_waveaug_info* info, float* snr_out, size_t snr_cap, float* gain_out,
+                         size_t gain_cap);
+
 /* Thread-local description of the last ALACGPU_E_HIP / E_ARG / E_CONFIG failure. */
 const char* alacgpu_last_error(void);
 

@@ -38,6 +38,7 @@ __all__ = [
     "NormConfig", "FeatureNorm", "NewFeatureNorm", "normalize_features", "kaldi_frame_counts", "load_features",
     "StackConfig", "StackInfo", "FrameStack", "NewFrameStack", "stack_frames", "add_deltas", "lfr",
     "SpecAugConfig", "SpecAugInfo", "SpecAugment", "NewSpecAugment", "spec_augment",
+    "WaveAugConfig", "WaveAugInfo", "WaveAugment", "NewWaveAugment", "augment_waveform",
 ]
 
 PACKET_PAD = 0  # ALACGPU_PACKET_PAD: blobs are dense since 0.3.0
@@ -334,6 +335,17 @@ _EXPORTS = {
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
                                               ctypes.c_void_p, ctypes.c_int]),
     "alacgpu_specaug_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "alacgpu_waveaug_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "alacgpu_waveaug_destroy": (None, [ctypes.c_void_p]),
+    "alacgpu_waveaug_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "alacgpu_waveaug_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
+    "alacgpu_waveaug_last_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    "alacgpu_waveaug_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "alacgpu_waveaug_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_size_t]),
     "alacgpu_last_error": (ctypes.c_char_p, []),
     "alacgpu_version": (ctypes.c_char_p, []),
 }
@@ -904,7 +916,7 @@ def NewPacketEncoder(config, device=0):
     return PacketEncoder(config, device)
 
 
-# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures, FeatureNorm, FrameStack, SpecAugment): what they share (§15a)
+# ---- the float32 row passes (Resampler, MelSpectrogram, KaldiFeatures, FeatureNorm, FrameStack, SpecAugment, WaveAugment): what they share (§15a)
 class _RowPass:
     """The handle of a row pass: _h (NULL once closed), _lib and device, and the entries every such handle has. A subclass names
     its C functions one by one (they are irregular: alacgpu_resampler_last_ms, but alacgpu_resample_out_frames), creates the
@@ -2008,8 +2020,208 @@ def spec_augment(feats, lengths=None, seed=_NO_SEED, ids=None, row_base=0, freq_
     return sa(feats, lengths, seed, ids, row_base, layout, out, out_layout, return_draws)
 
 
+# ---- WaveAugment (new: gain, noise from a bank at an SNR and dither per row, between load_clips and the feature pass) ----
+class WaveAugConfig(ctypes.Structure):
+    """alacgpu_waveaug_config (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("snr_lo_q8", "snr_hi_q8", "gain_lo_q8", "gain_hi_q8")] + [
+        ("noise_prob_q16", ctypes.c_uint32), ("dither", ctypes.c_float), ("clamp", ctypes.c_uint32), ("pad_value", ctypes.c_float)]
+
+
+class WaveAugInfo(ctypes.Structure):
+    """alacgpu_waveaug_info (include/alacgpu.h)."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("snr_lo_q8", "snr_hi_q8", "gain_lo_q8", "gain_hi_q8")] + [
+        (k, ctypes.c_uint32) for k in ("noise_prob_q16", "clamp", "tile", "draws", "snr_entries", "gain_entries", "lds_bytes")] + [
+        ("dither", ctypes.c_float), ("pad_value", ctypes.c_float), ("reserved", ctypes.c_uint32),
+        ("scratch_bytes", ctypes.c_uint64), ("scratch_address", ctypes.c_uint64)]
+
+
+def _waveaug_range(db, name):
+    """(lo, hi) in dB -> (round(lo * 256), round(hi * 256)), each within +-64 dB, in order and at most 64 dB apart"""
+    try:
+        lo, hi = db
+        lo, hi = int(round(float(lo) * 256)), int(round(float(hi) * 256))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s is (lo, hi) in dB, not %r" % (name, db))
+    if not (-16384 <= lo <= hi <= 16384 and hi - lo <= 16384):
+        raise ValueError("%s is (lo, hi) within [-64, 64] dB, lo <= hi <= lo + 64, not %r" % (name, db))
+    return lo, hi
+
+
+def _waveaug_config(snr, gain, noise_prob, dither, clamp, pad_value):
+    """The keywords -> the fields of a WaveAugConfig; ValueError for what alacgpu_waveaug_create refuses"""
+    if isinstance(noise_prob, bool) or not isinstance(noise_prob, (int, float)) or not 0.0 <= noise_prob <= 1.0:
+        raise ValueError("noise_prob is a number in [0, 1], not %r" % (noise_prob,))
+    if isinstance(dither, bool) or not isinstance(dither, (int, float)) or not 0.0 <= dither < float("inf"):
+        raise ValueError("dither is a finite number >= 0, not %r" % (dither,))
+    if not isinstance(clamp, (bool, int)) or clamp not in (0, 1):
+        raise ValueError("clamp is True or False, not %r" % (clamp,))
+    return (*_waveaug_range(snr, "snr"), *_waveaug_range(gain, "gain"), int(round(noise_prob * 65536)), float(np.float32(dither)),
+            int(clamp), float(np.float32(pad_value)))
+
+
+def _wave_rows(t, rows):
+    """[..., T] -> ([rows, T] without a copy, the row stride in elements), or (None, None) where the rows do not flatten or the
+    samples are not contiguous"""
+    T = int(t.shape[-1])
+    try:
+        v = t.view(rows, T) if t.ndim != 2 else t
+    except RuntimeError:
+        return None, None
+    if not v.numel():
+        return v, max(T, 1)
+    rs = T if rows == 1 else int(v.stride(0))
+    if (T > 1 and v.stride(1) != 1) or rs < T:
+        return None, None
+    return v, rs
+
+
+class WaveAugment(_RowPass):
+    """float32 waveforms [..., T] with per-row lengths -> gain, noise at an SNR, dither, clamp and padding on one MI355X
+    (include/alacgpu.h: alacgpu_waveaug_*). Per row over its first n = clamp(lengths, 0, T) samples: y = a x + b z +
+    dither g, where a is a gain drawn from `gain` (dB, in steps of 1 / 256 dB), z the samples of a clip k of the noise bank from a
+    drawn offset on, looping, b = sqrt(Ex / En) 10^(-snr / 20) a with the SNR drawn from `snr` and both energies taken over the
+    row's own n samples, in a share noise_prob of the rows, and g an approximately normal variate per sample (Irwin-Hall of
+    eight 16-bit words, unit variance, cut at 4.9 sigma; added to the waveform once, not per frame as Kaldi does). Every sample
+    from n on is pad_value, whatever the input holds there. The random words are Philox4x32-10 keyed by `seed` at a counter made
+    of the row's identity (ids[r], or row_base + r) and a stream number apart from SpecAugment's, so an utterance's augmentation
+    depends on (seed, identity, n) and the bank only: not on its place in the batch, nor on the rows around it. With gain (0, 0),
+    no noise, no dither and no clamp a sample is 1.0 * x: its own bits, but a signalling NaN comes out quiet. ValueError, before
+    any HIP call, for a range outside [-64, 64] dB, out of order or more than 64 dB wide, noise_prob outside [0, 1], a dither
+    that is negative or not finite. Single-caller, bound to one device and one stream. out_frames(T) is T."""
+
+    _CREATE, _DESTROY = "alacgpu_waveaug_create", "alacgpu_waveaug_destroy"
+    _LAST_MS, _SYNCHRONIZE = "alacgpu_waveaug_last_ms", "alacgpu_waveaug_synchronize"
+
+    def __init__(self, snr=(5, 20), gain=(0, 0), noise_prob=1.0, dither=0.0, clamp=False, pad_value=0.0, device=0):
+        super().__init__()
+        self.config = WaveAugConfig(*_waveaug_config(snr, gain, noise_prob, dither, clamp, pad_value))
+        self._create(device, ctypes.byref(self.config))
+
+    def out_frames(self, in_frames):
+        """in_frames itself: the pass keeps every sample; 0 on a closed handle."""
+        return int(in_frames) if self._h else 0
+
+    def waveaug_device(self, d_in, in_row_stride, rows, samples, d_lengths, seed, d_out, out_row_stride, d_noise=0, noise_row_stride=0,
+                       noise_rows=0, noise_samples=0, d_noise_lengths=0, row_base=0, d_ids=0, d_draws=0, d_stats=0, sync=True):
+        """alacgpu_waveaug_device: raw device pointers (ints; d_lengths, d_noise, d_noise_lengths, d_ids, d_draws and d_stats may be
+        0), strides in elements. Exactly the rows x samples elements of the output, the rows x 5 int32 of d_draws and the rows x
+        4 floats of d_stats are written; the output may be the input itself with the same stride and may not overlap it
+        otherwise, nor the bank. Runs on the handle's stream, which does not order against torch's: synchronize the input first."""
+        _check(self._lib.alacgpu_waveaug_device(self._h, d_in, int(in_row_stride), rows, samples, d_lengths or None, d_noise or None,
+                                                int(noise_row_stride), noise_rows, noise_samples, d_noise_lengths or None,
+                                                _specaug_u64(seed, "seed"), _specaug_u64(row_base, "row_base"), d_ids or None, d_out,
+                                                int(out_row_stride), d_draws or None, d_stats or None, 1 if sync else 0))
+
+    def plan(self):
+        """alacgpu_waveaug_plan -> dict: the parameters, tile (the samples of a chunk of the energy sums), draws (5), lds_bytes,
+        the scratch block as it stands, and the two tables snr_amp and gain_amp (float32 numpy arrays)."""
+        info = WaveAugInfo()
+        snr, gain = _fetch_plan(self._lib.alacgpu_waveaug_plan, self._h, info, lambda i: np.zeros(i.snr_entries, np.float32),
+                                lambda i: np.zeros(i.gain_entries, np.float32))
+        out = {k: (float if k in ("dither", "pad_value") else int)(getattr(info, k)) for k, _ in WaveAugInfo._fields_ if k != "reserved"}
+        out.update(snr_amp=snr, gain_amp=gain)
+        return out
+
+    def __call__(self, clips, lengths=None, seed=0, noise=None, noise_lengths=None, ids=None, row_base=0, out=None, return_draws=False,
+                 return_stats=False):
+        """A float32 tensor or numpy array [..., T] -> the augmented tensor [..., T] on the handle's device, new and contiguous or
+        `out`. A tensor whose leading dimensions flatten without a copy and whose samples are contiguous is used on its own row
+        stride (clips[:, 0] of load_clips' [B, channels, L] included); anything else is made contiguous first. lengths: None
+        (every sample is valid) or one integer per row. seed: the step's, a uint64. noise: None, or a float32 bank [N, Tn] with
+        noise_lengths (None, or one integer per clip). ids: None, or one int64 per row, the utterance's identity; without it row
+        r of the flattened leading dimensions is row_base + r. out: a float32 tensor of clips' shape on the device, which may be
+        clips itself (in place) and may not share memory with it otherwise, nor with the bank. return_draws: also int32 [..., 5]:
+        applied, k, o, the SNR and the gain in 1 / 256 dB. return_stats: also float32 [..., 4]: Ex, En, a, b."""
+        import torch
+        if not self._h:
+            raise ValueError("the handle is closed")
+        _float32_input(clips)
+        seed, row_base = _specaug_u64(seed, "seed"), _specaug_u64(row_base, "row_base")
+        dev = torch.device("cuda", self.device)
+        same = out is clips
+        if same and (not isinstance(clips, torch.Tensor) or clips.device != dev):
+            raise ValueError("in place needs a tensor on the handle's device")
+        x = (torch.from_numpy(np.ascontiguousarray(clips)) if isinstance(clips, np.ndarray) else clips).to(dev)
+        lead, T = tuple(x.shape[:-1]), int(x.shape[-1])
+        rows = int(np.prod(lead, dtype=np.int64))
+        if out is not None and not same and (not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or
+                                             tuple(out.shape) != tuple(x.shape) or out.device != dev):
+            raise ValueError("out must be a float32 tensor of shape %r on the handle's device" % (tuple(x.shape),))
+        xv, xs = _wave_rows(x, rows)
+        if xv is None:
+            if same:
+                raise ValueError("in place needs a tensor whose rows flatten without a copy and whose samples are contiguous")
+            xv, xs = _wave_rows(x.contiguous(), rows)
+        if same:
+            y, yv, ys = clips, xv, xs
+        else:
+            y = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev) if out is None else out
+            yv, ys = _wave_rows(y, rows)
+            if yv is None:
+                raise ValueError("out needs rows that flatten without a copy and contiguous samples")
+        ln = _FeaturePass._lengths(lengths, rows, dev)
+        nz, nzs, nl = None, 0, None
+        if noise is not None:
+            _float32_input(noise)
+            nz = (torch.from_numpy(np.ascontiguousarray(noise)) if isinstance(noise, np.ndarray) else noise).to(dev)
+            if nz.ndim != 2:
+                raise ValueError("noise is a float32 bank [N, Tn]")
+            nv, nzs = _wave_rows(nz, int(nz.shape[0]))
+            if nv is None:
+                nz = nz.contiguous()
+                nv, nzs = _wave_rows(nz, int(nz.shape[0]))
+            nl = _FeaturePass._lengths(noise_lengths, int(nz.shape[0]), dev)
+        elif noise_lengths is not None:
+            raise ValueError("noise_lengths without a noise bank")
+        idv = None
+        if ids is not None:
+            idv = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+            if idv.numel() != rows or idv.dtype.is_floating_point or idv.dtype is torch.bool:
+                raise ValueError("ids holds one integer per row: %d, not %d" % (rows, idv.numel()))
+            idv = idv.to(dev, torch.int64).contiguous().reshape(rows)
+        draws = torch.zeros((rows, 5), dtype=torch.int32, device=dev) if return_draws else None
+        stats = torch.zeros((rows, 4), dtype=torch.float32, device=dev) if return_stats else None
+        if rows and T:
+            torch.cuda.synchronize(dev)  # the handle's stream does not order against torch's
+            has_bank = nz is not None and nz.numel() > 0
+            self.waveaug_device(xv.data_ptr(), xs, rows, T, 0 if ln is None else ln.data_ptr(), seed, yv.data_ptr(), ys,
+                                nz.data_ptr() if has_bank else 0, nzs, int(nz.shape[0]) if has_bank else 0,
+                                int(nz.shape[1]) if has_bank else 0, 0 if nl is None or not has_bank else nl.data_ptr(), row_base,
+                                0 if idv is None else idv.data_ptr(), draws.data_ptr() if return_draws else 0,
+                                stats.data_ptr() if return_stats else 0, sync=True)
+        res = (y,) + ((draws.reshape(lead + (5,)),) if return_draws else ()) + ((stats.reshape(lead + (4,)),) if return_stats else ())
+        return res if len(res) > 1 else y
+
+
+def NewWaveAugment(snr=(5, 20), gain=(0, 0), noise_prob=1.0, dither=0.0, clamp=False, pad_value=0.0, device=0):
+    """A WaveAugment (context manager); ValueError where no plan can be built."""
+    return WaveAugment(snr, gain, noise_prob, dither, clamp, pad_value, device)
+
+
+_WAVEAUGS = {}  # (device, the eight fields of the configuration) -> WaveAugment
+
+
+def augment_waveform(clips, lengths=None, seed=_NO_SEED, noise=None, noise_lengths=None, snr=(5, 20), noise_prob=1.0, gain=(0, 0),
+                     dither=0.0, clamp=False, pad_value=0.0, ids=None, row_base=0, out=None, return_draws=False, return_stats=False,
+                     device=None):
+    """WaveAugment(snr, gain, ...)(clips, lengths, seed, noise, noise_lengths, ids, row_base, out, return_draws, return_stats) with
+    the handle of a (device, parameter set) made once and kept: clips a float32 tensor [..., T] on cuda:`device` (default: the
+    tensor's own, cuda:0 for a CPU tensor or a numpy array, which is uploaded). seed is required: a default would give every
+    training step the same noise."""
+    if seed is _NO_SEED:
+        raise ValueError("augment_waveform needs a seed: the step's, so that no two steps draw the same noise")
+    _float32_input(clips)
+    _, device = _on_device(clips, device)
+    fields = _waveaug_config(snr, gain, noise_prob, dither, clamp, pad_value)
+    key = (device,) + fields[:5] + (np.float32(fields[5]).tobytes(), fields[6], np.float32(fields[7]).tobytes())
+    wa = _cached(_WAVEAUGS, key, lambda: WaveAugment(snr, gain, noise_prob, dither, clamp, pad_value, device))
+    return wa(clips, lengths, seed, noise, noise_lengths, ids, row_base, out, return_draws, return_stats)
+
+
 def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="fbank", norm="mean", channel=0, transform="direct",
-                  device=0, deltas=0, delta_window=2, context=(0, 0), subsample=1, augment=None, **kaldi_kwargs):
+                  device=0, deltas=0, delta_window=2, context=(0, 0), subsample=1, augment=None, wave_augment=None, **kaldi_kwargs):
     """Files to normalised features in one call: load_clips(sources, frame_offsets, num_frames, sample_rate=sample_rate) -> the
     channel `channel` -> kaldi_fbank (kind "fbank") or kaldi_mfcc ("mfcc") with kaldi_kwargs (torchaudio's names; frames layout)
     -> kaldi_frame_counts of load_clips' lengths -> FeatureNorm(stat=norm: "mean", "mean_var" or None, which only masks).
@@ -2020,7 +2232,10 @@ def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="f
     and frame_lengths its out_lengths. With the defaults that pass is not run.
     augment: None, or a dict of spec_augment's keywords that must hold `seed` (and may hold ids, row_base, the mask and warp
     parameters, mask_value): SpecAugment runs between the normalisation and the stacking, so its masks fall on the
-    features' own bins and frames, and behind norm "mean" a mask_value of 0 is the row's mean. With None nothing runs."""
+    features' own bins and frames, and behind norm "mean" a mask_value of 0 is the row's mean. With None nothing runs.
+    wave_augment: None, or a dict of augment_waveform's keywords that must hold `seed` (and may hold noise, noise_lengths, snr,
+    noise_prob, gain, dither, clamp, ids, row_base): the waveform augmentation runs on the chosen channel over load_clips'
+    lengths, in front of the feature pass, with a pad_value of 0, which the feature pass relies on. With None nothing runs."""
     try:
         left, right = context
     except (TypeError, ValueError):
@@ -2031,6 +2246,12 @@ def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="f
         for k in ("feats", "lengths", "layout", "out", "out_layout", "return_draws", "device", "pad_value"):
             if k in augment:
                 raise ValueError("%s is not a key of augment" % k)
+    if wave_augment is not None:
+        if not isinstance(wave_augment, dict) or "seed" not in wave_augment:
+            raise ValueError("wave_augment is a dict of augment_waveform's keywords that holds 'seed'")
+        for k in ("clips", "lengths", "out", "return_draws", "return_stats", "device", "pad_value"):
+            if k in wave_augment:
+                raise ValueError("%s is not a key of wave_augment" % k)
     stacked = (_stack_int(deltas, "deltas", 0, 2), _stack_int(left, "context left", 0, 16), _stack_int(right, "context right", 0, 16),
                _stack_int(subsample, "subsample", 1, 64)) != (0, 0, 0, 1)
     if kind not in ("fbank", "mfcc"):
@@ -2043,8 +2264,11 @@ def load_features(sources, frame_offsets, num_frames, sample_rate=16000, kind="f
     clips, lengths, rate = load_clips(sources, frame_offsets, num_frames, device=device, sample_rate=sample_rate)
     if not 0 <= int(channel) < clips.shape[1]:
         raise ValueError("channel %d of %d" % (channel, clips.shape[1]))
-    feats = (kaldi_fbank if kind == "fbank" else kaldi_mfcc)(clips[:, int(channel)], sample_frequency=rate, device=device,
-                                                            transform=transform, **kaldi_kwargs)
+    wave = clips[:, int(channel)]
+    if wave_augment is not None:
+        wave = augment_waveform(wave, lengths, device=device, **wave_augment)
+    feats = (kaldi_fbank if kind == "fbank" else kaldi_mfcc)(wave, sample_frequency=rate, device=device, transform=transform,
+                                                            **kaldi_kwargs)
     W = int(rate * kaldi_kwargs.get("frame_length", 25.0) * 0.001)
     h = int(rate * kaldi_kwargs.get("frame_shift", 10.0) * 0.001)
     counts = kaldi_frame_counts(lengths, W, h, kaldi_kwargs.get("snip_edges", True))
