@@ -63,7 +63,7 @@ int waveaug_sim_run(const int32_t* cfg, float dither, float pad_value, const flo
         !scratch_floats_of(rows, T, p.reduce != 0u, stats == nullptr, &floats))
         return -2;
     std::vector<float> scratch(floats);
-    memset(scratch.data(), 0xFF, floats * sizeof(float)); /* NaN wherever a kernel reads what none wrote */
+    if (floats) memset(scratch.data(), 0xFF, floats * sizeof(float)); /* NaN wherever a kernel reads what none wrote */
     set_scratch(&p, scratch.data());
     std::vector<float> lds(kLdsFloats);
     const auto each = [](auto&& phase) {

@@ -62,21 +62,30 @@ def new_waveaug(pkg, cfg, dither=0.0, pad_value=0.0):
     return h
 
 
-def hold_to_host(got, want, x, lengths, cfg, bank, bl, what, **kw):
+def hold_to_host(got, want, x, lengths, cfg, bank, bl, what, nan_ok=False, host_output=False, **kw):
     """(y, draws, stats) of the device against the host build's: draws, Ex, En and a bit for bit, b within B_TOL, the output bit
-    for bit against the formula over the device's own stats -> whether b is equal too"""
+    for bit against the formula over the device's own stats -> whether b is equal too. nan_ok: where the host build has a NaN
+    the device has one, of whatever sign and payload (inputs that hold NaN or overflow). host_output: where all four stats are
+    the host build's bit for bit, the formula over them is the host build's own output (the CPU suite holds it to that), so
+    the output is compared with it and the formula is not worked out again (rows of millions of samples)"""
     y, draws, stats = got
+    same = wa.same_or_nan if nan_ok else wa.same_bits
     assert np.array_equal(draws, want[1]), "draws: " + what
-    assert wa.same_bits(stats[:, :3], want[2][:, :3]), "Ex, En, a: " + what
+    assert same(stats[:, :3], want[2][:, :3]), "Ex, En, a: " + what
     b, wb = stats[:, 3].astype(np.float64), want[2][:, 3].astype(np.float64)
     assert ((b == 0) == (wb == 0)).all() and (np.abs(b - wb) <= B_TOL * np.abs(wb)).all(), "b: " + what
-    assert wa.same_bits(y, wa.formula(x, lengths, cfg, SEED, draws, stats, bank, bl, **kw)), "output: " + what
-    return wa.same_bits(stats[:, 3], want[2][:, 3])
+    equal = wa.same_bits(stats[:, 3], want[2][:, 3])
+    if host_output and equal:
+        assert same(y, want[0]), "output: " + what
+    else:
+        assert same(y, wa.formula(x, lengths, cfg, SEED, draws, stats, bank, bl, **kw)), "output: " + what
+    return equal
 
 
-def device_run(torch, h, x, lengths, bank, bank_lengths, k, in_place, row_base=0, ids=None):
+def device_run(torch, h, x, lengths, bank, bank_lengths, k, in_place, row_base=0, ids=None, want_draws=True, want_stats=True):
     """The pass over x and the bank laid out at odd offsets with gaps and poison, through waveaug_device -> (y, draws, stats) as
-    numpy; asserts that nothing but the output's elements and the rows' draws and stats changed"""
+    numpy, None for draws or stats where the pass gets no block for them (d_draws = 0, d_stats = 0); asserts that nothing but the
+    output's elements and the rows' draws and stats changed"""
     rows, T = x.shape
     poison = (F32(np.nan), F32(np.inf), F32(-np.inf), F32(1e30))[k % 4]
     xin = x.copy()
@@ -112,7 +121,8 @@ def device_run(torch, h, x, lengths, bank, bank_lengths, k, in_place, row_base=0
     torch.cuda.synchronize()
     h.waveaug_device(d_in.data_ptr() + 4 * lead, rs, rows, T, 0 if d_len is None else d_len.data_ptr(), SEED, d_out.data_ptr() + 4 * olead,
                      ors, 0 if d_bank is None else d_bank.data_ptr() + 4 * nlead, nrs, N, Tn, 0 if d_nl is None else d_nl.data_ptr(),
-                     row_base, 0 if d_ids is None else d_ids.data_ptr(), d_draws.data_ptr() + 4 * 5, d_stats.data_ptr() + 4 * 4, sync=True)
+                     row_base, 0 if d_ids is None else d_ids.data_ptr(), d_draws.data_ptr() + 4 * 5 if want_draws else 0,
+                     d_stats.data_ptr() + 4 * 4 if want_stats else 0, sync=True)
     assert h.last_ms() > 0
     got, draws, stats = d_out.cpu().numpy(), d_draws.cpu().numpy(), d_stats.cpu().numpy()
     if in_place:
@@ -123,8 +133,10 @@ def device_run(torch, h, x, lengths, bank, bank_lengths, k, in_place, row_base=0
         assert rest.size and (bits(rest) == bits(CANARY)).all(), "an element outside the output was written"
     assert (draws[0] == -77).all() and (draws[-1] == -77).all(), "a draw outside the rows' was written"
     assert (bits(stats[0]) == bits(CANARY)).all() and (bits(stats[-1]) == bits(CANARY)).all(), "a stat outside the rows' was written"
+    assert want_draws or (draws == -77).all(), "draws were written without a block for them"
+    assert want_stats or (bits(stats) == bits(CANARY)).all(), "stats were written without a block for them"
     y = np.lib.stride_tricks.as_strided(got[olead:], x.shape, (4 * ors, 4)).copy()
-    return y, draws[1:-1], stats[1:-1]
+    return y, draws[1:-1] if want_draws else None, stats[1:-1] if want_stats else None
 
 
 # ---- 1. the three kernels against the host build over the CPU suite's grid --------------------------------------------------
@@ -187,9 +199,21 @@ def test_in_place_channels_ids_and_the_functional_entry(torch, pkg, sim):
         work = d_clips.clone()
         lane = work[:, 1]
         assert h(lane, lengths, SEED, noise=d_bank, noise_lengths=bl, row_base=40, out=lane) is lane
-        both = work.clone()
-        y2 = h(both, None, SEED, noise=d_bank, noise_lengths=bl, out=both)
-        assert y2 is both and not torch.equal(both, work)
+        # [B, channels, L] in place: row r of the flattened leading dimensions is row_base + r, draws and stats come back per
+        # leading dimension; against the same data as [B * channels, L] and against the host build
+        both, flat, every = work.clone(), work.reshape(B * C, L), [L, 700, 0, 4097, 1, L - 1, 4096, 333]
+        y2, draws2, stats2 = h(both, every, SEED, noise=d_bank, noise_lengths=bl, row_base=40, out=both, return_draws=True,
+                               return_stats=True)
+        assert y2 is both and tuple(draws2.shape) == (B, C, 5) and tuple(stats2.shape) == (B, C, 4)
+        y1, draws1, stats1 = h(flat, every, SEED, noise=d_bank, noise_lengths=bl, row_base=40, return_draws=True, return_stats=True)
+        assert tuple(y1.shape) == (B * C, L) and tuple(draws1.shape) == (B * C, 5) and tuple(stats1.shape) == (B * C, 4)
+        assert torch.equal(both.reshape(B * C, L).view(torch.int32), y1.view(torch.int32)) and torch.equal(draws2.reshape(B * C, 5), draws1)
+        assert torch.equal(stats2.reshape(B * C, 4).view(torch.int32), stats1.view(torch.int32))
+        rows = flat.cpu().numpy()
+        hold_to_host((y1.cpu().numpy(), draws1.cpu().numpy(), stats1.cpu().numpy()), wa.host_values(sim, rows, every, cfg, SEED, bank, bl,
+                                                                                                    row_base=40),
+                     rows, every, cfg, bank, bl, "[B, channels, L]", row_base=40)
+        assert len({tuple(d) for d in draws1.tolist()}) == B * C, "every row its own draws"
         chan = d_clips[:, 1].clone()
         assert h(chan, lengths, SEED, noise=d_bank, noise_lengths=bl, row_base=40, out=chan) is chan
         # ids against row_base: a row's augmentation is its identity's, wherever it stands in the batch

@@ -76,9 +76,10 @@ def test_plan_tables_are_the_doubles_rounded_once(sim):
 
 
 # ---- 2. bit for bit against the numpy restatement: offsets, gaps, poisoned padding, canaries ------------------------------
-def run_over_buffers(sim, x, lengths, cfg, dither, bank, bank_lengths, k, in_place):
+def run_over_buffers(sim, x, lengths, cfg, dither, bank, bank_lengths, k, in_place, row_base=11, want_draws=True, want_stats=True):
     """x and the bank laid out at odd offsets with gaps, poison behind n_r and m_k and in the gaps -> (y, draws, stats) of the host
-    build; asserts that nothing but the output's elements, the rows' draws and the rows' stats changed"""
+    build, None for draws or stats that the pass is not given a block for; asserts that nothing but the output's elements, the
+    rows' draws and the rows' stats changed"""
     rows, T = x.shape
     poison = (F32(np.nan), F32(np.inf), F32(-np.inf), F32(1e30))[k % 4]
     xin = x.copy()
@@ -102,7 +103,8 @@ def run_over_buffers(sim, x, lengths, cfg, dither, bank, bank_lengths, k, in_pla
     before = buf.copy()
     draws, stats = np.full((rows + 2, 5), -77, np.int32), np.full((rows + 2, 4), CANARY, F32)
     rc = wa.host_run(sim, cfg, buf.ctypes.data + 4 * off, rs, rows, T, lengths, SEED, obuf.ctypes.data + 4 * ooff, ors, nptr, nrs, N, Tn,
-                     bank_lengths, draws[1:], stats[1:], row_base=11, dither=dither, pad_value=-3.5)
+                     bank_lengths, draws[1:] if want_draws else None, stats[1:] if want_stats else None, row_base=row_base, dither=dither,
+                     pad_value=-3.5)
     assert rc == 0
     if in_place:
         assert np.array_equal(bits(wa.outside(buf, off, x.shape, rs)), bits(wa.outside(before, off, x.shape, rs))), "a gap was written"
@@ -113,7 +115,9 @@ def run_over_buffers(sim, x, lengths, cfg, dither, bank, bank_lengths, k, in_pla
     assert (draws[0] == -77).all() and (draws[-1] == -77).all(), "exactly rows x 5 draws are written"
     assert (bits(stats[0]) == bits(CANARY)).all() and (bits(stats[-1]) == bits(CANARY)).all(), "exactly rows x 4 stats are written"
     y = np.lib.stride_tricks.as_strided(obuf[ooff:], x.shape, (4 * ors, 4)).copy()
-    return y, draws[1:-1], stats[1:-1]
+    assert want_draws or (draws == -77).all(), "draws were written without a block for them"
+    assert want_stats or (bits(stats) == bits(CANARY)).all(), "stats were written without a block for them"
+    return y, draws[1:-1] if want_draws else None, stats[1:-1] if want_stats else None
 
 
 def banks_of(rng, name):
@@ -291,7 +295,7 @@ def test_energies_against_float64(sim):
     fraction of the bound"""
     rng = np.random.default_rng(9)
     worst = 0.0
-    for T in (1, 255, 256, 257, TILE - 1, TILE, TILE + 1, 2 * TILE + 3, 9 * TILE + 100):
+    for T in (1, 255, 256, 257, TILE - 1, TILE, TILE + 1, 2 * TILE + 3, 9 * TILE + 100, 257 * TILE + 100):
         x = (rng.standard_normal((4, T)) * np.array([[1e-3], [1.0], [30.0], [0.3]])).astype(F32)
         x[3] = np.abs(x[3]) + 0.2  # no cancellation, nothing that hides an error
         bank = wa.waves(rng, 1, 777, 0.2)
@@ -413,7 +417,8 @@ def test_standalone_program_builds_and_runs(tmp_path):
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     print(r.stdout)
     assert r.returncode == 0, r.stdout
-    assert r.stdout.count("-> 0,") == 90 and "90 passes" in r.stdout and "nan" not in r.stdout.lower()
+    assert r.stdout.count("-> 0,") == 92 and "92 passes" in r.stdout and "nan" not in r.stdout.lower()
+    assert ": 0 of the passes" not in r.stdout, "a combination of bank, stats and draws never ran"
 
 
 # ---- 8. the names --------------------------------------------------------------------------------------------------------

@@ -18,8 +18,12 @@ cfg = (snr_lo_q8, snr_hi_q8, gain_lo_q8, gain_hi_q8, noise_prob_q16, clamp) with
 * g_t: the block's halves h0 .. h7 (low half of word 0 first), s = (h0 + h1 + h2 + h3) - (h4 + h5 + h6 + h7), g = float32(s) * KSCALE.
 
 fma32 is stack_ref's correctly rounded float32 fused multiply-add, so the host build, whose fmaf is the C library's, must give
-these bits."""
+these bits; fma here hands it the finite operands and rounds the double a b + c where one is infinite or NaN.
+
+The shared cases of the second look (tests/test_waveaug_paths_host.py holds the host build to reference() over them,
+tests/test_gpu_waveaug_paths.py the kernels to the host build): long_rows_case, clip_case, edge_cases."""
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -36,6 +40,7 @@ LANES = 256
 M64 = (1 << 64) - 1
 KSCALE = F32(1.0 / math.sqrt((2 ** 32 - 1) * 2.0 / 3.0))  # 0x1.3988e2p-16
 ROW_STREAM, DITHER_STREAM = 2, 3
+SEED = 0x1234_5678_9ABC_DEF1  # of the shared cases; the two test files use the same
 u64 = np.uint64
 MASK = u64(0xFFFFFFFF)
 
@@ -109,6 +114,25 @@ def draws_of(cfg, words, noise_rows, noise_T, noise_lengths):
 
 
 # ---- the energies --------------------------------------------------------------------------------------------------------
+def fma(a, b, c):
+    """fmaf over float32 arrays of one shape: fma32 where every operand is finite. fma32's error terms are NaN where one is not;
+    there the double a b + c, rounded, is fmaf's own answer: the product of two floats is exact in double and cannot overflow, so
+    the sum is an infinity or a NaN exactly where fmaf's is (which NaN is the platform's choice: compare with same_or_nan)"""
+    with np.errstate(all="ignore"):
+        r = fma32(a, b, c)
+        odd = ~(np.isfinite(a) & np.isfinite(b) & np.isfinite(c))
+        if odd.any():
+            r[odd] = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F32)[odd]
+    return r
+
+
+def same_or_nan(a, b):
+    """same_bits, but a NaN equals any NaN: x86 and gfx950 may differ in the sign and the payload of a NaN they generate"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
 def energy(v):
     """v float32 [n] -> the header's sum of squares, float32"""
     total = F32(0.0)
@@ -116,13 +140,14 @@ def energy(v):
         ch = v[c0:c0 + TILE]
         ch = np.concatenate([ch, np.zeros(-len(ch) % LANES, F32)]).reshape(-1, LANES)  # fma(0, 0, acc) is acc
         acc = np.zeros(LANES, F32)
-        for line in ch:
-            acc = fma32(line, line, acc)
-        s = LANES // 2
-        while s:
-            acc[:s] = acc[:s] + acc[s:2 * s]
-            s //= 2
-        total = F32(total + acc[0])
+        with np.errstate(all="ignore"):
+            for line in ch:
+                acc = fma(line, line, acc)
+            s = LANES // 2
+            while s:
+                acc[:s] = acc[:s] + acc[s:2 * s]
+                s //= 2
+            total = F32(total + acc[0])
     return total
 
 
@@ -149,7 +174,8 @@ def reference(x, lengths, cfg, seed, noise=None, noise_lengths=None, row_base=0,
         a = gain[gi]
         b = F32(0.0)
         if applied and ex > 0 and en > 0 and np.isfinite(ex) and np.isfinite(en):
-            b = F32(F32(np.sqrt(F32(ex / en))) * snr[si]) * a
+            with np.errstate(all="ignore"):
+                b = F32(F32(np.sqrt(F32(ex / en))) * snr[si]) * a
         stats[r] = (ex, en, a, b)
     return formula(x, lengths, cfg, seed, draws, stats, noise, noise_lengths, row_base, ids, dither, pad_value), draws, stats
 
@@ -168,9 +194,9 @@ def formula(x, lengths, cfg, seed, draws, stats, noise=None, noise_lengths=None,
             if b != 0:
                 k, o = int(draws[r][1]), int(draws[r][2])
                 m = noise.shape[1] if noise_lengths is None else min(max(int(noise_lengths[k]), 0), noise.shape[1])
-                out = fma32(np.full(n, b, F32), noise[k][(o + np.arange(n)) % m], out)
+                out = fma(np.full(n, b, F32), noise[k][(o + np.arange(n)) % m], out)
             if dither != 0:
-                out = fma32(np.full(n, dither, F32), dither_variates(seed, ident, np.arange(n)), out)
+                out = fma(np.full(n, dither, F32), dither_variates(seed, ident, np.arange(n)), out)
             if cfg[5]:
                 out = np.where(out < -1, F32(-1), np.where(out > 1, F32(1), out))
         y[r, :n] = out
@@ -198,6 +224,72 @@ def outside(buf, off, shape, rs):
 
 def waves(rng, rows, T, scale=0.3):
     return (scale * rng.standard_normal((rows, T))).astype(F32)
+
+
+# ---- the shared cases of the second look ---------------------------------------------------------------------------------
+# Each is a dict: x [rows, T], lengths, cfg, dither, bank, bl (the bank's lengths), row_base. They are built once per process.
+CLIP_LENGTHS = (3, 5, 100, 255, 256, 300, 1000, TILE - 1)
+LONG_T = 513 * TILE + 5
+SPECIALS = np.array([-0.0, 1.0, -1.0, np.nextafter(F32(1), F32(2)), np.nextafter(F32(-1), F32(-2))], F32)
+
+
+@functools.lru_cache(maxsize=None)
+def long_rows_case():
+    """Six rows of up to 513 chunks under the "all" set: the finish kernel walks the partials 256 chunks at a time, so the lengths
+    stand on both sides of its first and second block edge; o + t0 and the dither counters pass 2^21. row_base is the first at
+    which every row with a sample draws noise and both clips are drawn, found from the draws alone"""
+    rng = np.random.default_rng(4300)
+    cfg, dither = PARAMS["all"]
+    lengths = [LONG_T, 256 * TILE, 256 * TILE + 1, 0, 257 * TILE - 1, 512 * TILE + 1]
+    bl = [5000, 257]
+    for row_base in range(1000):
+        d = [draws_of(cfg, w, 2, 5000, bl) for w in row_words(SEED, [row_base + r for r in range(6)])]
+        if all(e[0] for e in d) and {e[1] for e in d} == {0, 1}:
+            break
+    return dict(x=waves(rng, 6, LONG_T), lengths=lengths, cfg=cfg, dither=dither, bank=waves(rng, 2, 5000, 0.1), bl=bl, row_base=row_base)
+
+
+@functools.lru_cache(maxsize=None)
+def clip_case(m):
+    """Both clips m samples long under a noise probability of 1, at T = 2 tile + 3: for m < tile every work item of stage_noise
+    walks the clip in steps of 256 mod m, chunk 1 starts at (o + 4096) mod m, and the last chunk is short"""
+    rng = np.random.default_rng(4200 + m)
+    T = 2 * TILE + 3
+    return dict(x=waves(rng, 6, T), lengths=lengths_of(T), cfg=(5 * 256, 20 * 256, -6 * 256, 3 * 256, 65536, 0), dither=0.0,
+                bank=waves(rng, 2, TILE, 0.1), bl=[m, m], row_base=11)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_cases(clamp):
+    """name -> case. Edge values inside the valid samples, under noise at probability 1, dither 0.01, clamp 0 / 1, T = tile + 7.
+    "rows": a bank of ordinary amplitude under rows of amplitude 1e-20 (the squares are subnormal, Ex is normal), 1e-23 (Ex is
+    subnormal), 3e19 (Ex = +Inf, so b = 0), an ordinary row with one NaN sample (Ex = NaN, b = 0, the sample stays NaN through the
+    clamp), one with a +Inf sample in its second chunk, and one that starts with -0.0, 1, -1 and the floats next above 1 and next
+    below -1. "bank ...": ordinary rows under one clip of amplitude 3e19, with a NaN sample, with a +Inf sample, with the
+    special values; "tiny ...": rows and clip both of amplitude 1e-20, and both 1e-23, so that En is built of subnormals too.
+    Left out on purpose: an ordinary row under a clip of amplitude around 1e-20. There sqrt(Ex / En) overflows, the header
+    yields b = +Inf by its own definition, and fma32 cannot take an infinite factor; no audio reaches that case"""
+    rng = np.random.default_rng(4100 + clamp)
+    T = TILE + 7
+    base = dict(cfg=(5 * 256, 20 * 256, -6 * 256, 3 * 256, 65536, clamp), dither=0.01, row_base=11)
+    x = waves(rng, 6, T)
+    x[0], x[1], x[2] = waves(rng, 1, T, 1e-20)[0], waves(rng, 1, T, 1e-23)[0], waves(rng, 1, T, 3e19)[0]
+    x[3, 1234], x[4, TILE + 4], x[5, :5] = np.nan, np.inf, SPECIALS
+    cases = {"rows": dict(base, x=x, lengths=[T, T - 1, T, T, T, 300], bank=waves(rng, 2, 3000, 0.1), bl=[3000, 257])}
+    plain, lengths, m = waves(rng, 6, T), [T, 700, T - 1, 257, T, 1000], 700
+    clips = {"bank 3e19": waves(rng, 1, m, 3e19), "bank nan": waves(rng, 1, m, 0.1), "bank inf": waves(rng, 1, m, 0.1),
+             "bank specials": waves(rng, 1, m, 0.1)}
+    clips["bank nan"][0, 333], clips["bank inf"][0, 400], clips["bank specials"][0, :5] = np.nan, np.inf, SPECIALS
+    for name, clip in clips.items():
+        cases[name] = dict(base, x=plain, lengths=lengths, bank=clip, bl=[m])
+    for scale in (1e-20, 1e-23):
+        cases["tiny %g" % scale] = dict(base, x=waves(rng, 6, T, scale), lengths=lengths, bank=waves(rng, 1, m, scale), bl=[m])
+    return cases
+
+
+def case_kw(case):
+    """The keywords of reference, formula and host_values that a case sets"""
+    return dict(row_base=case["row_base"], dither=case["dither"])
 
 
 # ---- the host build ------------------------------------------------------------------------------------------------------
